@@ -2,6 +2,7 @@
 """Headline benchmark: M-correspondences/s of the registration hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config plane_b01|icp_b01|icp_b01_harness|plane_b01_100k|vplane_10m|ndt_10m|plane_100m]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is ONE pass of the hot path -- one ``calc_H_g_e2``: float32 transform of the whole
 scan shard, exact nearest-neighbour search against the target, the ``dist < max_dist`` gate,
@@ -20,15 +21,25 @@ default) or ``gloo`` (host all-reduce: the agreed fallback transport, and what t
 ``--scaling weak`` (default): every rank owns a scan shard of the SAME size (its own perturbed scan);
 ``--scaling strong``: ONE scan of the configured size, rank r takes ``shard_scan(scan, r, N)``.
 
-Timing: ``--repeats R`` (default 5) timed blocks of exactly ``--steps`` passes each, every block
-bracketed by barrier + synchronize on both sides, max over ranks; ``ms_per_step`` / ``value`` are the
-MEDIAN block, min / max and all blocks are reported beside it.  HIP events bracket every 3rd pass of
-those blocks (an event pair costs microseconds of stream time); one further block with the events off
-is reported as ``ms_per_step_events_off``.
+Plain run (the default): set up (workload, target index, the trajectory), collect garbage, serve the target
+SETTLE_PASSES untimed passes along the trajectory (the library builds some search structures lazily after
+its first passes, and the GPU has idled through the collection: the timed steps see the steady state),
+``--warmup`` passes, then ONE timed block of exactly ``--steps`` passes, bracketed by barrier + synchronize
+on both sides, max over ranks; ``ms_per_step`` = block / steps, ``value`` = correspondences of the whole
+job per second.  Rank 0 prints one JSON line.
 
-Rank 0 prints one JSON line (contract in the task statement) with ``roofline`` (HIP-event kernel
-time measured here, live) and ``cpu_baseline`` (the CPU oracle on this box's host cores, bounded
-sample, N = 1 only).
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what the last timed step returned -- the
+Gauss-Newton normal equations a ``calc_H_g_e2`` caller receives -- as float64 ``DIR/H.npy`` (6x6),
+``DIR/g.npy`` (6), ``DIR/e2.npy`` and ``DIR/correspondences.npy``.  The inputs are seeded: the same
+arguments give the same workload on every run.
+
+``--full`` adds every secondary measurement to the line: ``--repeats R`` (default 5 with ``--full``)
+timed blocks whose MEDIAN gives ``ms_per_step`` / ``value``, min / max and all blocks beside it; HIP
+events around every 3rd pass of those blocks (an event pair costs microseconds of stream time) for
+``kernels`` and ``roofline`` (``roofline.traffic`` from two live ``rocprofv3 --pmc`` child runs); one
+further block with the events off (``ms_per_step_events_off``); the fresh-target numbers
+(``config.set_target_ms`` / ``first_align_ms``); and at N = 1 the one-rank RCCL / P2P probe, the class
+``seam`` and ``cpu_baseline`` (the CPU oracle on this box's host cores, bounded sample).
 """
 
 import argparse
@@ -51,6 +62,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+SETTLE_PASSES = 200             # untimed passes of a plain run before its warm-up (lazy list set after 12 point passes, filter index after 8)
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy ceiling ~6300
 B_ALG = {"icp": 24, "plane": 36, "vplane": 36, "ndt": 48}     # bytes / scan point / pass
 
@@ -103,7 +115,13 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-passes", type=int, default=3)
     ap.add_argument("--variant", type=int, default=None, help="0 fused kernel, 1 NN + reduce kernels, 2 per launch (default)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps passes; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary measurement: repeated blocks, per-kernel times and roofline, fresh-target "
+                         "numbers, communicator probes, the class seam and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (H, g, e2, correspondences) as float64 DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps passes; the median is reported (default 1, or 5 with --full)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--event-period", type=int, default=3, help="HIP events around every n-th pass")
     ap.add_argument("--no-pmc", action="store_true",
@@ -114,7 +132,10 @@ def parse():
                          "exchange; Registration(devices=[...])) instead of one rank per GPU; PCR_BENCH_GROUP_DEVICES=0,0 picks the ids")
     ap.add_argument("--backend", default=os.environ.get("PCR_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="torch.distributed backend of the N > 1 plumbing (barrier, max over ranks); nccl = RCCL")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def effective_cpus():
@@ -159,7 +180,7 @@ def live_traffic(args):
     if not os.path.exists(exe):
         return None, {"error": "rocprofv3 not found"}
     child = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", "10", "--warmup", "2", "--repeats", "1",
-             "--no-cpu-baseline", "--no-pmc", "--pmc-child"]
+             "--full", "--no-cpu-baseline", "--no-pmc", "--pmc-child"]
     if args.variant is not None:
         child += ["--variant", str(args.variant)]
     env = dict(os.environ, TMPDIR="/tmp", PCR_BENCH_NO_RCCL_PROBE="1")
@@ -390,7 +411,7 @@ def main():
     # passes: its second list set / filter index exist (built lazily after 12 / 8 passes); a fresh target's first align never
     # sees them.  Kernels are loaded by now, the scan is device-resident: this is the library's time, not the process start-up.
     first_align_ms = set_target_ms = first_align_iters = None
-    if n_target <= 20_000_000:
+    if args.full and n_target <= 20_000_000:
         ctx.synchronize()
         t0 = time.perf_counter()
         if kind_name in ("icp", "plane"):
@@ -423,14 +444,23 @@ def main():
             torch.distributed.barrier()
             torch.cuda.synchronize()
 
+    import gc
+    if not args.full:
+        # part of the set-up: collect first (the GPU idles through it, see below), then serve the target SETTLE_PASSES
+        # passes -- its lazily built structures exist and the GPU is busy again: the steady state that the median
+        # of --full's blocks reports
+        gc.collect()
+        gc.disable()
+        for k in range(SETTLE_PASSES):
+            step(k)
     for k in range(args.warmup):
         step(k)
     # With torch.cuda initialised the interpreter tracks ~1e6 objects and a generation-2 garbage
     # collection costs 35-50 ms -- a hundred passes' worth -- whenever the allocation counter trips
     # (measured: tools/latency_probe.py).  Collect now, keep the collector out of the timed region.
-    import gc
-    gc.collect()
-    gc.disable()
+    if args.full:
+        gc.collect()
+        gc.disable()
 
     def timed_block():
         """EXACTLY args.steps passes, barrier + synchronize on both sides, max over ranks."""
@@ -447,69 +477,43 @@ def main():
             dt = float(t.item())
         return dt, o
 
-    prof_ctx.profile_enable(True, period=args.event_period)
-    prof_ctx.profile_reset()
+    if args.full:
+        prof_ctx.profile_enable(True, period=args.event_period)
+        prof_ctx.profile_reset()
     blocks = []
     out = None
     for r in range(max(args.repeats, 1)):
         dt, out = timed_block()
         blocks.append(dt)
-    prof = prof_ctx.profile_read()
-    prof_ctx.profile_enable(False)
-    t_noev, _ = timed_block()                                  # the same block with the events off
+    prof = t_noev = None
+    if args.full:
+        prof = prof_ctx.profile_read()
+        prof_ctx.profile_enable(False)
+        t_noev, _ = timed_block()                              # the same block with the events off
     gc.enable()
     elapsed = float(np.median(blocks))
     step_t = [b / args.steps for b in blocks]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
 
     per_rank = None
-    if use_comm:                                                # every rank's own kernel / all-reduce times
+    if args.full and use_comm:                                  # every rank's own kernel / all-reduce times
         mine = {k: round(v[1] / v[0], 5) for k, v in prof.items() if v[0]}
         per_rank = [None] * world
         torch.distributed.all_gather_object(per_rank, mine)
     if rank == 0:
         units = n_scan_job * args.steps                     # correspondences searched, whole job
         value = units / elapsed / 1e6
-        kern = {k: {"launches": v[0], "avg_ms": v[1] / v[0]} for k, v in prof.items() if v[0]}
-        # dominant kernel(s) of one pass: everything that touches the scan / target
-        hot_ms = sum(kern[k]["avg_ms"] for k in ("linearize", "nn", "reduce") if k in kern)
-        shard_n = sc.n // world if sp else sc.n             # points one launch of the profiled context processes
-        alg_bytes = B_ALG[kind_name] * shard_n              # per launch (one pass over this rank's / member's shard)
-        achieved = alg_bytes / (hot_ms * 1e-3) / 1e9
-        # HBM traffic per pass from the PMC passes of the SAME command (profiles/pmc_summary.json, collected
-        # as MI355X_MICROARCH.md prescribes: separate --pmc runs, FETCH_SIZE x2); only trusted when that
-        # profile was taken on these very kernels (hash of the HIP sources), otherwise null
-        traffic, traffic_src = None, None
-        pmc_file = os.path.join(REPO, "profiles", "pmc_summary.json")
-        if world == 1 and not args.no_pmc and not args.pmc_child and not os.environ.get("PCR_BENCH_NO_PMC"):
-            traffic, traffic_src = live_traffic(args)
-        if traffic is None and os.path.exists(pmc_file):
-            live_err = traffic_src
-            try:
-                pm = json.load(open(pmc_file))
-                entry = pm.get(args.config, {})
-                if pm.get("kernel_source_hash") == kernel_source_hash():
-                    traffic = entry.get("hbm_bytes_per_pass")
-                    traffic_src = {"file": "profiles/pmc_summary.json", "collected_at_commit": pm.get("commit"),
-                                   "kernel_source_hash": pm.get("kernel_source_hash"), "raw": entry.get("source")}
-                else:
-                    traffic_src = {"file": "profiles/pmc_summary.json", "stale": True,
-                                   "note": "PMC profile predates the current kernels; traffic withheld"}
-            except Exception:
-                traffic = None
-            if live_err and isinstance(traffic_src, dict):
-                traffic_src["live_attempt"] = live_err
         line = {
             "metric": "M-correspondences/sec, %s calc_H_g_e2 on the B-01 stand-in (1.06 M pts)" % kind_name
                       if "b01" in args.config else "M-correspondences/sec, %s calc_H_g_e2" % kind_name,
             "value": round(value, 3), "unit": "Mcorr/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "settle_passes": 0 if args.full else SETTLE_PASSES,    # untimed passes of the set-up, before the warm-up
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "iterations_per_sec": round(args.steps / elapsed, 2),
-            "ms_per_step_min": round(min(step_t) * 1e3, 4), "ms_per_step_max": round(max(step_t) * 1e3, 4),
-            "repeat_ms_per_step": [round(t * 1e3, 4) for t in step_t], "repeats": len(blocks),
-            "ms_per_step_events_off": round(t_noev / args.steps * 1e3, 4), "event_period": args.event_period,
+            "iterations_per_sec": round(args.steps / elapsed, 2), "repeats": len(blocks),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32", "accumulate_dtype": "f64", "data": data_tag,
+            "dtype": "f32", "accumulate_dtype": "f64", "data": data_tag, "full": bool(args.full),
             "config": {"workload": args.config, "description": desc, "kind": kind_name,
                        "target_points": int(n_target), "scan_points_per_gpu": int(sc.n // world if sp else sc.n),
                        "max_dist": max_dist, "voxel_size": voxel_size,
@@ -526,44 +530,98 @@ def main():
                                     "cell_population_max": info.get("pop_max"), "cell_population_p99": info.get("pop_p99"),
                                     "heavy_cells_index": info.get("heavy")},
                        "gauss_newton_iters_to_converge": iters, "pose_error_m": round(pose_err, 6),
-                       "first_align_ms": None if first_align_ms is None else round(first_align_ms, 3),
-                       "first_align_iterations": first_align_iters,
-                       "set_target_ms": None if set_target_ms is None else round(set_target_ms, 3),
-                       "first_align_note": "fresh target (no second list set / filter index yet), one align of the device-resident "
-                                           "scan: the reference's protocol; `value` is the steady state of a target that has served "
-                                           "dozens of passes",
                        "correspondences_last_step": int(out[28]), "setup_s": round(t_setup, 2)},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "+".join(k for k in ("linearize", "nn", "reduce") if k in kern),
-                         "kernel_ms": round(hot_ms, 5), "algorithmic_bytes_per_launch": int(alg_bytes),
-                         "bytes_per_point": B_ALG[kind_name]},
-            "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["avg_ms"], 5)} for k, v in kern.items()},
         }
-        if "reduce" in kern:
-            # SURVEY.md section 8d asks for the streaming kernel on its own: B_alg + the 4-byte index per point
-            k2 = (B_ALG[kind_name] + 4) * shard_n / (kern["reduce"]["avg_ms"] * 1e-3) / 1e9
-            line["roofline_reduce_kernel"] = {"bound": "hbm", "achieved": round(k2, 3), "peak": HBM_PEAK_GBS,
-                                              "unit": "GB/s", "frac": round(k2 / HBM_PEAK_GBS, 6),
-                                              "bytes_per_point": B_ALG[kind_name] + 4,
-                                              "kernel_ms": round(kern["reduce"]["avg_ms"], 5)}
-        if per_rank is not None:
-            line["per_rank_kernel_ms"] = per_rank
-        if world == 1 and not use_comm and not os.environ.get("PCR_BENCH_NO_RCCL_PROBE") and not args.pmc_child:
-            one = rccl_one_rank_probe(ctx, step, args.steps, sync_all)
-            line["rccl_1rank"] = one.get("rccl", one)                 # in-stream exchange with ONE rank attached: everything but the hops
-            line["p2p_1rank"] = one.get("p2p", one)                   # ... and the same for the peer-to-peer transport (PCR_COMM=p2p)
-        if world == 1 and not args.pmc_child:
-            line["seam"] = seam_timings(kind_name, target, scan, tgt, sc, kind, traj, max_dist, voxel_size, n_target)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(kind_name, target, scan, tgt, traj, max_dist, voxel_size,
-                                                args.cpu_passes)
+        if args.full:
+            line.update(full_measurements(args, line, prof, step_t, t_noev, kind_name, sc, sp, world))
+            line["config"].update({
+                "first_align_ms": None if first_align_ms is None else round(first_align_ms, 3),
+                "first_align_iterations": first_align_iters,
+                "set_target_ms": None if set_target_ms is None else round(set_target_ms, 3),
+                "first_align_note": "fresh target (no second list set / filter index yet), one align of the device-resident "
+                                    "scan: the reference's protocol; `value` is the steady state of a target that has served "
+                                    "dozens of passes"})
+            if per_rank is not None:
+                line["per_rank_kernel_ms"] = per_rank
+            if world == 1 and not use_comm and not os.environ.get("PCR_BENCH_NO_RCCL_PROBE") and not args.pmc_child:
+                one = rccl_one_rank_probe(ctx, step, args.steps, sync_all)
+                line["rccl_1rank"] = one.get("rccl", one)             # in-stream exchange with ONE rank attached: everything but the hops
+                line["p2p_1rank"] = one.get("p2p", one)               # ... and the same for the peer-to-peer transport (PCR_COMM=p2p)
+            if world == 1 and not args.pmc_child:
+                line["seam"] = seam_timings(kind_name, target, scan, tgt, sc, kind, traj, max_dist, voxel_size, n_target)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(kind_name, target, scan, tgt, traj, max_dist, voxel_size,
+                                                    args.cpu_passes)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if comm is not None:
         torch.distributed.barrier()
         comm.close()
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(d, out):
+    """What the last timed step returned, as a ``calc_H_g_e2`` caller receives it: float64 H (6x6), g (6), e2 and the
+    number of correspondences, one ``<name>.npy`` each."""
+    from point_cloud_registration_amd._capi import unpack29
+    os.makedirs(d, exist_ok=True)
+    H, g, e2, count = unpack29(out)
+    for name, a in (("H", H), ("g", g), ("e2", e2), ("correspondences", count)):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def full_measurements(args, line, prof, step_t, t_noev, kind_name, sc, sp, world):
+    """The ``--full`` fields of the line: spread of the repeated blocks, the events-off block, per-kernel HIP-event
+    times and the roofline (with the live PMC traffic)."""
+    kern = {k: {"launches": v[0], "avg_ms": v[1] / v[0]} for k, v in prof.items() if v[0]}
+    # dominant kernel(s) of one pass: everything that touches the scan / target
+    hot_ms = sum(kern[k]["avg_ms"] for k in ("linearize", "nn", "reduce") if k in kern)
+    shard_n = sc.n // world if sp else sc.n             # points one launch of the profiled context processes
+    alg_bytes = B_ALG[kind_name] * shard_n              # per launch (one pass over this rank's / member's shard)
+    achieved = alg_bytes / (hot_ms * 1e-3) / 1e9
+    # HBM traffic per pass from the PMC passes of the SAME command (profiles/pmc_summary.json, collected in
+    # separate --pmc runs, FETCH_SIZE x2); only trusted when that profile was taken on these very kernels
+    # (hash of the HIP sources), otherwise null
+    traffic, traffic_src = None, None
+    pmc_file = os.path.join(REPO, "profiles", "pmc_summary.json")
+    if world == 1 and not args.no_pmc and not args.pmc_child and not os.environ.get("PCR_BENCH_NO_PMC"):
+        traffic, traffic_src = live_traffic(args)
+    if traffic is None and os.path.exists(pmc_file):
+        live_err = traffic_src
+        try:
+            pm = json.load(open(pmc_file))
+            entry = pm.get(args.config, {})
+            if pm.get("kernel_source_hash") == kernel_source_hash():
+                traffic = entry.get("hbm_bytes_per_pass")
+                traffic_src = {"file": "profiles/pmc_summary.json", "collected_at_commit": pm.get("commit"),
+                               "kernel_source_hash": pm.get("kernel_source_hash"), "raw": entry.get("source")}
+            else:
+                traffic_src = {"file": "profiles/pmc_summary.json", "stale": True,
+                               "note": "PMC profile predates the current kernels; traffic withheld"}
+        except Exception:
+            traffic = None
+        if live_err and isinstance(traffic_src, dict):
+            traffic_src["live_attempt"] = live_err
+    steps = line["steps"]
+    full = {
+        "ms_per_step_min": round(min(step_t) * 1e3, 4), "ms_per_step_max": round(max(step_t) * 1e3, 4),
+        "repeat_ms_per_step": [round(t * 1e3, 4) for t in step_t],
+        "ms_per_step_events_off": round(t_noev / steps * 1e3, 4), "event_period": args.event_period,
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
+                     "kernel": "+".join(k for k in ("linearize", "nn", "reduce") if k in kern),
+                     "kernel_ms": round(hot_ms, 5), "algorithmic_bytes_per_launch": int(alg_bytes),
+                     "bytes_per_point": B_ALG[kind_name]},
+        "kernels": {k: {"launches": v["launches"], "avg_ms": round(v["avg_ms"], 5)} for k, v in kern.items()},
+    }
+    if "reduce" in kern:
+        # SURVEY.md section 8d asks for the streaming kernel on its own: B_alg + the 4-byte index per point
+        k2 = (B_ALG[kind_name] + 4) * shard_n / (kern["reduce"]["avg_ms"] * 1e-3) / 1e9
+        full["roofline_reduce_kernel"] = {"bound": "hbm", "achieved": round(k2, 3), "peak": HBM_PEAK_GBS,
+                                          "unit": "GB/s", "frac": round(k2 / HBM_PEAK_GBS, 6),
+                                          "bytes_per_point": B_ALG[kind_name] + 4,
+                                          "kernel_ms": round(kern["reduce"]["avg_ms"], 5)}
+    return full
 
 
 def rccl_one_rank_probe(ctx, step, steps, sync_all):

@@ -38,6 +38,39 @@ def test_configs_match_baseline_json():
     assert a.gpus == 1 and a.config == "plane_b01" and a.steps > 0 and a.warmup >= 0
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """A plain run times ONE block of exactly --steps passes; --full brings back the repeated blocks (and everything
+    else that is not the headline); --repeats still wins when given."""
+    bench = _load_bench()
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "17"]
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.repeats == 1 and a.steps == 17
+        sys.argv = ["bench.py", "--full"]
+        a = bench.parse()
+        assert a.full is True and a.repeats == 5
+        sys.argv = ["bench.py", "--full", "--repeats", "3", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.repeats == 3 and a.dump_outputs == "out"
+    finally:
+        sys.argv = old
+
+
+def test_dump_outputs_writes_what_a_caller_receives(tmp_path):
+    """--dump-outputs: the 29 sums of the last step as H (6x6, symmetric), g (6), e2 and the correspondence count,
+    float64 .npy files."""
+    bench = _load_bench()
+    out = np.arange(29, dtype=np.float64)
+    out[28] = 1234.0
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("H", "g", "e2", "correspondences")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    H = got["H"]
+    assert H.shape == (6, 6) and np.array_equal(H, H.T) and H[0, 0] == 0 and H[0, 5] == 5 and H[5, 5] == 20
+    assert np.array_equal(got["g"], np.arange(21, 27)) and got["e2"] == 27 and got["correspondences"] == 1234
+
+
 def test_cpu_baseline_leg_runs_on_the_oracle():
     bench = _load_bench()
     from point_cloud_registration_amd.synthetic import street, perturbed_scan

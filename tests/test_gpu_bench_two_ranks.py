@@ -20,7 +20,7 @@ def _run(extra, timeout=900):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PCR_BENCH_SELF_LAUNCHED")}
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--config", "plane_b01_100k", "--steps", "5", "--warmup", "2",
-           "--repeats", "2"] + extra
+           "--repeats", "2", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

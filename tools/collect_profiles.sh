@@ -12,7 +12,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out
 export TMPDIR=/tmp
 for e in "$@"; do export "$e"; done
-cmd="python $root/bench.py --config $cfg --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline"
+cmd="python $root/bench.py --full --config $cfg --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline"
 cd /tmp
 run() {   # name, rocprofv3 args...
     local name=$1; shift

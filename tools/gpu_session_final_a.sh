@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."; TAG=${1:-r06}
 o=gpurun_out; mkdir -p $o; export TMPDIR=/tmp
 timeout 3000 python -m pytest tests -m gpu -x -q -rs --durations=40 > $o/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $o/${TAG}_pytest_gpu.log; tail -4 $o/${TAG}_pytest_gpu.log
 for c in plane_b01 icp_b01 icp_b01_harness plane_b01_100k vplane_b01_harness ndt_b01_harness vplane_10m ndt_10m plane_b01_resampled plane_b01_crop plane_lidar icp_lidar_harness plane_100m plane_100m_resampled; do
-    timeout 1500 python bench.py --config $c > $o/${TAG}_bench_$c.json 2> $o/${TAG}_bench_$c.err
+    timeout 1500 python bench.py --full --config $c > $o/${TAG}_bench_$c.json 2> $o/${TAG}_bench_$c.err
     python - "$o/${TAG}_bench_$c.json" <<'PY'
 import json, sys
 try:
@@ -18,8 +18,8 @@ except Exception as e:
     print("bench parse failed", sys.argv[1], e)
 PY
 done
-PCR_BENCH_GROUP_DEVICES=0,0 GPU_MAX_HW_QUEUES=8 timeout 600 python bench.py --gpus 2 --single-process --no-pmc --no-cpu-baseline --config plane_b01 --steps 20 --warmup 5 > $o/${TAG}_bench_plane_b01_group2_1gpu.json 2> $o/${TAG}_bench_group2.err; cut -c1-400 $o/${TAG}_bench_plane_b01_group2_1gpu.json
-timeout 600 python bench.py --gpus 2 --backend gloo --config plane_b01 --steps 20 --warmup 5 > $o/${TAG}_bench_plane_b01_2ranks_1gpu.json 2> $o/${TAG}_bench_2ranks.err; cut -c1-400 $o/${TAG}_bench_plane_b01_2ranks_1gpu.json
+PCR_BENCH_GROUP_DEVICES=0,0 GPU_MAX_HW_QUEUES=8 timeout 600 python bench.py --full --gpus 2 --single-process --no-pmc --no-cpu-baseline --config plane_b01 --steps 20 --warmup 5 > $o/${TAG}_bench_plane_b01_group2_1gpu.json 2> $o/${TAG}_bench_group2.err; cut -c1-400 $o/${TAG}_bench_plane_b01_group2_1gpu.json
+timeout 600 python bench.py --full --gpus 2 --backend gloo --config plane_b01 --steps 20 --warmup 5 > $o/${TAG}_bench_plane_b01_2ranks_1gpu.json 2> $o/${TAG}_bench_2ranks.err; cut -c1-400 $o/${TAG}_bench_plane_b01_2ranks_1gpu.json
 timeout 600 python tools/build_time.py 1.06e6 1e7 1e8 > $o/${TAG}_build_time.txt 2>&1; tail -3 $o/${TAG}_build_time.txt
 timeout 600 python tools/speed_test_comparison.py > $o/${TAG}_speed_test_comparison.txt 2>&1; tail -8 $o/${TAG}_speed_test_comparison.txt
 timeout 300 python tools/set_target_probe.py 2>&1 | grep -v "^/opt" | head -8 > $o/${TAG}_seam_align.txt; timeout 200 python tools/align_seam_probe.py 2>&1 | grep -v '^/opt' | head -8 >> $o/${TAG}_seam_align.txt; cat $o/${TAG}_seam_align.txt

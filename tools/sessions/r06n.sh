@@ -5,7 +5,7 @@ for rep in 1 2; do
 for cfg in icp_b01_harness vplane_b01_harness ndt_b01_harness plane_b01_100k; do
   for lib in r05 ship; do
     if [ $lib = r05 ]; then export PCR_LIB=$root/build/exp/libpcr_r05.so; else unset PCR_LIB; fi
-    timeout 600 python bench.py --config $cfg --no-pmc --no-cpu-baseline --repeats 5 2> $o/r06n_$cfg.$lib.err | tail -1 > $o/r06n_bench_$cfg.$lib.json
+    timeout 600 python bench.py --full --config $cfg --no-pmc --no-cpu-baseline --repeats 5 2> $o/r06n_$cfg.$lib.err | tail -1 > $o/r06n_bench_$cfg.$lib.json
     python - $o/r06n_bench_$cfg.$lib.json $lib <<'PY' | tee -a $o/r06n_harness_ab.txt
 import json, sys
 try:

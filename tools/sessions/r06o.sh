@@ -18,7 +18,7 @@ for name, cloud in (("lidar_sweep", lidar_sweep(1_060_000, 0)), ("street", stree
 PY
 grep -v "^/opt" $o/r06_lidar_set_target.txt)
 for n in 4 8; do
-  PCR_BENCH_GROUP_DEVICES=$(python -c "print(','.join(['0']*$n))") GPU_MAX_HW_QUEUES=$((n+4)) timeout 600 python bench.py --gpus $n --single-process --no-pmc --no-cpu-baseline --config plane_b01 --steps 20 --warmup 5 > $o/r06_bench_plane_b01_group${n}_1gpu.json 2> $o/r06o_group$n.err; cut -c1-300 $o/r06_bench_plane_b01_group${n}_1gpu.json
+  PCR_BENCH_GROUP_DEVICES=$(python -c "print(','.join(['0']*$n))") GPU_MAX_HW_QUEUES=$((n+4)) timeout 600 python bench.py --full --gpus $n --single-process --no-pmc --no-cpu-baseline --config plane_b01 --steps 20 --warmup 5 > $o/r06_bench_plane_b01_group${n}_1gpu.json 2> $o/r06o_group$n.err; cut -c1-300 $o/r06_bench_plane_b01_group${n}_1gpu.json
 done
 (cd $root && timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 | tee $o/r06_smoke.txt)
 (cd $root && timeout 1200 python -m pytest tests/test_gpu_heavy_index.py -m gpu -q --durations=3 2>&1 | tail -6 | tee $o/r06o_heavy.txt)

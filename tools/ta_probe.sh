@@ -4,7 +4,7 @@
 # every pass under its own timeout.  Output: gpurun_out/ta_probe.txt (per-instance averages per launch).
 root=$(cd "$(dirname "$0")/.." && pwd); out=$root/gpurun_out; export TMPDIR=/tmp; cd /tmp
 rocprofv3 --list-avail 2>/dev/null | grep -o -E "\b(TA_[A-Z_0-9]+|TCP_[A-Z_0-9]+|TD_[A-Z_0-9]+|SQ_INST_CYCLES_VMEM[A-Z_]*|SQ_ACTIVE_INST_[A-Z_]+|SQ_WAIT_INST_[A-Z_]+|SQ_BUSY_CYCLES|SQ_INSTS_VMEM[A-Z_]*|SQ_THREAD_CYCLES_VALU|SQ_INST_LEVEL_VMEM)\b" | sort -u | tr "\n" " " > $out/avail_counters.txt
-cmd="python $root/bench.py --config plane_b01 --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline"
+cmd="python $root/bench.py --full --config plane_b01 --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline"
 run() { local name=$1; shift
   rm -rf "$out/prof_ta_$name"
   timeout -k 5 150 rocprofv3 --pmc "$@" --kernel-trace --output-format rocpd -d "$out/prof_ta_$name" -o r -- $cmd > "$out/prof_ta_$name.log" 2>&1
