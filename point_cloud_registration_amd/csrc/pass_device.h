@@ -347,11 +347,8 @@ __device__ __forceinline__ void fold_step(double *acc, int lane) {
 }
 
 // After the call lane l holds the wave-wide sum of component (l >> 1) in acc[0].
-// SPLIT (k_scan_reduce): the lanes come in holding 16 values each -- components 0..15 on lanes 0..31, 16..31 on lanes 32..63 --
-// i.e. the state after the first halving step.
-template <bool SPLIT = false>
 __device__ __forceinline__ void wave_fold32(double *acc, int lane) {
-    if (!SPLIT) fold_step<16, 32>(acc, lane);
+    fold_step<16, 32>(acc, lane);
     fold_step<8, 16>(acc, lane);
     fold_step<4, 8>(acc, lane);
     fold_step<2, 4>(acc, lane);
@@ -361,11 +358,11 @@ __device__ __forceinline__ void wave_fold32(double *acc, int lane) {
 
 // COHERENT: the store is written through to memory at agent scope, so that a block on ANOTHER XCD
 // (each XCD has a private, mutually non-coherent L2) can read it inside the same kernel.
-template <bool COHERENT = false, bool SPLIT = false>
+template <bool COHERENT = false>
 __device__ __forceinline__ void block_store_partials(double *acc, double *__restrict__ partials) {
     __shared__ double wsum[4][32];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wave_fold32<SPLIT>(acc, lane);
+    wave_fold32(acc, lane);
     if ((lane & 1) == 0) wsum[wave][lane >> 1] = acc[0];
     __syncthreads();
     if (threadIdx.x < 32) {
@@ -415,8 +412,8 @@ __device__ __forceinline__ void linearize_body(const LinArgs &a, const PoseK &P,
         bool ok;
         if (KIND == PCR_ICP || KIND == PCR_PLANE) {
             float best;
-            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH_SMALL, false, LB != 0>(a.gf, a.pts, a.cell_start, tx, ty, tz,
-                                                                                                          a.bound2_f, best, bj, bo);
+            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH_SMALL, LB != 0>(a.gf, a.pts, a.cell_start, tx, ty, tz,
+                                                                                                   a.bound2_f, best, bj, bo);
             ok = bj != PCR_NONE && __builtin_sqrtf(best) < a.md_f;                 // icp.py:34 strict gate
         } else if (FILT) {
             double d;
@@ -619,9 +616,9 @@ __device__ __forceinline__ void nnj_store(uint32_t *p, uint32_t v) {
 // distance from the transformed point to every other target point, for k_certify of the next pass.  A point
 // that moved less than mu since the previous pass searches up to mu beyond its match to make that bound useful;
 // one that moved more searches exactly like the plain kernel (its bound then carries no margin).
-// RB (round 6): 1 = the rings of a plain point search prune by the target's row-block boxes (nn_rings_box); 2 = a target with
-// heavy cells: every range longer than PCR_LB_MIN records is scanned through its leaf / group boxes (nn_scan_range_lb)
-template <int VOXEL, int HALO, int TRACK, int RB = 0>
+// LB: a target with heavy cells: every range longer than PCR_LB_MIN records is scanned through its leaf / group boxes
+// (nn_scan_range_lb)
+template <int VOXEL, int HALO, int TRACK, bool LB = false>
 __device__ __forceinline__ void nn_point(const LinArgs &a, const Geom<float> &gf, const PoseK &P, const PoseQ &Q, int64_t i) {
     const float x = a.sx[i], y = a.sy[i], z = a.sz[i];
     float tx, ty, tz;
@@ -645,16 +642,7 @@ __device__ __forceinline__ void nn_point(const LinArgs &a, const Geom<float> &gf
             nn_search<float, PtF, false, false, HALO != 0, true>(gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo, nullptr, &tk);
             lb2q = fminf(tk.second, tk.pmin);
         } else {
-#ifdef PCR_EXP_SEED
-            // developer TIMING experiment (exact results): what the per-lane search costs when it starts from a near-exact
-            // upper bound -- the match the previous pass left in nn_j (tools/pose0_passes.py repeats ONE pose, so that is the
-            // true neighbour): the potential of any scheme that proposes a near neighbour before the exact search
-            const uint32_t pj = a.nn_j[i];
-            if (pj != PCR_NONE) nn_test<float, PtF, 0>(a.pts[pj], pj, tx, ty, tz, best, bj, bo);
-            nn_search<float, PtF, false, true, HALO != 0, false>(gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo);
-#else
-            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH, RB == 1, RB == 2>(gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo);
-#endif
+            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH, LB>(gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo);
             lb2q = best;
         }
         if (TRACK) {
@@ -917,9 +905,8 @@ __device__ __forceinline__ void finalize_emit(const FinArgs &f, const double *to
 // last of the 8 second-level tickets folds those rows and emits.  8 x (nblocks/8) + 8 serialised atomics
 // instead of nblocks.
 // (returns true in the ONE block that folded the last contribution and emitted the result)
-template <bool SPLIT = false>
 __device__ __forceinline__ bool ticket_fold_emit(double *acc, const LinArgs &a, const FinArgs &f) {
-    block_store_partials<true, SPLIT>(acc, a.partials);
+    block_store_partials<true>(acc, a.partials);
 
     __shared__ int role;
     __shared__ double part[8][33];

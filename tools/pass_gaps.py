@@ -37,7 +37,7 @@ def show(db):
     cur = sqlite3.connect(db).cursor()
     ev = [(s, e, re.sub(r"\(.*", "", nm).replace("void ", "")) for nm, s, e in cur.execute("select name, start, end from kernels").fetchall()]
     ev.sort()
-    hot = [(s, e, nm) for s, e, nm in ev if re.match(r"k_nn_|k_reduce_|k_linearize|k_scan_reduce", nm)]
+    hot = [(s, e, nm) for s, e, nm in ev if re.match(r"k_nn_|k_reduce_|k_linearize", nm)]
     hot = hot[-60:]
     gaps = {}
     durs = {}
