@@ -132,7 +132,12 @@ PCR_API pcr_status pcr_comm_p2p_finegrained(pcr_context *ctx, int *finegrained);
  * (hipDeviceEnablePeerAccess; no IPC, no RCCL, no torch): every member takes the same Gauss-Newton step on bit-identical
  * sums, and the call returns member 0's copy -- what the SPMD run with the same sharding returns, bit for bit.
  * Calls on one group are serialised by the caller (like every other handle); errors: the first failing member's status,
- * pcr_last_error() names the member.  PCR_FLAG_LOCAL_ONLY is ignored (a group call is the sum over its members).          */
+ * pcr_last_error() names the member.  PCR_FLAG_LOCAL_ONLY is ignored (a group call is the sum over its members).
+ * Members must agree: pcr_group_linearize compares every member's 29 sums with member 0's, pcr_group_align every member's
+ * status, iteration count, pose and (with a trace wanted) every row of its trace; on any difference the call returns
+ * PCR_ERR_COMM and pcr_last_error() names the first member that disagrees.
+ * pcr_group_scan_member: member i's shard (borrowed, like pcr_group_target_member): pcr_scan_read_matches / reuse stats of
+ * one member; a plain pcr_linearize over it needs PCR_FLAG_LOCAL_ONLY (the member's context is attached to the exchange). */
 PCR_API pcr_status pcr_group_create(const int *device_ids, int n, pcr_group **out);
 PCR_API pcr_status pcr_group_destroy(pcr_group *g);
 PCR_API pcr_status pcr_group_size(pcr_group *g, int *n);
@@ -148,6 +153,7 @@ PCR_API pcr_status pcr_group_target_member(pcr_group_target *gt, int i, pcr_targ
 PCR_API pcr_status pcr_group_target_destroy(pcr_group_target *gt);
 PCR_API pcr_status pcr_group_scan_create(pcr_group *g, const float *xyz, int64_t n, unsigned flags, pcr_group_scan **out);
 PCR_API pcr_status pcr_group_scan_size(pcr_group_scan *gs, int64_t *n);
+PCR_API pcr_status pcr_group_scan_member(pcr_group_scan *gs, int i, pcr_scan **s);        /* borrowed */
 PCR_API pcr_status pcr_group_scan_destroy(pcr_group_scan *gs);
 PCR_API pcr_status pcr_group_linearize(pcr_group_target *gt, pcr_group_scan *gs, int kind, const double T[16], double max_dist,
                                        unsigned flags, double out[29]);

@@ -119,6 +119,7 @@ PROTOTYPES = {
     "pcr_group_target_destroy": (C.c_int, [_vp]),
     "pcr_group_scan_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_uint, C.POINTER(_vp)]),
     "pcr_group_scan_size": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "pcr_group_scan_member": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "pcr_group_scan_destroy": (C.c_int, [_vp]),
     "pcr_group_linearize": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, _f64p]),
     "pcr_group_align": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p,
@@ -567,7 +568,7 @@ class Target:
         return dist, idx
 
     def close(self):
-        if getattr(self, "handle", None) and not _shutdown:
+        if getattr(self, "handle", None) and not _shutdown and not getattr(self, "_borrowed", False):
             lib().pcr_target_destroy(self.handle)
         self.handle = None
 
@@ -624,10 +625,22 @@ class Scan:
         m[out == 0xFFFFFFFF] = -1
         return m
 
+    def member(self, i):
+        """Member i's shard of a group scan (borrowed: destroyed with the group scan; ``ctx`` is the member's context).  A plain
+        ``linearize`` over it needs FLAG_LOCAL_ONLY: the member's context takes part in the group's exchange."""
+        if self.ghandle is None:
+            raise ValueError("member() of a scan that is not a group scan")
+        h, n = _vp(), C.c_int64(0)
+        check(lib().pcr_group_scan_member(self.ghandle, int(i), C.byref(h)))
+        check(lib().pcr_scan_size(h, C.byref(n)))
+        s = Scan.__new__(Scan)
+        s.ctx, s.ghandle, s.handle, s.n, s._borrowed, s._owner = self.ctx.member(i), None, h, n.value, True, self
+        return s
+
     def close(self):
         if getattr(self, "ghandle", None) and not _shutdown:
             lib().pcr_group_scan_destroy(self.ghandle)
-        elif getattr(self, "handle", None) and not _shutdown:
+        elif getattr(self, "handle", None) and not _shutdown and not getattr(self, "_borrowed", False):
             lib().pcr_scan_destroy(self.handle)
         self.handle = None
         self.ghandle = None
@@ -691,6 +704,15 @@ class GroupTarget(Target):
         h = _vp()
         check(lib().pcr_group_target_member(ghandle, 0, C.byref(h)))
         super().__init__(group, h, is_voxel)
+
+    def member(self, i):
+        """Member i's target (borrowed: destroyed with the group target; ``ctx`` is the member's context): index_info,
+        queries and read-backs of that member."""
+        h = _vp()
+        check(lib().pcr_group_target_member(self.ghandle, int(i), C.byref(h)))
+        t = Target.__new__(Target)
+        t.ctx, t.handle, t.is_voxel, t._borrowed, t._owner = self.ctx.member(i), h, self.is_voxel, True, self
+        return t
 
     def set_normals(self, normals):
         check(lib().pcr_group_target_set_normals(self.ghandle, np.ascontiguousarray(normals, dtype=np.float32)))

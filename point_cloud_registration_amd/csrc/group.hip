@@ -254,6 +254,13 @@ extern "C" pcr_status pcr_group_scan_size(pcr_group_scan *gs, int64_t *n) {
     return PCR_OK;
 }
 
+// member i's shard (borrowed: pcr_scan_read_matches, pcr_scan_reuse_stats ...); destroyed with the group scan
+extern "C" pcr_status pcr_group_scan_member(pcr_group_scan *gs, int i, pcr_scan **s) {
+    PCR_REQUIRE(gs && s && i >= 0 && i < (int)gs->s.size(), "bad member index");
+    *s = gs->s[(size_t)i];
+    return PCR_OK;
+}
+
 extern "C" pcr_status pcr_group_scan_destroy(pcr_group_scan *gs) {
     if (!gs) return PCR_OK;
     for (pcr_scan *p : gs->s) pcr_scan_destroy(p);
@@ -271,7 +278,15 @@ extern "C" pcr_status pcr_group_linearize(pcr_group_target *gt, pcr_group_scan *
     PCR_TRY(group_run(g, [&](int i) {
         return pcr_linearize(gt->t[(size_t)i], gs->s[(size_t)i], kind, T, max_dist, flags, outs.data() + (size_t)i * 29);
     }));
-    memcpy(out, outs.data(), 29 * sizeof(double));                // (every member holds the same, bit-identical sums)
+    // every member must hold the same, bit-identical sums: a member that read a stale slot or summed in another order would
+    // take another Gauss-Newton step than member 0, whose copy is the one returned
+    for (int i = 1; i < g->n(); ++i) {
+        if (memcmp(outs.data() + (size_t)i * 29, outs.data(), 29 * sizeof(double)) != 0) {
+            pcr_set_error("group member %d (device %d): its exchanged sums differ from member 0's", i, g->ctx[(size_t)i]->device);
+            return PCR_ERR_COMM;
+        }
+    }
+    memcpy(out, outs.data(), 29 * sizeof(double));
     return PCR_OK;
 }
 
@@ -284,11 +299,31 @@ extern "C" pcr_status pcr_group_align(pcr_group_target *gt, pcr_group_scan *gs, 
     const int n = g->n();
     std::vector<double> Ts((size_t)n * 16, 0.0);
     std::vector<int> its((size_t)n, 0);
+    std::vector<pcr_status> sts((size_t)n, PCR_OK);
+    // with a trace wanted, every member writes its own (member 0's into the caller's buffer) so that the sums of every
+    // iteration are compared, not only where they led
+    const size_t trace_len = trace_or_null && max_iter > 0 ? (size_t)max_iter * 45 : 0;
+    std::vector<double> traces(trace_len * (size_t)(n > 1 ? n - 1 : 0), 0.0);
     const pcr_status s = group_run(g, [&](int i) {
-        return pcr_align(gt->t[(size_t)i], gs->s[(size_t)i], kind, T_init, max_iter, tol, max_dist, flags, Ts.data() + (size_t)i * 16,
-                         &its[(size_t)i], i == 0 ? trace_or_null : nullptr);
+        double *tr = trace_len == 0 ? nullptr : i == 0 ? trace_or_null : traces.data() + (size_t)(i - 1) * trace_len;
+        sts[(size_t)i] = pcr_align(gt->t[(size_t)i], gs->s[(size_t)i], kind, T_init, max_iter, tol, max_dist, flags,
+                                   Ts.data() + (size_t)i * 16, &its[(size_t)i], tr);
+        return sts[(size_t)i];
     });
     memcpy(T_out, Ts.data(), 16 * sizeof(double));
     if (iterations) *iterations = its[0];
+    // every member must end alike: same status, iteration count, pose and (traced) per-iteration sums as member 0
+    for (int i = 1; i < n; ++i) {
+        const char *what = sts[(size_t)i] != sts[0] ? "status" : its[(size_t)i] != its[0] ? "iteration count"
+                         : memcmp(Ts.data() + (size_t)i * 16, Ts.data(), 16 * sizeof(double)) != 0 ? "pose" : nullptr;
+        if (!what && trace_len && its[0] > 0 &&
+            memcmp(traces.data() + (size_t)(i - 1) * trace_len, trace_or_null, (size_t)its[0] * 45 * sizeof(double)) != 0)
+            what = "trace";
+        if (what) {
+            pcr_set_error("group member %d (device %d): its %s differs from member 0's (status %d / %d, %d / %d iterations)", i,
+                          g->ctx[(size_t)i]->device, what, sts[(size_t)i], sts[0], its[(size_t)i], its[0]);
+            return PCR_ERR_COMM;
+        }
+    }
     return s;
 }

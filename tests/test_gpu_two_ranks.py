@@ -122,6 +122,111 @@ def test_two_ranks_one_gpu_sharded_plane_icp(g2, transport, world):
         assert np.max(np.abs(Ha - g2[f"T_{name}_H"])) < 1e-5 * np.max(np.abs(g2[f"T_{name}_H"])), name
 
 
+def _b01_clouds():
+    """The g8 cloud, its full perturbed scan and the supplied normals, regenerated and checksum-guarded (as conftest.g8)."""
+    import zlib
+    from point_cloud_registration_amd.synthetic import street, perturbed_scan, street_normals
+    g = load_golden("g8_b01_fullsize.npz")
+    target = street(int(g["n"]), seed=0)
+    clouds = {"target": target, "pertfull": perturbed_scan(target, None, seed=2)[0], "given_normals": street_normals(target)}
+    for name, arr in clouds.items():
+        assert zlib.crc32(arr.tobytes()) == int(g[f"crc32_{name}"]), name
+    g.update(clouds)
+    return g
+
+
+# what every rank of the run at size evaluates: PlaneICP with the supplied normals at its B-01 trajectory, NDT at the 100 k
+# scan's trajectory (the fixture's poses), then one align() each
+_AT_SIZE = (("planeg", "pertfull_planeg_T"), ("ndt", "pert100k_ndt_T"))
+
+
+def _at_size_targets(ctx, g):
+    from point_cloud_registration_amd import _capi
+    return {"planeg": (_capi.PLANE, _capi.Target.points(ctx, g["target"], g["given_normals"])),
+            "ndt": (_capi.NDT, _capi.Target.voxels(ctx, g["target"], float(g["voxel_size"]), 10))}
+
+
+def _worker_at_size(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK="0", PCR_DEVICE="0")
+    sys.path.insert(0, REPO)
+    import torch.distributed as dist
+    from point_cloud_registration_amd import _capi, distributed as pdist
+    pdist.init_from_env("gloo")
+    g = _b01_clouds()
+    ctx = _capi.get_context(0)
+    comm = pdist.Communicator(ctx, in_library=True, transport="p2p")
+    md = float(g["max_dist"])
+    out = {}
+    if comm.in_library:                       # (the agreed host fallback: nothing of the in-library exchange to check)
+        sc = _capi.Scan(ctx, np.ascontiguousarray(pdist.shard_scan(g["pertfull"], rank, world)))
+        for name, (kind, tgt) in _at_size_targets(ctx, g).items():
+            sums = np.array([_capi.linearize(tgt, sc, kind, T, md) for T in g[dict(_AT_SIZE)[name]]])
+            T, its = _capi.align(tgt, sc, kind, np.eye(4), 30, 1e-3, md)
+            out[name] = (sums, T, its)
+    failed = ctx.comm_p2p_failed() if comm.in_library else False
+    q.put((rank, comm.in_library, out, comm.transport, failed))
+    dist.barrier()
+    comm.close()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_p2p_ranks_at_b01_size(world):
+    """The peer-to-peer transport between PROCESSES at B-01 size: rank r holds shard r of the 1.06 M-point scan (530 k / 353 k
+    points: the search + reduce kernels feed the exchange, not the fused small-scan kernel of the g2 cases above).  Ranks are
+    bit-identical; every exchanged result equals the SPMD sums computed here shard by shard on one context; at world 2 a
+    [0, 0] group in this process returns the same sums, pose and iteration count (include/pcr.h: "what the SPMD run with the
+    same sharding returns, bit for bit")."""
+    import multiprocessing as mp
+    import queue as queue_mod
+    from point_cloud_registration_amd import _capi, distributed as pdist
+    mctx = mp.get_context("spawn")
+    q = mctx.Queue()
+    port = _free_port()
+    procs = [mctx.Process(target=_worker_at_size, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    try:
+        res = sorted([q.get(timeout=600) for _ in procs], key=lambda r: r[0])
+    except queue_mod.Empty:
+        for p in procs:
+            p.kill()
+        pytest.fail("a rank did not report within 600 s")
+    for p in procs:
+        p.join(120)
+        assert p.exitcode == 0
+    assert len({(r[1], r[3]) for r in res}) == 1                # every rank took the same transport
+    if not res[0][1] and os.environ.get("PCR_ALLOW_FALLBACK") == "1":
+        pytest.skip("hipIpc between processes is not available on this box: the ranks agreed on the host fallback")
+    assert res[0][1] and res[0][3] == "p2p", "the peer-to-peer transport fell back to the host all-reduce (PCR_ALLOW_FALLBACK=1 tolerates it)"
+    assert not any(r[4] for r in res)
+    out = res[0][2]
+    for r in res[1:]:
+        for name in out:
+            assert all(np.array_equal(a, b) for a, b in zip(out[name], r[2][name])), (name, "ranks disagree")
+    g = _b01_clouds()
+    md = float(g["max_dist"])
+    ctx = _capi.get_context(0)
+    shards = [_capi.Scan(ctx, np.ascontiguousarray(pdist.shard_scan(g["pertfull"], r, world))) for r in range(world)]
+    for name, (kind, tgt) in _at_size_targets(ctx, g).items():
+        poses = g[dict(_AT_SIZE)[name]]
+        spmd = np.zeros((poses.shape[0], 29))
+        for sc in shards:                       # rank order from 0.0, as k_p2p_allreduce adds the slots
+            spmd = spmd + np.array([_capi.linearize(tgt, sc, kind, T, md, _capi.FLAG_ICP_RR_QUIRK | _capi.FLAG_LOCAL_ONLY)
+                                    for T in poses])
+        assert np.array_equal(out[name][0], spmd), (name, "exchanged sums != SPMD sums")
+        print(f"p2p world {world} {name}: {out[name][2]} iterations, {int(spmd[0, 28])} correspondences at the first pose")
+    if world == 2:
+        grp = _capi.get_group((0, 0))          # (process-wide: released after its targets and scans at exit)
+        gs = _capi.Scan(grp, g["pertfull"])
+        for name, (kind, tgt) in _at_size_targets(grp, g).items():
+            sums = np.array([_capi.linearize(tgt, gs, kind, T, md) for T in g[dict(_AT_SIZE)[name]]])
+            T, its = _capi.align(tgt, gs, kind, np.eye(4), 30, 1e-3, md)
+            assert np.array_equal(sums, out[name][0]), (name, "group sums != the ranks' sums")
+            assert np.array_equal(T, out[name][1]) and its == out[name][2], (name, "group align != the ranks' align")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("order", ["rccl_then_torch", "torch_then_rccl"])
 def test_process_exits_cleanly_with_rccl_and_torch(order):
