@@ -238,6 +238,24 @@ PCR_API pcr_status pcr_lzf_compress(const void *in, uint64_t in_len, void *out, 
  * the rest of a 100 ms scheduler period, the calling thread of pcr_linearize included.          */
 PCR_API int pcr_usable_cpus(void);
 
+/* ---- Gauss-Newton coresets (caratheodory.py:62-138; K. Koide, arXiv 2307.02948) ----------------
+ * pcr_gn_set = create_gn_set(J, r) (caratheodory.py:118-138): J (n, d) row-major and r (n), each float32 or float64
+ * (*_is_f64), 1 <= d <= 12 -> P_out (m, n) float64 row-major, m = d (d + 1) / 2 + d + 1: the rows J[:, a] J[:, b] for
+ * (a, b) in np.triu_indices(d) order, then J[:, a] r, then r^2.  Every product is rounded once in the type NumPy's
+ * promotion gives it (float32 x float32 in float32, then widened): the reference's values bit for bit.
+ * pcr_coreset = fast_caratheodory(P, u, k, n_target) (caratheodory.py:62-116): P (m, n) float64 row-major, u (n) finite
+ * and > 0, k > m + 1, n_target >= m + 1 (the reference does not finish below those: its caratheodory() returns the
+ * same chunk again, caratheodory.py:42-43).  Writes *n_out <= n_target points: idx_out ascending, w_out > 0 with
+ * sum w P[:, idx] = sum u P up to rounding, P_sel_out = P[:, idx] as (m, *n_out) row-major.  The chunk bounds are the
+ * reference's np.linspace ones; the Caratheodory elimination of each level runs on the host in float64 with its null
+ * vector from a pivoted QR (the reference: the last right-singular vector of an SVD), so the points chosen differ from
+ * the reference's -- only the properties above are the contract.  n <= n_target: the inputs and 0..n-1, no GPU work.
+ * P is uploaded once and stays in HBM; the O(n m) sums of every level run on the GPU, bit-reproducible.              */
+PCR_API pcr_status pcr_gn_set(pcr_context *ctx, const void *J, int J_is_f64, const void *r, int r_is_f64, int64_t n, int d,
+                              double *P_out);
+PCR_API pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int64_t n, const double *u, int k, int64_t n_target,
+                               int64_t *n_out, double *w_out, int64_t *idx_out, double *P_sel_out);
+
 /* ---- the hot path ---------------------------------------------------------------------
  * One calc_H_g_e2: transform (math_tools.py:111-113) -> exact 1-NN (kdtree.py:18-21 /
  * voxel.py:171-179) -> gate dist < max_dist -> residual + Jacobian -> 6x6 normal equations

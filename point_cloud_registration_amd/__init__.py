@@ -1,8 +1,8 @@
 """MI355X-native drop-in for the registration hot path of scomup/point-cloud-registration.
 
-Same public names as the reference's ``point_cloud_registration/__init__.py:1-10`` (minus the
-experimental Caratheodory coreset helpers, which are not on any ``align()`` path): the O(N) work
-of ``set_target`` / ``calc_H_g_e2`` / ``align`` runs in hand-written HIP kernels for gfx950 behind
+Same public names as the reference's ``point_cloud_registration/__init__.py:1-10``: the O(N) work
+of ``set_target`` / ``calc_H_g_e2`` / ``align`` and of the Gauss-Newton coresets
+(``create_gn_set`` / ``fast_caratheodory``) runs in hand-written HIP kernels for gfx950 behind
 a C ABI (include/pcr.h); there is no CPU fallback.
 """
 
@@ -16,10 +16,11 @@ from .ndt import NDT
 from .kdtree import KDTree
 from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
 from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
+from .caratheodory import fast_caratheodory, create_gn_set
 
 __all__ = [
     "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "KDTree", "VoxelGrid", "voxel_filter",
     "color_by_voxel", "get_keys", "estimate_normals", "get_norm_lines", "estimate_norm_with_tree",
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
-    "skew_time_vector", "skew", "skew2",
+    "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
 ]

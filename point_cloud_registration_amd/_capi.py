@@ -105,6 +105,10 @@ PROTOTYPES = {
     "pcr_comm_p2p_finegrained": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "pcr_lzf_decompress": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcr_lzf_compress": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    # Gauss-Newton coresets (include/pcr.h, caratheodory.py)
+    "pcr_gn_set": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, _f64p]),
+    "pcr_coreset": (C.c_int, [_vp, _f64p, C.c_int, C.c_int64, _f64p, C.c_int, C.c_int64, C.POINTER(C.c_int64), _f64p, _i64p,
+                              _f64p]),
     # single-process multi-device groups (include/pcr.h)
     "pcr_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(_vp)]),
     "pcr_group_destroy": (C.c_int, [_vp]),
@@ -746,6 +750,25 @@ def lzf_compress(data):
     w = C.c_uint64(0)
     check(lib().pcr_lzf_compress(src.ctypes.data_as(_vp), src.size, out.ctypes.data_as(_vp), out.size, C.byref(w)))
     return out[:w.value].tobytes()
+
+
+def gn_set(ctx, J, r):
+    """pcr_gn_set: J (n, d) and r (n), each C-contiguous float32 or float64 -> P (m, n) float64."""
+    n, d = J.shape
+    P = np.empty((d * (d + 1) // 2 + d + 1, n))
+    check(lib().pcr_gn_set(ctx.handle, _ptr(J), int(J.dtype == np.float64), _ptr(r), int(r.dtype == np.float64), n, d, P))
+    return P
+
+
+def coreset(ctx, P, u, k, n_target):
+    """pcr_coreset: P (m, n) and u (n) C-contiguous float64 -> (P_sel (m, n_out), w (n_out), idx (n_out))."""
+    m, n = P.shape
+    cap = max(min(int(n_target), n), 1)
+    w, idx, sel = np.empty(cap), np.empty(cap, np.int64), np.empty(m * cap)
+    n_out = C.c_int64(0)
+    check(lib().pcr_coreset(ctx.handle, P, m, n, u, int(k), int(n_target), C.byref(n_out), w, idx, sel))
+    c = n_out.value
+    return sel[:m * c].reshape(m, c), w[:c], idx[:c]
 
 
 def hash64(arr):
