@@ -277,6 +277,44 @@ PCR_API pcr_status pcr_align(pcr_target *t, pcr_scan *s, int kind, const double 
                              int max_iter, double tol, double max_dist, unsigned flags,
                              double T_out[16], int *iterations, double *trace_or_null);
 
+/* ---- batches: many scans and / or start poses against ONE target in one launch -----------
+ * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
+ * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the
+ * chip with waves that wait on dependent misses.  A caller with K scans (a LiDAR sequence against a map, several robots,
+ * loop-closure candidates) or K start poses for one scan (multi-start) gets one launch per iteration for the WHOLE batch: a
+ * second grid dimension over the items, each item with its own partial sums, tickets, pose and trace rows.
+ * pcr_scan_batch_create: S scans in one upload -- xyz = all points concatenated, offsets[S + 1] ascending from 0 (empty scans
+ * allowed); every scan is Morton-sorted exactly as pcr_scan_create sorts it.  Device blocks come from and return to the
+ * context's block cache, like a scan's.  "One upload" is one host-to-device copy only: each scan is then sorted by its own
+ * pcr_scan_create_device -- its own x / y / z blocks, its own sort temporaries, one stream synchronisation each -- so creating a
+ * batch costs about what S pcr_scan_create calls cost minus S - 1 copies; create it once and reuse it across calls.
+ * An ITEM of a call = scan item_scan[i] of the batch at pose T[16 i ..]; several items may name the same scan (the points are
+ * held once).  item_scan == NULL: item i = scan i and n_items must be the number of scans.  At most 65535 items per call.
+ * pcr_linearize_batch: out[29 i ..] = what pcr_linearize gives for item i alone.
+ * pcr_align_batch: per item T_out[16 i ..], iterations[i], item_status[i] (PCR_OK, or PCR_ERR_SINGULAR with T_out = the pose
+ * of the failed solve, as pcr_align leaves it), and with trace_or_null != NULL max_iter rows of 45 doubles per item (row r of
+ * item i at 45 (max_iter i + r); rows past iterations[i] are zero).  iterations / item_status may be NULL.  A singular item
+ * neither fails the call nor disturbs the others: the call itself fails only for bad arguments, unsupported configurations
+ * or HIP errors.  The loop is always the device-resident one (PCR_FLAG_HOST_LOOP / PCR_FLAG_DEVICE_LOOP are ignored).
+ * Every item runs the fused small-scan kernel with the block count, work split, fold order and Gauss-Newton step of a single
+ * launch over that scan, so its sums, trace rows, iteration count and pose are BIT-IDENTICAL to pcr_linearize /
+ * pcr_align(PCR_FLAG_DEVICE_LOOP) of that scan alone under pcr_set_variant(ctx, 0) -- which is also what the default variant
+ * runs for scans of up to num_cu x 1024 points.  Larger items are accepted and correct (sums equal to the default path's up
+ * to the order of summation) but are not what this is for: above that size search + reduce is the faster pipeline.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group); PCR_PLANE over a target
+ * with float64 coordinates (pcr_target_points_set_f64: quirk Q6 always runs search + reduce).  Certified reuse
+ * (pcr_set_reuse) does not apply to batches.                                                                             */
+typedef struct pcr_scan_batch pcr_scan_batch;
+PCR_API pcr_status pcr_scan_batch_create(pcr_context *ctx, const float *xyz, const int64_t *offsets, int n_scans, unsigned flags,
+                                         pcr_scan_batch **out);
+PCR_API pcr_status pcr_scan_batch_size(pcr_scan_batch *b, int *n_scans, int64_t *n_points);
+PCR_API pcr_status pcr_scan_batch_destroy(pcr_scan_batch *b);
+PCR_API pcr_status pcr_linearize_batch(pcr_target *t, pcr_scan_batch *b, int kind, int n_items, const int *item_scan,
+                                       const double *T, double max_dist, unsigned flags, double *out);
+PCR_API pcr_status pcr_align_batch(pcr_target *t, pcr_scan_batch *b, int kind, int n_items, const int *item_scan,
+                                   const double *T_init, int max_iter, double tol, double max_dist, unsigned flags,
+                                   double *T_out, int *iterations, pcr_status *item_status, double *trace_or_null);
+
 /* ---- fine seam: KDTree(data).query(points, k) (kdtree.py:18-65) ------------------------
  * dist is Euclidean (not squared).  For point targets dist is float32 and idx indexes the
  * array given to pcr_target_points_create; for voxel targets use the f64 variant (idx =

@@ -109,6 +109,13 @@ PROTOTYPES = {
     "pcr_gn_set": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, _f64p]),
     "pcr_coreset": (C.c_int, [_vp, _f64p, C.c_int, C.c_int64, _f64p, C.c_int, C.c_int64, C.POINTER(C.c_int64), _f64p, _i64p,
                               _f64p]),
+    # batches: many scans / start poses against one target in one launch (include/pcr.h)
+    "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "pcr_scan_batch_destroy": (C.c_int, [_vp]),
+    "pcr_linearize_batch": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
+    "pcr_align_batch": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p,
+                                  _vp, _vp, _vp]),
     # single-process multi-device groups (include/pcr.h)
     "pcr_group_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(_vp)]),
     "pcr_group_destroy": (C.c_int, [_vp]),
@@ -823,6 +830,84 @@ def align(target, scan, kind, T_init, max_iter, tol, max_dist, flags=FLAG_ICP_RR
     if want_trace:
         return T, iters.value, trace[:iters.value]
     return T, iters.value
+
+
+class ScanBatch:
+    """pcr_scan_batch handle: S float32 scans uploaded together, each Morton-sorted as a ``Scan`` of those points is."""
+
+    def __init__(self, ctx, arrays, flags=0):
+        if isinstance(ctx, Group):
+            raise ValueError("a scan batch lives on one context, not on a group")
+        arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+        for a in arrays:
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("every scan of a batch must have shape (N, 3)")
+        offsets = np.zeros(len(arrays) + 1, np.int64)
+        np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+        xyz = np.concatenate(arrays) if arrays else np.zeros((0, 3), np.float32)
+        self.ctx = ctx
+        self.offsets = offsets
+        h = _vp()
+        check(lib().pcr_scan_batch_create(ctx.handle, _ptr(xyz), offsets, len(arrays), int(flags), C.byref(h)))
+        self.handle = h
+        _live.add(self)
+
+    def size(self):
+        """(number of scans, points held on the device)."""
+        s, n = C.c_int(0), C.c_int64(0)
+        check(lib().pcr_scan_batch_size(self.handle, C.byref(s), C.byref(n)))
+        return s.value, n.value
+
+    def close(self):
+        if getattr(self, "handle", None) and not _shutdown:
+            lib().pcr_scan_batch_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _batch_items(target, batch, Ts, item_scan):
+    if getattr(target, "ghandle", None) is not None:
+        raise ValueError("batched passes run on one context, not on a group target")
+    Ts = np.ascontiguousarray(Ts, dtype=np.float64)
+    if Ts.ndim != 3 or Ts.shape[1:] != (4, 4):
+        raise ValueError("poses of a batch must have shape (B, 4, 4)")
+    if item_scan is not None:
+        item_scan = np.ascontiguousarray(item_scan, dtype=np.intc)
+        if item_scan.shape != (Ts.shape[0],):
+            raise ValueError("item_scan must name one scan per pose")
+    return Ts, item_scan
+
+
+def linearize_batch(target, batch, kind, Ts, max_dist, flags=FLAG_ICP_RR_QUIRK, item_scan=None):
+    """pcr_linearize_batch: item i = scan ``item_scan[i]`` of ``batch`` (None: scan i) at ``Ts[i]`` -> (B, 29) sums."""
+    Ts, item_scan = _batch_items(target, batch, Ts, item_scan)
+    out = np.zeros((Ts.shape[0], 29))
+    check(lib().pcr_linearize_batch(target.handle, batch.handle, int(kind), Ts.shape[0], _ptr(item_scan), Ts.reshape(-1),
+                                    float(max_dist), int(flags), out.reshape(-1)))
+    return out
+
+
+def align_batch(target, batch, kind, T_init, max_iter, tol, max_dist, flags=FLAG_ICP_RR_QUIRK, item_scan=None,
+                want_trace=False):
+    """pcr_align_batch: the Gauss-Newton loops of all items, one launch per iteration for the whole batch ->
+    (T (B, 4, 4), iterations (B,), status (B,) of PCR_OK / PCR_ERR_SINGULAR[, trace (B, max_iter, 45)])."""
+    T0, item_scan = _batch_items(target, batch, T_init, item_scan)
+    B = T0.shape[0]
+    T = np.zeros((B, 16))
+    iters = np.zeros(B, np.intc)
+    status = np.zeros(B, np.intc)
+    trace = np.zeros((B, max(int(max_iter), 1), 45)) if want_trace else None
+    check(lib().pcr_align_batch(target.handle, batch.handle, int(kind), B, _ptr(item_scan), T0.reshape(-1), int(max_iter),
+                                float(tol), float(max_dist), int(flags), T.reshape(-1), _ptr(iters), _ptr(status), _ptr(trace)))
+    T = T.reshape(B, 4, 4)
+    if want_trace:
+        return T, iters, status, trace
+    return T, iters, status
 
 
 def nn_counters(target, scan, T, max_dist):

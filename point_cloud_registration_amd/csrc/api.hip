@@ -227,6 +227,7 @@ extern "C" pcr_status pcr_context_destroy(pcr_context *ctx) {
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
     if (ctx->d_pose) (void)hipFree(ctx->d_pose);
     if (ctx->d_trace) (void)hipFree(ctx->d_trace);
     if (ctx->d_tile_ctr) (void)hipFree(ctx->d_tile_ctr);
@@ -778,6 +779,92 @@ extern "C" pcr_status pcr_align(pcr_target *t, pcr_scan *s, int kind, const doub
     if ((flags & PCR_FLAG_HOST_LOOP) || t->ctx->reuse == 2 || small_host)
         return align_host_loop(t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
     return pcr_run_align(t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// ---- batches: many scans / start poses against one target in one launch ------------------------
+extern "C" pcr_status pcr_scan_batch_destroy(pcr_scan_batch *b) {
+    if (!b) return PCR_OK;
+    for (pcr_scan *s : b->scans) (void)pcr_scan_destroy(s);
+    delete b;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_scan_batch_create(pcr_context *ctx, const float *xyz, const int64_t *offsets, int n_scans, unsigned flags,
+                                            pcr_scan_batch **out) {
+    PCR_REQUIRE(ctx && out && offsets, "NULL argument");
+    PCR_REQUIRE(n_scans >= 0, "n_scans is negative");
+    PCR_REQUIRE(offsets[0] == 0, "offsets[0] must be 0");
+    for (int i = 0; i < n_scans; ++i) PCR_REQUIRE(offsets[i + 1] >= offsets[i], "offsets must ascend");
+    const int64_t total = offsets[n_scans];
+    PCR_REQUIRE(xyz || total == 0, "bad scan array");
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    // one upload; every scan is then sorted from its slice exactly as pcr_scan_create sorts it (its own box, its own key width)
+    DevBuf<float> d_xyz;
+    PCR_TRY(upload<float>(ctx, xyz, (size_t)total * 3, &d_xyz, false, false));
+    pcr_scan_batch *b = new pcr_scan_batch();
+    b->ctx = ctx; b->n_points = total;
+    for (int i = 0; i < n_scans; ++i) {
+        pcr_scan *s = nullptr;
+        const pcr_status st = pcr_scan_create_device(ctx, d_xyz.p + 3 * offsets[i], offsets[i + 1] - offsets[i], flags, &s);
+        if (st != PCR_OK) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)pcr_scan_batch_destroy(b);
+            return st;
+        }
+        b->scans.push_back(s);
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {      // (a batch of empty scans never waited for the upload)
+        (void)pcr_scan_batch_destroy(b);
+        pcr_set_error("hipStreamSynchronize failed after the upload of a scan batch");
+        return PCR_ERR_HIP;
+    }
+    *out = b;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_scan_batch_size(pcr_scan_batch *b, int *n_scans, int64_t *n_points) {
+    PCR_REQUIRE(b, "NULL argument");
+    if (n_scans) *n_scans = (int)b->scans.size();
+    if (n_points) *n_points = b->n_points;
+    return PCR_OK;
+}
+
+// item i -> its scan (item_scan == NULL: item i = scan i)
+static pcr_status batch_items(pcr_target *t, pcr_scan_batch *b, int n_items, const int *item_scan, std::vector<pcr_scan *> *scans) {
+    PCR_REQUIRE(b->ctx == t->ctx, "scan batch and target belong to different contexts");
+    const int S = (int)b->scans.size();
+    PCR_REQUIRE(n_items >= 0, "n_items is negative");
+    if (!item_scan) PCR_REQUIRE(n_items == S, "item_scan is NULL: n_items must be the number of scans of the batch");
+    scans->resize((size_t)n_items);
+    for (int i = 0; i < n_items; ++i) {
+        const int k = item_scan ? item_scan[i] : i;
+        PCR_REQUIRE(k >= 0 && k < S, "item_scan names a scan the batch does not have");
+        (*scans)[(size_t)i] = b->scans[(size_t)k];
+    }
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_linearize_batch(pcr_target *t, pcr_scan_batch *b, int kind, int n_items, const int *item_scan,
+                                          const double *T, double max_dist, unsigned flags, double *out) {
+    PCR_REQUIRE(t && b, "NULL argument");
+    PCR_REQUIRE(n_items == 0 || (T && out), "NULL argument");
+    CtxScope scope(t->ctx);
+    std::vector<pcr_scan *> scans;
+    PCR_TRY(batch_items(t, b, n_items, item_scan, &scans));
+    return pcr_run_batch(t, scans.data(), n_items, kind, T, false, 0, 0.0, max_dist, flags, out, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" pcr_status pcr_align_batch(pcr_target *t, pcr_scan_batch *b, int kind, int n_items, const int *item_scan,
+                                      const double *T_init, int max_iter, double tol, double max_dist, unsigned flags,
+                                      double *T_out, int *iterations, pcr_status *item_status, double *trace_or_null) {
+    PCR_REQUIRE(t && b, "NULL argument");
+    PCR_REQUIRE(n_items == 0 || (T_init && T_out), "NULL argument");
+    CtxScope scope(t->ctx);
+    std::vector<pcr_scan *> scans;
+    PCR_TRY(batch_items(t, b, n_items, item_scan, &scans));
+    return pcr_run_batch(t, scans.data(), n_items, kind, T_init, true, max_iter, tol, max_dist, flags, nullptr, T_out, iterations,
+                         item_status, trace_or_null);
 }
 
 // ---- KD-tree seam ----------------------------------------------------------------------------

@@ -489,6 +489,83 @@ __global__ void __launch_bounds__(256) k_linearize_finalize(const LinArgs a, con
     }
 }
 
+// The batched form of k_linearize_finalize (pcr_linearize_batch / pcr_align_batch): blockIdx.y = item of the batch,
+// blockIdx.x = block within the item.  A 100 k-point scan fills a fraction of the chip with waves that wait on dependent cold
+// misses; K such scans against ONE target are K times the waves in flight in one launch instead of K launches.  An instantiation
+// of its own over the shared device functions (no run-time branch in the single-scan kernels): per item the scan slice, n,
+// nblocks, rows, tickets, pose, sums and trace rows come from the item's descriptor, so TileIter, ticket_fold_emit and
+// gn_update see exactly the arguments a single launch over that scan gives them -- every item's sums, trace rows and poses
+// are bit-identical to the single path's.  GN = 1: the device-resident loop (pose from the item's PoseDev, step inline);
+// GN = 0: a plain pass at the descriptor's pose.
+template <int KIND, int HALO, int GN, int FILT, int LB = 0>
+__global__ void __launch_bounds__(256) k_linearize_batch(const LinArgs a0, const FinArgs f0, const BatchItem *__restrict__ items) {
+    const BatchItem *d = items + blockIdx.y;
+    const int nblocks = __builtin_amdgcn_readfirstlane(d->nblocks);
+    if ((int)blockIdx.x >= nblocks) return;
+    LinArgs a = a0;
+    FinArgs f = f0;
+    a.sx = uniform_ptr(d->sx); a.sy = uniform_ptr(d->sy); a.sz = uniform_ptr(d->sz);
+    {
+        const long long n = (long long)d->n;
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)n);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)n >> 32));
+        a.n = (int64_t)(((unsigned long long)hi << 32) | lo);
+    }
+    a.nblocks = nblocks; f.nblocks = nblocks;
+    a.partials = uniform_ptr(d->partials); f.partials = a.partials;
+    f.tickets = uniform_ptr(d->tickets);
+    f.out = uniform_ptr(d->out);
+    PoseK P;
+    if (GN) {
+        PoseDev *pose = uniform_ptr(d->pose);
+        a.pose = pose; f.pose = pose;
+        if (!load_pose<true>(a, P)) return;
+    } else {
+        a.pose = nullptr; f.pose = nullptr;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double v = uniform_f64(d->T[4 * i + j]);
+                P.R[3 * i + j] = v; P.r32[3 * i + j] = (float)v; f.R[3 * i + j] = v;
+            }
+            P.t32[i] = (float)uniform_f64(d->T[4 * i + 3]);
+        }
+    }
+    double acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) acc[i] = 0.0;
+    linearize_body<KIND, HALO, FILT, LB>(a, P, acc);
+    const bool last = ticket_fold_emit(acc, a, f);
+    if (GN && last && threadIdx.x == 0 && f.pose->done == PCR_LOOP_RUNNING) {
+        // (what only the step reads is fetched here, by the one thread that takes it)
+        f.trace = d->trace; f.host_T = d->host_T; f.host_state = d->host_state;
+        for (int i = 0; i < 3; ++i) { f.bb_c[i] = d->bb_c[i]; f.bb_e[i] = d->bb_e[i]; }
+        double A[6][7];
+        gn_update(f, A);
+    }
+}
+
+// start of a batched call, one wave per item: the item's tickets and trace rows zeroed (the block they live in comes from the
+// context's cache), its start pose into its PoseDev (kernel boundary in front of the first pass: no host-to-device copy of
+// state beyond the descriptors)
+__global__ void __launch_bounds__(64) k_batch_init(const BatchItem *__restrict__ items, int max_iter) {
+    const BatchItem &d = items[blockIdx.x];
+    for (int i = threadIdx.x; i < 9 * PCR_TICKET_STRIDE; i += 64) d.tickets[i] = 0u;
+    if (d.trace) for (size_t i = threadIdx.x; i < (size_t)max_iter * 45; i += 64) d.trace[i] = 0.0;
+    PoseDev *p = d.pose;
+    if (threadIdx.x != 0 || p == nullptr) return;
+    for (int i = 0; i < 16; ++i) p->T[i] = d.T[i];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) { p->R[3 * i + j] = d.T[4 * i + j]; p->r32[3 * i + j] = (float)d.T[4 * i + j]; }
+        p->t32[i] = (float)d.T[4 * i + 3];
+    }
+    p->iter = 0;
+    p->done = max_iter > 0 ? PCR_LOOP_RUNNING : PCR_LOOP_MAXITER;
+    p->tile_local = 0;
+    p->halo_deep = 1;
+}
+
 // after the RCCL all-reduce: hand the 29 doubles to the host the same zero-copy way k_finalize does
 __global__ void __launch_bounds__(64) k_publish(const double *__restrict__ out, double *host_out,
                                                 volatile uint32_t *host_flag, uint32_t seq) {
@@ -621,7 +698,8 @@ static void set_filter_bound(LinArgs &a, double bound);
 // (bits 27-29 of LinArgs::flags are internal -- the gate switch of quirk Q6, two developer timing switches; a
 // caller-supplied word must not reach them)
 #define PCR_PUBLIC_FLAGS (PCR_FLAG_ICP_RR_QUIRK | PCR_FLAG_NO_SCAN_SORT | PCR_FLAG_LOCAL_ONLY | PCR_FLAG_HOST_LOOP | PCR_FLAG_DEVICE_LOOP)
-static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, double max_dist, unsigned flags) {
+// (force_fused: a batched pass -- the fused kernel whatever the variant and the size of the scan)
+static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, double max_dist, unsigned flags, bool force_fused = false) {
     pcr_context *ctx = t->ctx;
     flags &= PCR_PUBLIC_FLAGS;
     PCR_REQUIRE(s->ctx == ctx, "scan and target belong to different contexts");
@@ -644,7 +722,7 @@ static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, dou
     // and runs fused (tools/variant_crossover.py: 100 k points 74 vs 80 us per pass, 300 k 97 vs 92, 1.06 M 190 vs 151)
     // quirk Q6: a PlaneICP pass over a float64 point target searches in float64 -- always search + reduce, always a full search
     const bool q6 = kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr;
-    const bool one_kernel = pcr_pass_is_fused(ctx, s) && !q6;
+    const bool one_kernel = (force_fused || pcr_pass_is_fused(ctx, s)) && !q6;
     if (!one_kernel && !s->nn_j) {
         HIP_TRY(pcr_scan_alloc(s, (void **)&s->nn_j, sizeof(uint32_t) * (size_t)(s->n > 0 ? s->n : 1)));
         s->nn_serial = 0;
@@ -1194,6 +1272,207 @@ pcr_status pcr_run_align(pcr_target *t, pcr_scan *s, int kind, const double T_in
     if (done == PCR_LOOP_SINGULAR) {
         pcr_set_error("Singular matrix");
         return PCR_ERR_SINGULAR;
+    }
+    return PCR_OK;
+}
+
+// ---- batched passes: many scans / start poses against one target in one launch (pcr_linearize_batch, pcr_align_batch) ----
+// The instantiation a single fused launch over this target would pick (pass_enqueue), GN = the device-resident loop.
+template <int K>
+static void launch_batch_kind(bool gn, bool halo, bool filt, bool lbf, dim3 grid, hipStream_t st, const LinArgs &a, const FinArgs &f,
+                              const BatchItem *items) {
+    const dim3 block(256);
+#define PCR_BATCH_GO(H, F, L) do { if (gn) hipLaunchKernelGGL((k_linearize_batch<K, H, 1, F, L>), grid, block, 0, st, a, f, items); \
+                                   else hipLaunchKernelGGL((k_linearize_batch<K, H, 0, F, L>), grid, block, 0, st, a, f, items); } while (0)
+    if constexpr (K == PCR_ICP || K == PCR_PLANE) {
+        if (lbf) { if (halo) PCR_BATCH_GO(1, 0, 1); else PCR_BATCH_GO(0, 0, 1); }
+        else { if (halo) PCR_BATCH_GO(1, 0, 0); else PCR_BATCH_GO(0, 0, 0); }
+    } else {
+        if (!filt) PCR_BATCH_GO(0, 0, 0);
+        else if (halo) PCR_BATCH_GO(1, 1, 0);
+        else PCR_BATCH_GO(0, 1, 0);
+    }
+#undef PCR_BATCH_GO
+}
+
+static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// pcr_run_align is the model: one launch per iteration for the WHOLE batch, queued AHEAD iterations beyond the slowest
+// unfinished item; every item reports (done << 32 | passes) in its own pinned word and its final pose next to it; an item
+// that is done makes its blocks of the later launches return at load_pose.  No stream synchronisation between iterations.
+pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int kind, const double *T, bool align, int max_iter,
+                         double tol, double max_dist, unsigned flags, double *out29, double *T_out, int *iterations,
+                         pcr_status *item_status, double *trace_or_null) {
+    pcr_context *ctx = t->ctx;
+    if (ctx->comm != nullptr) {
+        pcr_set_error("batched passes are not available on a context with a communicator attached (pcr_comm_*, pcr_group)");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr) {
+        pcr_set_error("batched PlaneICP passes are not available over a float64 point target (quirk Q6 runs search + reduce)");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    PCR_REQUIRE(n_items >= 0 && n_items <= 65535, "a batch call takes at most 65535 items");
+    if (n_items == 0) return PCR_OK;
+    pcr_scan *big = scans[0];
+    for (int i = 1; i < n_items; ++i) if (scans[i]->n > big->n) big = scans[i];
+    Pass ps;
+    // (pass_setup also makes sure the context's pass scratch exists -- pcr_ensure_scratch: a one-time, size-independent
+    // allocation that fixes ctx->max_blocks, which choose_blocks reads; the batch itself uses none of those buffers but d_tile_ctr)
+    PCR_TRY(pass_setup(&ps, t, big, kind, max_dist, flags, true));
+    if (!ps.one_kernel || !ps.fused_fin) {
+        pcr_set_error("batched passes need the fused pipeline (pcr_set_fuse_finalize(1))");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    const size_t B = (size_t)n_items;
+    if (align && max_iter <= 0) {                      // as pcr_run_align: nothing runs
+        memcpy(T_out, T, B * 16 * sizeof(double));
+        for (size_t i = 0; i < B; ++i) { if (iterations) iterations[i] = 0; if (item_status) item_status[i] = PCR_OK; }
+        return PCR_OK;
+    }
+    // ---- device block: descriptors | tickets | poses | sums | partial rows | trace rows (from / back to the context's cache)
+    std::vector<int> nb(B);
+    size_t rows = 0;
+    int max_nb = 0;
+    for (size_t i = 0; i < B; ++i) {
+        nb[i] = choose_blocks(ctx, scans[i]->n);
+        rows += (size_t)nb[i] + 8;
+        if (nb[i] > max_nb) max_nb = nb[i];
+    }
+    const size_t trace_rows = align && trace_or_null ? (size_t)max_iter : 0;
+    const size_t pose_stride = round_up(sizeof(PoseDev), 128), ticket_bytes = sizeof(uint32_t) * 9 * PCR_TICKET_STRIDE;
+    const size_t off_tickets = round_up(B * sizeof(BatchItem), 256);      // (the descriptors sit at the start of the block)
+    const size_t off_pose = off_tickets + B * ticket_bytes;
+    const size_t off_out = off_pose + B * pose_stride;
+    const size_t off_part = off_out + B * 32 * sizeof(double);
+    const size_t off_trace = off_part + rows * 32 * sizeof(double);
+    const size_t total = off_trace + B * trace_rows * 45 * sizeof(double);
+    // The block goes back to the cache when this function returns, while up to AHEAD trailing launches that read `items` and
+    // the items' PoseDev may still be queued: safe because every user of the cache runs on the context's ONE stream, behind them.
+    DevBuf<char> ws;
+    HIP_TRY(ws.alloc_bytes(total));
+    // ---- pinned block: per item 24 doubles (pose 16, state word, padding) | 32 sums per item | staging of the descriptors
+    const size_t h_state = 0, h_out = h_state + B * 24 * sizeof(double), h_items = h_out + B * 32 * sizeof(double);
+    const size_t h_need = h_items + B * sizeof(BatchItem);
+    if (ctx->h_batch_cap < h_need) {
+        if (ctx->h_batch) { HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(hipHostFree(ctx->h_batch)); }
+        ctx->h_batch = nullptr; ctx->h_batch_dev = nullptr; ctx->h_batch_cap = 0;
+        const size_t cap = round_up(h_need * 2 > 65536 ? h_need * 2 : 65536, 4096);
+        HIP_TRY(hipHostMalloc((void **)&ctx->h_batch, cap, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&ctx->h_batch_dev, ctx->h_batch, 0));
+        ctx->h_batch_cap = cap;
+    }
+    BatchItem *hi = (BatchItem *)(ctx->h_batch + h_items);
+    auto state_word = [&](size_t i) { return (volatile unsigned long long *)(ctx->h_batch + h_state + (i * 24 + 16) * sizeof(double)); };
+    auto host_pose = [&](size_t i) { return (const double *)(ctx->h_batch + h_state + i * 24 * sizeof(double)); };
+    size_t row = 0;
+    for (size_t i = 0; i < B; ++i) {
+        const pcr_scan *s = scans[i];
+        BatchItem &d = hi[i];
+        memset(&d, 0, sizeof d);
+        d.sx = s->x; d.sy = s->y; d.sz = s->z; d.n = s->n;
+        d.partials = (double *)(ws.p + off_part) + row * 32;
+        row += (size_t)nb[i] + 8;
+        d.tickets = (uint32_t *)(ws.p + off_tickets + i * ticket_bytes);
+        d.pose = align ? (PoseDev *)(ws.p + off_pose + i * pose_stride) : nullptr;
+        d.out = (double *)(ws.p + off_out) + i * 32;
+        d.trace = trace_rows ? (double *)(ws.p + off_trace) + i * trace_rows * 45 : nullptr;
+        d.host_T = (double *)(ctx->h_batch_dev + h_state + i * 24 * sizeof(double));
+        d.host_state = (unsigned long long *)(ctx->h_batch_dev + h_state + (i * 24 + 16) * sizeof(double));
+        d.nblocks = nb[i];
+        for (int k = 0; k < 3; ++k) { d.bb_c[k] = s->bb_c[k]; d.bb_e[k] = s->bb_e[k]; }
+        memcpy(d.T, T + 16 * i, sizeof d.T);
+        *state_word(i) = 0;
+    }
+    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+    const BatchItem *items = (const BatchItem *)ws.p;
+    HIP_TRY(hipMemcpyAsync(ws.p, hi, B * sizeof(BatchItem), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_batch_init, dim3((unsigned)B), dim3(64), 0, ctx->stream, items, align ? max_iter : 0);
+    HIP_TRY(hipGetLastError());
+
+    ps.a.pose = nullptr; ps.f.pose = nullptr;          // (per item: the descriptor's)
+    // (ps.f.tile_ctr stays the context's: every item's emitting block re-zeroes those counters in finalize_emit -- all writers
+    // store 0 and the fused kernels never read them, so the concurrent stores are harmless)
+    ps.f.max_iter = max_iter; ps.f.tol = tol;
+    const bool filt = t->is_voxel && ps.a.band_f > 0.f;
+    const bool halo = t->is_voxel ? (filt && t->filter->cs_h != nullptr) : t->cs_h != nullptr;
+    const bool lbf = !t->is_voxel && ps.a.gf.lbox != nullptr;
+    const dim3 grid((unsigned)max_nb, (unsigned)B);
+    auto enqueue_pass = [&]() -> pcr_status {
+        retire_completed(ctx);
+        ProfEvent ev;
+        if (ctx->prof_on) ctx->prof_this_pass = (ctx->prof_pass++ % (uint64_t)ctx->prof_period) == 0;
+        pcr_prof_begin(ctx, PCR_K_LINEARIZE, &ev);
+        {
+            RoctxRange range("pcr:linearize_batch");
+            switch (kind) {
+            case PCR_ICP: launch_batch_kind<PCR_ICP>(align, halo, filt, lbf, grid, ctx->stream, ps.a, ps.f, items); break;
+            case PCR_PLANE: launch_batch_kind<PCR_PLANE>(align, halo, filt, lbf, grid, ctx->stream, ps.a, ps.f, items); break;
+            case PCR_VPLANE: launch_batch_kind<PCR_VPLANE>(align, halo, filt, lbf, grid, ctx->stream, ps.a, ps.f, items); break;
+            default: launch_batch_kind<PCR_NDT>(align, halo, filt, lbf, grid, ctx->stream, ps.a, ps.f, items); break;
+            }
+        }
+        pcr_prof_end(ctx, &ev);
+        HIP_TRY(hipGetLastError());
+        return PCR_OK;
+    };
+
+    if (!align) {
+        PCR_TRY(enqueue_pass());
+        double *ho = (double *)(ctx->h_batch + h_out);
+        HIP_TRY(hipMemcpyAsync(ho, ws.p + off_out, B * 32 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < B; ++i) memcpy(out29 + 29 * i, ho + 32 * i, 29 * sizeof(double));
+        return PCR_OK;
+    }
+
+    // what the unfinished items report: how many there are and the fewest passes any of them has completed
+    auto progress = [&](int *fin) {
+        int running = 0, lo = 0x7fffffff;
+        for (size_t i = 0; i < B; ++i) {
+            const unsigned long long w = *state_word(i);
+            if ((int)(unsigned)(w >> 32) != PCR_LOOP_RUNNING) continue;
+            ++running;
+            const int p = (int)(unsigned)(w & 0xffffffffull);
+            if (p < lo) lo = p;
+        }
+        *fin = lo;
+        return running;
+    };
+    const int AHEAD = 2;
+    int enq = 0;
+    long spin = 0;
+    for (;;) {
+        int fin = 0;
+        if (progress(&fin) == 0) break;
+        if (enq < max_iter && enq < fin + AHEAD) {
+            PCR_TRY(enqueue_pass());
+            ++enq;
+            spin = 0;
+            continue;
+        }
+        __builtin_ia32_pause();
+        if (++spin > 4000000L) {    // a very long pass (or a fault): block, then look again
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            int fin2 = 0;
+            if (progress(&fin2) != 0 && fin2 == fin && !(enq < max_iter)) {
+                pcr_set_error("device Gauss-Newton loop of a batch made no progress");
+                return PCR_ERR_HIP;
+            }
+            spin = 0;
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    for (size_t i = 0; i < B; ++i) {
+        const unsigned long long w = *state_word(i);
+        const double *hT = host_pose(i);
+        for (int k = 0; k < 16; ++k) T_out[16 * i + k] = hT[k];
+        if (iterations) iterations[i] = (int)(unsigned)(w & 0xffffffffull);
+        if (item_status) item_status[i] = (int)(unsigned)(w >> 32) == PCR_LOOP_SINGULAR ? PCR_ERR_SINGULAR : PCR_OK;
+    }
+    if (trace_rows) {
+        HIP_TRY(hipMemcpyAsync(trace_or_null, ws.p + off_trace, B * trace_rows * 45 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     return PCR_OK;
 }

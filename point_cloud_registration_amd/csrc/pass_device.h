@@ -838,6 +838,35 @@ struct FinArgs {
     volatile unsigned long long *host_state;   // ... then (done << 32 | passes completed), one 8-byte store
 };
 
+// ---- batched fused pass (k_linearize_batch): what differs between the items of one launch --------------
+// One descriptor per item in HBM, indexed by blockIdx.y, written by the host before the first launch and read-only to the
+// kernels (so it may travel the scalar path); everything else of LinArgs / FinArgs (target geometry, gate, bounds, flags,
+// max_iter, tol) is shared by the batch.  An item's partial-sum rows, tickets, pose, sums and trace rows are its own: its
+// blocks fold exactly as the blocks of a single launch over that scan do.
+struct BatchItem {
+    const float *sx, *sy, *sz;       // the item's scan, Morton-sorted as pcr_scan_create sorts it (items may share one)
+    int64_t n;
+    double *partials;                // [nblocks + 8][32]
+    uint32_t *tickets;               // 9 tickets, PCR_TICKET_STRIDE words apart, zero before the first launch
+    PoseDev *pose;                   // device-resident loop: the item's pose and state
+    double *out;                     // 32 doubles
+    double *trace;                   // [max_iter][45] or NULL
+    double *host_T;                  // pinned: the item's final pose ...
+    unsigned long long *host_state;  // ... then (done << 32 | passes completed)
+    int nblocks;                     // choose_blocks(ctx, n): blocks with blockIdx.x >= nblocks return at once
+    int pad;
+    float bb_c[3], bb_e[3];          // bounding box of the scan (gn_update)
+    double T[16];                    // start pose of the loop (k_batch_init) / the pose of a plain pass
+};
+
+template <typename T>
+__device__ __forceinline__ T *uniform_ptr(T *p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return (T *)(((unsigned long long)hi << 32) | lo);
+}
+
 // tot[0..31] (shared memory, complete before the call) -> the 29-vector in HBM and, optionally, in
 // pinned host memory followed by the sequence number; also re-arms the tile counters.
 __device__ __forceinline__ void finalize_emit(const FinArgs &f, const double *tot) {

@@ -215,6 +215,11 @@ struct pcr_context {
     PoseDev *d_pose = nullptr;
     double *d_trace = nullptr;
     int trace_cap = 0;
+    // batched passes (pcr_linearize_batch / pcr_align_batch): pinned + mapped block for the per-item progress words and poses,
+    // the items' 29 sums and the staging copy of the item descriptors; grown on demand, freed with the context
+    char *h_batch = nullptr;
+    char *h_batch_dev = nullptr;
+    size_t h_batch_cap = 0;
     int variant = 0;
     int nn_mode = 0;             // 0 per-lane search; 2 wave-cooperative, LDS-staged (developer builds); 3 = 0 without the float32 filter of the
                                  // centroid search; 4 = wave-cooperative with an MFMA distance filter (developer builds, round 5)
@@ -349,6 +354,13 @@ struct pcr_scan {
 hipError_t pcr_scan_alloc(pcr_scan *s, void **p, size_t bytes);
 void pcr_scan_free(pcr_scan *s, void *p);      // one block back to the cache (nullptr: no-op)
 
+// S scans uploaded together (pcr_scan_batch_create): each one sorted exactly as pcr_scan_create sorts it, each owning its blocks
+struct pcr_scan_batch {
+    pcr_context *ctx = nullptr;
+    std::vector<pcr_scan *> scans;
+    int64_t n_points = 0;
+};
+
 // what a pass does with the matches of the previous one
 #define PCR_NN_FULL 0     // plain exact search of every point
 #define PCR_NN_TRACK 1    // exact search of every point that also records the margin to the runner-up
@@ -378,6 +390,11 @@ pcr_status pcr_run_linearize(pcr_target *t, pcr_scan *s, int kind, const double 
 pcr_status pcr_run_align(pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
                          double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 pcr_status pcr_run_nn(pcr_target *t, const float *d_q, int64_t m, double r_max, void *d_dist, int64_t *d_idx, int f64);
+// the batched fused pass: item i = scans[i] at pose T[16 i ..].  align = false: one launch, out29[29 i ..]; align = true: the
+// device-resident Gauss-Newton loop of every item, one launch per iteration for the whole batch
+pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int kind, const double *T, bool align, int max_iter,
+                         double tol, double max_dist, unsigned flags, double *out29, double *T_out, int *iterations,
+                         pcr_status *item_status, double *trace_or_null);
 pcr_status pcr_ensure_scratch(pcr_context *ctx, int64_t n_points);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 

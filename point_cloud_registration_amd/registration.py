@@ -42,6 +42,53 @@ class UploadedScan:
         self._scan.close()
 
 
+def normalize_batch_inputs(sources, poses=None):
+    """Input forms of ``align_batch`` / ``calc_H_g_e2_batch`` -> ``(arrays, offsets, item_scan, Ts)``.  Pure (no GPU).
+
+    ``sources``: a sequence of (N_i, 3) arrays -- one item each; the same array OBJECT appearing several times is listed
+    once -- or ONE (N, 3) array, which every pose of ``poses`` is applied to (multi-start).  ``poses``: (B, 4, 4), or (4, 4)
+    broadcast over the items, default identity.
+    Returns the distinct scans as float32 arrays (registration.py:83), their offsets in the concatenated upload
+    (len(arrays) + 1, int64), the scan index of every item (B, intc) and the poses as (B, 4, 4) float64."""
+    if poses is not None:
+        poses = np.asarray(poses, dtype=np.float64)
+        if poses.shape[-2:] != (4, 4) or poses.ndim not in (2, 3):
+            raise ValueError("poses must have shape (B, 4, 4) or (4, 4)")
+    single = isinstance(sources, np.ndarray) and sources.ndim == 2
+    if single:
+        B = poses.shape[0] if poses is not None and poses.ndim == 3 else 1
+        items = [sources] * B
+    else:
+        try:
+            items = list(sources)
+        except TypeError:
+            raise ValueError("sources must be a sequence of (N, 3) arrays or one (N, 3) array") from None
+        B = len(items)
+    if B == 0:
+        raise ValueError("an empty batch: no sources / no poses")
+    arrays, index, item_scan = [], {}, np.zeros(B, np.intc)
+    for i, src in enumerate(items):
+        k = index.get(id(src))
+        if k is None:
+            a = np.asarray(src)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError(f"source {i} must have shape (N, 3)")
+            k = index[id(src)] = len(arrays)
+            arrays.append(a.astype(np.float32, copy=False))
+        item_scan[i] = k
+    if poses is None:
+        Ts = np.broadcast_to(np.eye(4), (B, 4, 4)).copy()
+    elif poses.ndim == 2:
+        Ts = np.broadcast_to(poses, (B, 4, 4)).copy()
+    elif poses.shape[0] == B:
+        Ts = np.ascontiguousarray(poses)
+    else:
+        raise ValueError(f"{poses.shape[0]} poses for {B} sources")
+    offsets = np.zeros(len(arrays) + 1, np.int64)
+    np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+    return arrays, offsets, item_scan, Ts
+
+
 class Registration:
     KIND = None           # _capi.ICP / PLANE / VPLANE / NDT in the subclasses
 
@@ -118,6 +165,62 @@ class Registration:
             cur_T = plus(cur_T, dx)
         self.last_iterations = it + 1 if self.max_iter > 0 else 0
         return cur_T
+
+    # -- batches: many scans and / or start poses against the target in one launch --------------
+    def align_batch(self, sources, init_Ts=None, return_info=False):
+        """``align`` of B items at once (``pcr_align_batch``): ``sources`` is a sequence of (N_i, 3) arrays, or ONE (N, 3)
+        array with ``init_Ts`` of shape (B, 4, 4) (multi-start); ``init_Ts``: (B, 4, 4), or (4, 4) for all, default identity.
+        Returns the (B, 4, 4) float64 poses, each bit-identical to ``align`` of that item alone through the fused kernel;
+        sets ``last_batch_iterations`` / ``last_batch_correspondences`` / ``last_batch_status``.  Items whose normal equations
+        are singular (quirk Q7) raise ``numpy.linalg.LinAlgError`` naming them, unless ``return_info=True``, which returns
+        ``(Ts, info)`` instead (``info["singular"]`` lists them; their pose is the one of the failed solve)."""
+        arrays, item_scan, Ts = self._batch_inputs(sources, init_Ts)
+        batch = _capi.ScanBatch(self._ctx(), arrays)
+        try:
+            T, iters, status, trace = _capi.align_batch(self._target, batch, self.KIND, Ts, self.max_iter, self.tol,
+                                                        self._max_dist(), self._call_flags(), item_scan=item_scan,
+                                                        want_trace=True)
+        finally:
+            batch.close()
+        B = T.shape[0]
+        cnt = np.zeros(B, np.int64)
+        for i in range(B):
+            if iters[i] > 0:
+                cnt[i] = int(round(trace[i, iters[i] - 1, 16 + 28]))
+        self.last_batch_iterations = iters.astype(np.int64)
+        self.last_batch_correspondences = cnt
+        self.last_batch_status = status.astype(np.int64)
+        singular = [int(i) for i in np.flatnonzero(status == _capi.PCR_ERR_SINGULAR)]
+        if return_info:
+            return T, {"iterations": self.last_batch_iterations, "correspondences": cnt, "status": self.last_batch_status,
+                       "singular": singular}
+        if singular:
+            raise np.linalg.LinAlgError(f"Singular matrix (batch items {singular})")
+        return T
+
+    def calc_H_g_e2_batch(self, cur_Ts, sources):
+        """``calc_H_g_e2`` of B items in one launch -> ``(H (B, 6, 6), g (B, 6), e2 (B,))``; input forms as ``align_batch``."""
+        arrays, item_scan, Ts = self._batch_inputs(sources, cur_Ts)
+        batch = _capi.ScanBatch(self._ctx(), arrays)
+        try:
+            out = _capi.linearize_batch(self._target, batch, self.KIND, Ts, self._max_dist(), self._call_flags(),
+                                        item_scan=item_scan)
+        finally:
+            batch.close()
+        B = out.shape[0]
+        H, g, e2, cnt = np.zeros((B, 6, 6)), np.zeros((B, 6)), np.zeros(B), np.zeros(B, np.int64)
+        for i in range(B):
+            H[i], g[i], e2[i], cnt[i] = _capi.unpack29(out[i])
+        self.last_batch_correspondences = cnt
+        return H, g, e2
+
+    def _batch_inputs(self, sources, poses):
+        if not self._is_target_set:
+            raise ValueError("Target is not set.")
+        if self._comm is not None or self._group is not None:
+            raise ValueError("batched alignment runs on one GPU of one process: not with comm= or devices=")
+        arrays, _, item_scan, Ts = normalize_batch_inputs(sources, poses)
+        return arrays, item_scan, Ts
 
     # -- internals -----------------------------------------------------------------------------
     def _ctx(self):

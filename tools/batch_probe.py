@@ -1,0 +1,142 @@
+"""Developer probe: what does batching buy?  `align_batch` of B items against a loop of B single `align(handle)` calls.
+
+ICP and PlaneICP on the B-01 stand-in (street(1_060_000)), B in {1, 4, 16, 64} harness scans of 100 k and of 2 k points,
+uploaded beforehand, max_iter = 30, tol = 1e-3.  The single loop runs on the library of ANOTHER revision (the parent commit:
+`tools/build_rev_lib.sh <rev> parent`, loaded with PCR_LIB), the batch on the working tree's.  A library is chosen when the
+binding is imported, so every measurement is a child process; the two sides alternate, `--reps` times each, and the table
+gives the median over the repetitions and their spread (max - min) in milliseconds.
+
+    python tools/batch_probe.py --parent-lib build/exp/libpcr_parent.so [--reps 5] [--out table.md]
+    (child mode, used by the probe itself:  --child batch|single  -> one JSON line)
+"""
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+SIZES = (100_000, 2_000)
+BATCHES = (1, 4, 16, 64)
+KINDS = ("icp", "plane")
+
+
+def make_clouds(path):
+    """The target and the scans of every configuration, generated once (the children load them)."""
+    import numpy as np
+    from point_cloud_registration_amd.synthetic import street, harness_scan
+    target = street(1_060_000, seed=0)
+    np.savez(path, target=target, **{f"s{n}": np.stack([harness_scan(target, n, seed=100 + s) for s in range(max(BATCHES))])
+                                     for n in SIZES})
+
+
+def child(mode, inner, clouds):
+    import numpy as np
+    import point_cloud_registration_amd as pcr
+    from point_cloud_registration_amd import _capi
+
+    data = np.load(clouds)
+    target = data["target"]
+    scans = {n: [np.ascontiguousarray(a) for a in data[f"s{n}"]] for n in SIZES}
+    out = {}
+    for kind in KINDS:
+        reg = (pcr.ICP if kind == "icp" else pcr.PlaneICP)(max_iter=30, tol=1e-3, max_dist=2.0)
+        reg.set_target(target)
+        ctx = reg._ctx()
+        for n in SIZES:
+            for B in BATCHES:
+                items = scans[n][:B]
+                Ts = np.broadcast_to(np.eye(4), (B, 4, 4)).copy()
+                if mode == "batch":
+                    batch = _capi.ScanBatch(ctx, items)
+
+                    def run():
+                        return _capi.align_batch(reg._target, batch, reg.KIND, Ts, reg.max_iter, reg.tol, reg._max_dist(),
+                                                 reg._call_flags(), want_trace=True)[1]
+                else:
+                    handles = [reg.upload(a) for a in items]
+
+                    def run():
+                        its = []
+                        for h in handles:
+                            reg.align(h)
+                            its.append(reg.last_iterations)
+                        return its
+                run()                                   # warm-up (and, for a voxel target, lazily built indices)
+                ctx.synchronize()
+                ts = []
+                for _ in range(inner):
+                    t0 = time.perf_counter()
+                    its = run()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                out[f"{kind}/{n}/{B}"] = {"ms": statistics.median(ts), "iterations": [int(i) for i in its]}
+                if mode == "batch":
+                    batch.close()
+                else:
+                    for h in handles:
+                        h.close()
+    print("PROBE " + json.dumps(out), flush=True)
+
+
+def run_child(mode, lib, inner, clouds):
+    env = dict(os.environ)
+    env.pop("PCR_LIB", None)
+    if lib:
+        env["PCR_LIB"] = os.path.abspath(lib)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--inner", str(inner), "--clouds", clouds],
+                       env=env,
+                       capture_output=True, text=True, timeout=600)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise SystemExit(f"child '{mode}' failed with status {r.returncode}")
+    line = [l for l in r.stdout.splitlines() if l.startswith("PROBE ")][-1]
+    return json.loads(line[6:])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--parent-lib", help="libpcr_hip.so of the revision the single loop runs on (default: the working tree's)")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--inner", type=int, default=3, help="timed calls per configuration inside one child (their median counts)")
+    ap.add_argument("--out", help="also write the table to this file")
+    ap.add_argument("--child", choices=("batch", "single"))
+    ap.add_argument("--clouds", help="(child mode) the .npz of make_clouds")
+    a = ap.parse_args()
+    if a.child:
+        child(a.child, a.inner, a.clouds)
+        return
+    import tempfile
+    res = {"batch": [], "single": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        clouds = os.path.join(tmp, "clouds.npz")
+        make_clouds(clouds)
+        for _ in range(a.reps):                          # alternating: single, batch, single, batch, ...
+            res["single"].append(run_child("single", a.parent_lib, a.inner, clouds))
+            res["batch"].append(run_child("batch", None, a.inner, clouds))
+    lines = ["| kind | points | B | B single aligns, parent (ms) | spread | align_batch (ms) | spread | ratio | iterations equal |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for kind in KINDS:
+        for n in SIZES:
+            for B in BATCHES:
+                key = f"{kind}/{n}/{B}"
+                s = [r[key]["ms"] for r in res["single"]]
+                b = [r[key]["ms"] for r in res["batch"]]
+                same = all(r[key]["iterations"] == res["single"][0][key]["iterations"] for r in res["single"] + res["batch"])
+                ms, mb = statistics.median(s), statistics.median(b)
+                lines.append(f"| {kind} | {n} | {B} | {ms:.3f} | {max(s) - min(s):.3f} | {mb:.3f} | {max(b) - min(b):.3f} | "
+                             f"{ms / mb:.2f}x | {'yes' if same else 'NO'} |")
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
