@@ -736,7 +736,7 @@ extern "C" pcr_status pcr_linearize(pcr_target *t, pcr_scan *s, int kind, const 
 }
 
 // ---- Gauss-Newton driver behind the boundary (registration.py:71-113) -------------------------
-// Default: the device-resident loop (kernels.hip: pcr_run_align).  PCR_FLAG_HOST_LOOP keeps the
+// Default: the device-resident loop (pass.hip: pcr_run_align).  PCR_FLAG_HOST_LOOP keeps the
 // host-driven form (one pcr_linearize + host solve per iteration), the same arithmetic from gn_math.h.
 static pcr_status align_host_loop(pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
                                   double max_dist, unsigned flags, double T_out[16], int *iterations,

@@ -918,7 +918,7 @@ pcr_status pcr_build_point_grid(pcr_context *ctx, const float *d_xyz, int64_t n,
 }
 
 // The second, DEEPER set of extended lists of a point target (halo PCR_HALO2_FRAC x cell), built by the first pass that
-// gets its cost back (kernels.hip: pass_setup); a pass picks one of the two sets by how far the scan moved.
+// gets its cost back (pass.hip: pass_setup); a pass picks one of the two sets by how far the scan moved.
 pcr_status pcr_build_deep_lists(pcr_context *ctx, pcr_target *t) {
     if (t->is_voxel || !t->cs_h || t->n <= 0 || t->cs_h2) return PCR_OK;
     // (an opt-out and a size cap.  PCR_DEEP_LISTS=0 never builds the set; the estimate -- copies per point scale

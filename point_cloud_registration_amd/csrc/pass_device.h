@@ -1,5 +1,5 @@
 // Device-side building blocks shared by the shipped kernels (kernels.hip) and the developer / A-B kernels
-// (kernels_dev.hip): pass arguments, pose handling, per-correspondence accumulation, the folds, tile hand-out,
+// (kernels_dev.hip), and what the host side of a pass (pass.hip) shares with them: pass arguments, launch functions, pose handling, per-correspondence accumulation, the folds, tile hand-out,
 // the per-lane search of one scan point.
 #pragma once
 
@@ -1002,6 +1002,31 @@ __device__ __forceinline__ bool ticket_fold_emit(double *acc, const LinArgs &a, 
     finalize_emit(f, tot);
     return true;
 }
+
+// ---- launch functions of kernels.hip: run-time arguments -> kernel instantiation (the host side of a pass is pass.hip) ----
+#define PCR_LIST_CHUNK 1024          // scan points per chunk of a LIST pass (kernels.hip: nn_chunk_list)
+// Which fused kernel (k_linearize_finalize / k_linearize_batch) a pass over a target runs, the kind aside.  Point targets:
+// halo = the target has the extended lists, lb = heavy target (ranges through their leaf / group boxes); voxel targets: filt =
+// float32 filter search over the rounded centroids (halo then refers to the FILTER index); gn = the Gauss-Newton step inline.
+struct FusedVariant {
+    bool halo, filt, lb, gn;
+};
+void launch_certify(bool voxel, dim3 grid, hipStream_t st, const LinArgs &a);
+void launch_nn_scan(int voxel, int mode, bool halo, int local, dim3 grid, hipStream_t st, const LinArgs &a);
+void launch_nn_filter(bool halo, int local, bool separate_fix, bool q6, dim3 grid, hipStream_t st, const LinArgs &a);
+void launch_nn_mfma(bool halo, int local, dim3 grid, hipStream_t st, const LinArgs &a);      // (developer build)
+void launch_reduce_kind(int kind, bool fix, dim3 grid, hipStream_t st, const LinArgs &a, const FinArgs &f);
+void launch_fused(int kind, const FusedVariant &v, dim3 grid, hipStream_t st, const LinArgs &a, const FinArgs &f);
+void launch_fused_batch(int kind, const FusedVariant &v, dim3 grid, hipStream_t st, const LinArgs &a, const FinArgs &f,
+                        const BatchItem *items);
+void launch_gn_update(hipStream_t st, const FinArgs &f);
+void launch_pose_init(hipStream_t st, PoseDev *pose, const double T[16], int max_iter);
+void launch_batch_init(hipStream_t st, const BatchItem *items, unsigned n_items, int max_iter);
+void launch_publish(hipStream_t st, const double *out, double *host_out, volatile uint32_t *host_flag, uint32_t seq);
+void launch_nn_query(const pcr_target *t, int form, hipStream_t st, const float *q, int64_t m, double bound2, double rmax, void *dist,
+                     int64_t *idx);
+enum { PCR_OCC_POINT, PCR_OCC_VOXEL, PCR_OCC_FILTER, PCR_OCC_POINT_LB, PCR_OCC_MFMA };
+int nn_blocks_per_cu(int which);
 
 // ---- developer / A-B kernels (kernels_dev.hip): unfused folds, the wave-cooperative search, work counters ----
 void pcr_dev_launch_linearize(int kind, bool halo, dim3 grid, hipStream_t st, const LinArgs &a);

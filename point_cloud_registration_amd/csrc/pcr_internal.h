@@ -207,7 +207,7 @@ struct pcr_context {
     double *h_out = nullptr;        // pinned + mapped: 32 doubles, then the completion sequence number
     double *h_out_dev = nullptr;    // device-side address of h_out
     uint32_t seq = 0;
-    uint32_t passes_since_query = 0;   // see retire_completed (kernels.hip)
+    uint32_t passes_since_query = 0;   // see retire_completed (pass.hip)
     bool stall_debug = false;          // PCR_STALL_DEBUG: report where a pass slower than 1 ms spent its time
     int retire_period = 0;             // hipStreamQuery every n-th pass (PCR_RETIRE_PERIOD; 0 = never, the default)
     // device-resident Gauss-Newton loop: pose in HBM, per-iteration trace rows (16 + 29 doubles),
@@ -223,7 +223,7 @@ struct pcr_context {
     int variant = 0;
     int nn_mode = 0;             // 0 per-lane search; 2 wave-cooperative, LDS-staged (developer builds); 3 = 0 without the float32 filter of the
                                  // centroid search; 4 = wave-cooperative with an MFMA distance filter (developer builds, round 5)
-    // certified reuse of the previous pass' matches (see kernels.hip: choose_nn_mode)
+    // certified reuse of the previous pass' matches (see pass.hip: host_choose_mode)
     double local_frac = 0.35;    // block-local tile hand-out when the scan moved less than this x cell size (PCR_LOCAL_FRAC)
     double voxel_cell_mult = 2.0; // PCR_VOXEL_CELL_MULT: centroid grid cell edge in voxels
     int vox_filter = 1;          // PCR_VOX_FILTER=0: plain passes search the centroids in float64 (no float32 filter)
@@ -384,7 +384,7 @@ pcr_status pcr_attach_points_f64(pcr_context *ctx, pcr_target *t, const double *
 pcr_status pcr_permute_rows_f64(pcr_context *ctx, const double *d_in, int64_t n, int in_stride, const int *cols,
                                 int ncols, const PtD *means, double *out);
 
-// ---- kernels.hip
+// ---- pass.hip
 pcr_status pcr_run_linearize(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
                              unsigned flags, double out[29]);
 pcr_status pcr_run_align(pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,

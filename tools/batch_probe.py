@@ -7,6 +7,8 @@ binding is imported, so every measurement is a child process; the two sides alte
 gives the median over the repetitions and their spread (max - min) in milliseconds.
 
     python tools/batch_probe.py --parent-lib build/exp/libpcr_parent.so [--reps 5] [--out table.md]
+    ... --ab: the comparison of two LIBRARIES instead (a refactor that must not cost host time): the single loop and the batch
+    each under the parent's library and under the working tree's, alternating; --sizes / --batches / --kinds cut the grid
     (child mode, used by the probe itself:  --child batch|single  -> one JSON line)
 """
 
@@ -34,6 +36,22 @@ def make_clouds(path):
     target = street(1_060_000, seed=0)
     np.savez(path, target=target, **{f"s{n}": np.stack([harness_scan(target, n, seed=100 + s) for s in range(max(BATCHES))])
                                      for n in SIZES})
+
+
+def ab_table(res):
+    """--ab: per configuration and mode, parent against working tree; the last column is the acceptance test of a host-side
+    refactor (the median may not rise by more than the parent's own spread)."""
+    lines = ["| mode | kind | points | B | parent median (ms) | parent spread | head median (ms) | head spread | head - parent | within parent's spread |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    for mode in ("single", "batch"):
+        for key in res[mode, "parent"][0]:
+            p = [r[key]["ms"] for r in res[mode, "parent"]]
+            h = [r[key]["ms"] for r in res[mode, "head"]]
+            mp, mh, sp = statistics.median(p), statistics.median(h), max(p) - min(p)
+            kind, n, B = key.split("/")
+            lines.append(f"| {mode} | {kind} | {n} | {B} | {mp:.4f} | {sp:.4f} | {mh:.4f} | {max(h) - min(h):.4f} | {mh - mp:+.4f} | "
+                         f"{'yes' if mh - mp <= sp else 'NO'} |")
+    return "\n".join(lines)
 
 
 def child(mode, inner, clouds):
@@ -84,12 +102,13 @@ def child(mode, inner, clouds):
     print("PROBE " + json.dumps(out), flush=True)
 
 
-def run_child(mode, lib, inner, clouds):
+def run_child(mode, lib, inner, clouds, a):
     env = dict(os.environ)
     env.pop("PCR_LIB", None)
     if lib:
         env["PCR_LIB"] = os.path.abspath(lib)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--inner", str(inner), "--clouds", clouds],
+    grid = [f"--{k}={v}" for k, v in (("sizes", a.sizes), ("batches", a.batches), ("kinds", a.kinds)) if v]
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--inner", str(inner), "--clouds", clouds] + grid,
                        env=env,
                        capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
@@ -107,7 +126,18 @@ def main():
     ap.add_argument("--out", help="also write the table to this file")
     ap.add_argument("--child", choices=("batch", "single"))
     ap.add_argument("--clouds", help="(child mode) the .npz of make_clouds")
+    ap.add_argument("--ab", action="store_true", help="single and batch under BOTH libraries (parent against working tree)")
+    ap.add_argument("--sizes", help="comma-separated subset of the scan sizes")
+    ap.add_argument("--batches", help="comma-separated subset of the batch sizes")
+    ap.add_argument("--kinds", help="comma-separated subset of icp,plane")
     a = ap.parse_args()
+    global SIZES, BATCHES, KINDS
+    if a.sizes:
+        SIZES = tuple(int(v) for v in a.sizes.split(","))
+    if a.batches:
+        BATCHES = tuple(int(v) for v in a.batches.split(","))
+    if a.kinds:
+        KINDS = tuple(a.kinds.split(","))
     if a.child:
         child(a.child, a.inner, a.clouds)
         return
@@ -116,9 +146,21 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         clouds = os.path.join(tmp, "clouds.npz")
         make_clouds(clouds)
+        if a.ab:
+            res = {(m, side): [] for m in ("single", "batch") for side in ("parent", "head")}
+            for _ in range(a.reps):                      # alternating: parent, head, parent, head, ...
+                for m in ("single", "batch"):
+                    res[m, "parent"].append(run_child(m, a.parent_lib, a.inner, clouds, a))
+                    res[m, "head"].append(run_child(m, None, a.inner, clouds, a))
+            text = ab_table(res)
+            print(text)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write(text + "\n")
+            return
         for _ in range(a.reps):                          # alternating: single, batch, single, batch, ...
-            res["single"].append(run_child("single", a.parent_lib, a.inner, clouds))
-            res["batch"].append(run_child("batch", None, a.inner, clouds))
+            res["single"].append(run_child("single", a.parent_lib, a.inner, clouds, a))
+            res["batch"].append(run_child("batch", None, a.inner, clouds, a))
     lines = ["| kind | points | B | B single aligns, parent (ms) | spread | align_batch (ms) | spread | ratio | iterations equal |",
              "|---|---|---|---|---|---|---|---|---|"]
     for kind in KINDS:
