@@ -47,7 +47,8 @@ def _float_array(a):
 def create_gn_set(J, r):
     """(N, D) Jacobian and (N,) residuals -> P (M, N) float64, M = D (D + 1) / 2 + D + 1 (caratheodory.py:118-138):
     J[:, a] J[:, b] for (a, b) in ``np.triu_indices(D)`` order, then J[:, d] r, then r^2 -- bit for bit the reference's
-    values for float32, float64 and mixed inputs.  The result is C-contiguous (the reference returns a transposed view)."""
+    values for float32, float64 and mixed inputs, including the +0.0 that ``np.einsum`` leaves where a J J product is -0.0.
+    The result is C-contiguous (the reference returns a transposed view)."""
     J, r = _float_array(J), _float_array(r)
     if J.ndim != 2:
         raise ValueError(f"J must have shape (N, D), got {J.shape}")

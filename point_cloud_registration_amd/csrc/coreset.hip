@@ -31,8 +31,10 @@ static int gn_dim(int m) {
 // ---- create_gn_set (caratheodory.py:118-138) -------------------------------------------------------------------------
 // One lane = one row of (J, r).  Each product is rounded once in the type C++ gives it -- float x float in float,
 // anything with a double in double -- which is NumPy's promotion (einsum / J * r[:, None] / r ** 2 in the reference), and
-// the build has -ffp-contract=off, so the values are the reference's bit for bit.  P is (M, n) row-major: lane i writes
-// column i of every row, so each row is written coalesced.
+// the build has -ffp-contract=off, so the values are the reference's bit for bit.  The reference takes the J J products
+// with np.einsum, which adds each product to a zeroed output: a product of -0.0 is +0.0 there (J r and r^2 are plain
+// products and keep the sign), hence the `+ 0` on those rows alone.  P is (M, n) row-major: lane i writes column i of
+// every row, so each row is written coalesced.
 template <typename TJ, typename TR, int D>
 __global__ void __launch_bounds__(CS_BLOCK) k_gn_set(const TJ *__restrict__ J, const TR *__restrict__ r, int64_t n,
                                                      double *__restrict__ P) {
@@ -47,7 +49,7 @@ __global__ void __launch_bounds__(CS_BLOCK) k_gn_set(const TJ *__restrict__ J, c
 #pragma unroll
             for (int b = a; b < D; ++b) {                 // np.triu_indices(D) order
                 const TJ p = j[a] * j[b];
-                P[row++ * n + i] = (double)p;
+                P[row++ * n + i] = (double)(p + (TJ)0);      // -0.0 -> +0.0, nothing else changes
             }
 #pragma unroll
         for (int a = 0; a < D; ++a) {

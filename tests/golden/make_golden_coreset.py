@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/g14_coreset.npz by RUNNING the reference's ``caratheodory.py`` on the CPU.
+"""Generate tests/golden/g14_coreset.npz and g15_coreset_cases.npz by RUNNING the reference's ``caratheodory.py`` on the CPU.
 
 Run in the authoring container only (the reference lives at /root/reference and never travels to the GPU box):
 
@@ -20,15 +20,28 @@ Contents (int64 / float32 / float64 arrays only):
                              pl_count = correspondences, pl_rel_H = rel_H(H from the full set, g2's T_plane_H),
                              pl_rel_H_coreset = the same for H rebuilt from the coreset
   edge_size                  len(w) of the reference at N_target = M + 1 (seed 0, N = 3000, D = 6, k = 64)
+
+g15_coreset_cases.npz: the reference on every case of tests/coreset_cases.py (every D, uneven blocks, k above the level, the
+n_sub branch, weights over many decades, ill-scaled / zero / equal columns, repeated rows, planar scenes, float32 input), drawn
+there by the same ``default_rng`` calls the GPU test makes -- only seeds and figures are stored:
+  seed, N, M, k, target      the case (in the order of coreset_cases.CASES) and its sizes
+  row_rel                    the reference's per-row figure (coreset_cases.per_row_error: fsum, each row against its own magnitude)
+  size, wmin, wsum_rel       len(w), min w, |sum w - sum u| / sum u of the reference's coreset
+  sv{i}_P                    the reference's P on coreset_cases.special_values() (float32 products that overflow, underflow
+                             or are -0.0) cast to the i-th of coreset_cases.TYPE_PAIRS
 """
 
 import importlib.util
 import os
+import sys
+import warnings
 
 import numpy as np
 from scipy.spatial import cKDTree
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import coreset_cases as cc  # noqa: E402
 REFERENCE = "/root/reference/point_cloud_registration"
 
 
@@ -87,6 +100,34 @@ def plane_gn_set(g2):
     return J, r.astype(np.float64)
 
 
+def main_cases():
+    cols = {k: [] for k in ("seed", "N", "M", "k", "target", "row_rel", "size", "wmin", "wsum_rel")}
+    for fam, name, seed in cc.CASES:
+        J, r, u, k, nt = cc.build(name, seed)
+        P = np.ascontiguousarray(car.create_gn_set(J, r))
+        assert np.array_equal(P.view(np.uint64), cc.gn_set_numpy(J, r).view(np.uint64))
+        with warnings.catch_warnings(), np.errstate(divide="ignore", invalid="ignore"):
+            warnings.simplefilter("ignore", RuntimeWarning)      # (identical rows, exact planar normals: u / v with v == 0)
+            P_sel, w, idx = car.fast_caratheodory(P, u, k, nt)
+        rel, exact = cc.per_row_error(P, u, w, idx)
+        assert exact and np.all(np.diff(idx) > 0) and np.all(w > 0) and len(w) <= nt and np.array_equal(P_sel, P[:, idx])
+        wsum = abs(w.sum() - u.sum()) / u.sum()
+        for key, v in zip(cols, (seed, P.shape[1], P.shape[0], k, nt, rel, len(w), w.min(), wsum)):
+            cols[key].append(v)
+        print(f"{fam:15s} {name:16s} seed {seed}: N {P.shape[1]} M {P.shape[0]} k {k} N_target {nt}: size {len(w)} "
+              f"row_rel {rel:.2e} wsum {wsum:.1e} wmin {w.min():.3g}")
+    out = {key: np.array(v, dtype=np.float64 if key in ("row_rel", "wmin", "wsum_rel") else np.int64) for key, v in cols.items()}
+    J32, r32 = cc.special_values()
+    for i, (tj, tr) in enumerate(cc.TYPE_PAIRS):
+        with np.errstate(over="ignore", under="ignore"):
+            out[f"sv{i}_P"] = np.ascontiguousarray(car.create_gn_set(J32.astype(tj), r32.astype(tr)))
+        print(f"special values, J {np.dtype(tj)} r {np.dtype(tr)}: inf {int(np.isinf(out[f'sv{i}_P']).sum())}, "
+              f"-0.0 {int((np.signbit(out[f'sv{i}_P']) & (out[f'sv{i}_P'] == 0)).sum())}")
+    path = os.path.join(HERE, "g15_coreset_cases.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+
+
 def main():
     out = {}
     i = 0
@@ -139,3 +180,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+    main_cases()

@@ -915,14 +915,12 @@ def test_fuzz_knn(capi, orc, ctx, seed):
     assert np.array_equal(i, io)
 
 
-@pytest.mark.parametrize("case", ["lattice", "dense_spot", "duplicates", "sheet", "two_scales"])
-@pytest.mark.parametrize("k", [1, 15, 16, 17])
-def test_knn_constructed_cases(capi, orc, ctx, case, k):
-    """The k <= 16 search's branches on clouds built to take them (knn_normals.hip: knn_collect): exact ties by the
-    hundred (a lattice: order by original index), more points than the queue holds inside the first distance class
-    (a dense spot: handed to the list search), repeated points (distance 0 several times), a flat sheet, a cloud
-    with two densities (sparse part: no bound from the 27-cell block), queries outside the grid -- and the same
-    clouds through the k > 16 list.  Distances and indices bit-exact against brute force."""
+CONSTRUCTED_CLOUDS = ["lattice", "dense_spot", "duplicates", "sheet", "two_scales"]
+
+
+def constructed_cloud(case):
+    """-> (cloud, queries) of one constructed case (test_knn_constructed_cases; tests/test_gpu_knn_range.py).  Queries in
+    three groups: 300 points of the cloud, 150 next to it, 50 far outside the grid."""
     rng = np.random.default_rng(7)
     if case == "lattice":
         a = np.arange(12, dtype=np.float32) * np.float32(0.25)
@@ -940,6 +938,18 @@ def test_knn_constructed_cases(capi, orc, ctx, case, k):
     q = np.vstack([pts[rng.integers(0, len(pts), 300)],
                    (pts[rng.integers(0, len(pts), 150)].astype(np.float64) + rng.normal(0, 0.1, (150, 3))).astype(np.float32),
                    (rng.uniform(-1, 1, (50, 3)) * 300).astype(np.float32)])
+    return pts, q
+
+
+@pytest.mark.parametrize("case", CONSTRUCTED_CLOUDS)
+@pytest.mark.parametrize("k", [1, 15, 16, 17])
+def test_knn_constructed_cases(capi, orc, ctx, case, k):
+    """The k <= 16 search's branches on clouds built to take them (knn_normals.hip: knn_collect): exact ties by the
+    hundred (a lattice: order by original index), more points than the queue holds inside the first distance class
+    (a dense spot: handed to the list search), repeated points (distance 0 several times), a flat sheet, a cloud
+    with two densities (sparse part: no bound from the 27-cell block), queries outside the grid -- and the same
+    clouds through the k > 16 list.  Distances and indices bit-exact against brute force."""
+    pts, q = constructed_cloud(case)
     t = capi.Target.points(ctx, pts)
     d, i = t.knn_query(q, k)
     do, io = orc.knn_brute(pts, q, k)
