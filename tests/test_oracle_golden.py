@@ -345,3 +345,112 @@ def test_g9_quirk_q6_float64_target(g9):
     moved = np.linalg.norm((src @ T_fin[:3, :3].T + T_fin[:3, 3]) - (src @ g9["align_final"][:3, :3].T + g9["align_final"][:3, 3]), axis=1)
     dt, dr = _pose_err(T_fin, g9["align_final"])
     assert moved.max() < 1e-4 and dr < 1e-4, (moved.max(), dt, dr)
+
+
+# ----------------------------------------------------------------------------- g16: gates on the boundary, poses far from I
+@pytest.fixture(scope="module")
+def g16():
+    """The reference's four classes on the cases of tests/pass_cases.py (make_golden_pass_cases.py) + those cases, regenerated
+    and checksum-guarded."""
+    from conftest import load_golden
+    import pass_cases as pc
+    g = load_golden("g16_pass_cases.npz")
+    return g, pc.build_all(g)
+
+
+def _g16_lattice_targets(g, built):
+    """(case, kind, oracle target, probes, d, written-out counts) of every lattice form."""
+    import pass_cases as pc
+    lat, heavy, vox = built["pt"], built["heavy"], built["vox"]
+    o_pt = orc.TargetPoints(lat["target32"], normals=g["normals_pt"])
+    o_64 = orc.TargetPoints(lat["target64"], normals=g["normals_pt64"], tree_f64=True)
+    o_hv = orc.TargetPoints(heavy["target32"], normals=g["normals_heavy"])
+    o_vx = orc.TargetVoxels(vox["target64"], vox["voxel_size"])
+    return [("pt", "icp", o_pt, lat, pc.POINT_COUNTS_F32), ("pt", "plane", o_pt, lat, pc.POINT_COUNTS_F32),
+            ("pt64", "plane", o_64, lat, pc.POINT_COUNTS_F64),
+            ("heavy", "icp", o_hv, heavy, pc.POINT_COUNTS_F32), ("heavy", "plane", o_hv, heavy, pc.POINT_COUNTS_F32),
+            ("vox", "vplane", o_vx, vox, pc.VOXEL_COUNTS), ("vox", "ndt", o_vx, vox, pc.VOXEL_COUNTS)]
+
+
+def test_g16_lattice_gates(g16):
+    """Scan points ON the gate (icp.py:34, plane_icp.py:41, voxelized_plane_icp.py:38, ndt.py:33: strict), one ulp either side in
+    float32 and float64, gates whose float32 square underflows / overflows, at 9 exact poses up to |t| = 8192 m: the oracle's
+    count is the count written out in tests/pass_cases.py (= the rule: float32 distance against (float)max_dist for a float32
+    tree, float64 against max_dist for centroids and for PlaneICP's float64 tree, quirk Q6), the reference's ICP count
+    (H[0, 0]) is the same number, and H is the reference's: within 1e-9 for PlaneICP, VPlaneICP and NDT, within the error bound
+    of a float32 sum of 280 terms for ICP (pass_cases.F32_SUM_BOUND); zero sums where nothing is kept."""
+    import pass_cases as pc
+    g, built = g16
+    worst = {}
+    for case, kind, ot, lat, table in _g16_lattice_targets(g, built):
+        gs = pc.gates(lat["d"])
+        f32 = case != "pt64" and kind in ("icp", "plane")
+        assert table == [pc.rule_count(lat["classes"], md, f32) for md in gs], (case, kind)
+        assert sum(n for _, n in lat["classes"]) == lat["probes"].shape[0] == table[-1]
+        for pi, (T, scan) in enumerate(pc.exact_poses(lat["probes"])):
+            assert np.array_equal(T, g["lat_T"][pi])
+            for gi, md in enumerate(gs):
+                H, gr, e2, cnt = orc.calc_H_g_e2(KINDS[kind], ot, T, scan, md, with_count=True)
+                Href = g[f"lat_{case}_{kind}_H"][pi, gi]
+                what = (case, kind, pi, md)
+                assert cnt == table[gi], (what, cnt, table[gi])
+                if kind == "icp":
+                    assert Href[0, 0] == table[gi], what
+                if cnt == 0:
+                    assert not H.any() and not gr.any() and e2 == 0 and not Href.any(), what
+                else:
+                    # every figure is exact on a lattice but the normals: 1e-9, the bar the generator checked before it wrote
+                    # the fixture -- except ICP, whose reference sums its moments in float32 (icp.py:42-46, quirk Q5)
+                    bar = pc.F32_SUM_BOUND if kind == "icp" else 1e-9
+                    assert rel_H(H, Href) <= bar, (what, rel_H(H, Href), bar)
+                    worst[kind] = max(worst.get(kind, 0.0), rel_H(H, Href))
+    # Q6 distinguishes: one float64 ulp above 1.25 keeps every probe under the float64 tree, none of the 200 under a float32 one
+    assert pc.POINT_COUNTS_F64[3] == 280 and pc.POINT_COUNTS_F32[3] == 80
+    print("g16 lattices: worst rel_H oracle vs reference", worst)
+
+
+def test_g16_general_poses(g16):
+    """Sensor-frame scans at start poses with large rotations (two random ones, one by pi - 1e-4) and |t| in (0, 50, 1e4) m: the
+    oracle against the reference's four classes -- rel_H < 1e-5, e2 within 5e-5, the Gauss-Newton step within 5e-5."""
+    import pass_cases as pc
+    g, built = g16
+    md, vs = pc.GENERAL_MAX_DIST, pc.GENERAL_VOXEL
+    worst = {}
+    for norm, target in built["gen_targets"].items():
+        o_pts = orc.TargetPoints(target, normals=g[f"normals_t{norm:g}"])
+        o_vox = orc.TargetVoxels(target, vs)
+        for ci, (name, nrm, T, scan) in enumerate(built["gen"]):
+            if nrm != norm:
+                continue
+            for kind in pc.KINDS:
+                H, gr, e2, cnt = orc.calc_H_g_e2(KINDS[kind], o_pts if kind in ("icp", "plane") else o_vox, T, scan, md, with_count=True)
+                Href, gref, e2ref = g[f"gen_{kind}_H"][ci], g[f"gen_{kind}_g"][ci], float(g[f"gen_{kind}_e2"][ci])
+                fig = (rel_H(H, Href), abs(e2 - e2ref) / abs(e2ref), step_err(H, gr, Href, gref))
+                assert 0 < cnt < scan.shape[0], (name, kind, cnt)          # the gate bites, and not everything goes
+                assert fig[0] < TOL_H and fig[1] <= 5 * TOL_H and fig[2] <= 5e-5, (name, kind, fig)
+                worst[kind] = tuple(max(a, b) for a, b in zip(worst.get(kind, (0, 0, 0)), fig))
+    print("g16 general poses, worst (rel_H, e2 rel, step_err) oracle vs reference:", worst)
+
+
+def test_g16_regenerates(g16, tmp_path):
+    """tests/golden/make_golden_pass_cases.py reproduces the committed fixture array for array, bit for bit.  Skipped only where
+    the reference or scipy (its KD-tree stand-in) is not at hand; anything else that stops the generator fails the test."""
+    import importlib.util
+    import re
+    import subprocess
+    import sys
+    gen = os.path.join(REPO, "tests", "golden", "make_golden_pass_cases.py")
+    with open(os.path.join(REPO, "tests", "golden", "make_golden.py")) as f:       # (where the generators look for the reference)
+        where = re.search(r'^REFERENCE = "([^"]+)"', f.read(), re.M).group(1)
+    if not os.path.isdir(os.path.join(where, "point_cloud_registration")):
+        pytest.skip("the reference is not at hand: the generator cannot run")
+    if importlib.util.find_spec("scipy") is None:
+        pytest.skip("scipy is not at hand: the generator cannot run")
+    out = tmp_path / "g16.npz"
+    r = subprocess.run([sys.executable, gen, str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-800:] + r.stderr[-800:]
+    new = dict(np.load(out, allow_pickle=False))
+    g = g16[0]
+    assert sorted(new) == sorted(g)
+    for key in g:
+        assert new[key].dtype == g[key].dtype and new[key].shape == g[key].shape and new[key].tobytes() == g[key].tobytes(), key
