@@ -67,9 +67,11 @@ enum {
                                      communicator is attached to the context (the collective is a per-call decision) */
     PCR_FLAG_HOST_LOOP = 8u,      /* pcr_align: host-driven loop (one pcr_linearize + host solve per iteration)
                                      instead of the device-resident one; same arithmetic, same bits */
-    PCR_FLAG_DEVICE_LOOP = 16u    /* pcr_align: device-resident loop even where the library would pick the host-driven
+    PCR_FLAG_DEVICE_LOOP = 16u,   /* pcr_align: device-resident loop even where the library would pick the host-driven
                                      one (small scans on one GPU, where it is ~8 % faster: 37.6 vs 41.0 us per iteration
                                      on a 100 k-point scan) */
+    PCR_FLAG_KEEP_ORDER = 32u     /* pcr_scan_create: a Morton-sorted scan remembers the caller's point order (4 bytes per
+                                     point), which pcr_linearize_rows / _weighted / pcr_scan_coreset need */
 };
 
 typedef struct pcr_context pcr_context;
@@ -264,6 +266,35 @@ PCR_API pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int64_t
  * is exact for these sums (anything farther is gated out anyway).                          */
 PCR_API pcr_status pcr_linearize(pcr_target *t, pcr_scan *s, int kind, const double T[16],
                                  double max_dist, unsigned flags, double out[29]);
+
+/* ---- per-correspondence rows, weighted sums, scan coresets ---------------------------------
+ * What pcr_linearize accumulates, written out per scan point IN THE CALLER'S ORDER.  The scan must know that order: created
+ * with PCR_FLAG_KEEP_ORDER (Morton-sorted, 4 more bytes per point) or with PCR_FLAG_NO_SCAN_SORT; any other scan gives
+ * PCR_ERR_INVALID.  Each call runs an ordinary full search into a match buffer of its own at pose T and the same transform and
+ * gate as pcr_linearize, so a point is in or out exactly as there; the scan's reuse state is left alone (a following
+ * pcr_linearize / pcr_align returns the bits it would have returned without the call).  n = points of the scan,
+ * m = 1 (PCR_PLANE, PCR_VPLANE) or 3 (PCR_ICP, PCR_NDT).
+ * pcr_linearize_rows: J (n, m, 6), r (n, m), w (n) = 1 where the point is gated in, else 0 with zero rows;
+ *   PLANE / VPLANE: J = [n, p x (R^T n)], r = n . (R p + t - q); ICP / NDT: J = [I, -R skew(p)], r = R p + t - q;
+ *   W_or_null (NDT: n x 9) = the matched voxel's inverse covariance, symmetric; idx_or_null (n) = the matched target point
+ *   (the caller's index) or voxel (its position in pcr_target_voxels_get's order), -1 where gated out.
+ * pcr_linearize_weighted: out[0..27] = sum_i weights[i] x (the 28 sums' terms of point i: triu(H) 21, g 6, e2) over the gated-in
+ *   points, out[28] = sum of their weights; weights (n, caller order) finite and >= 0.  ICP terms come from J = [I, -R skew(p)],
+ *   g[3:] = p x (R r) under PCR_FLAG_ICP_RR_QUIRK, p x (R^T r) without.  Fixed summation order: bit-reproducible.
+ * pcr_scan_coreset: fast_caratheodory (pcr_coreset) over those terms with unit weights, the terms never leaving HBM: at most
+ *   n_target gated-in points (idx_out: ascending caller indices) with weights w_out > 0 whose weighted sums equal the full
+ *   ones up to rounding; *n_out of them.  At most n_target gated-in points: all of them, weight 1.  k > 29, n_target >= 29.
+ * Device memory: pcr_linearize_weighted and pcr_scan_coreset hold the terms as 28 x n doubles whatever the gated-in count --
+ *   224 bytes per SCAN point plus ~50 of bookkeeping (237 MB at 1.06 M points, 2.2 GB at 10 M) -- and pcr_linearize_rows a device
+ *   copy of its outputs; all of it is taken for the length of the call and kept in the context's block cache afterwards.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group); PCR_PLANE over a target
+ * with float64 coordinates (quirk Q6).                                                                                   */
+PCR_API pcr_status pcr_linearize_rows(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                      double *J, double *r, double *w, double *W_or_null, int64_t *idx_or_null);
+PCR_API pcr_status pcr_linearize_weighted(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                          const double *weights, double out[29]);
+PCR_API pcr_status pcr_scan_coreset(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                    int k, int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out);
 
 /* Registration.align (registration.py:71-113) run entirely behind the boundary: up to
  * max_iter x { pcr_linearize, dx = -solve(H, g), stop if |dx| < tol (before the update,

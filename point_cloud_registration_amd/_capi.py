@@ -26,6 +26,7 @@ FLAG_NO_SCAN_SORT = 2
 FLAG_LOCAL_ONLY = 4          # no all-reduce even when the context has a communicator
 FLAG_HOST_LOOP = 8           # pcr_align: host-driven loop instead of the device-resident one
 FLAG_DEVICE_LOOP = 16        # pcr_align: device-resident loop even for small scans (where the host-driven one is picked)
+FLAG_KEEP_ORDER = 32         # pcr_scan_create: a sorted scan remembers the caller's point order (rows, weighted sums, coresets)
 K_LINEARIZE, K_FINALIZE, K_NN, K_REDUCE, K_ALLREDUCE, K_CERTIFY, K_COUNT = 0, 1, 2, 3, 4, 5, 6
 KERNEL_NAMES = ("linearize", "finalize", "nn", "reduce", "allreduce", "certify")
 NN_FULL, NN_TRACK, NN_LIST = 0, 1, 2      # what the search of a pass did (certified reuse, include/pcr.h)
@@ -109,6 +110,11 @@ PROTOTYPES = {
     "pcr_gn_set": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_int, _f64p]),
     "pcr_coreset": (C.c_int, [_vp, _f64p, C.c_int, C.c_int64, _f64p, C.c_int, C.c_int64, C.POINTER(C.c_int64), _f64p, _i64p,
                               _f64p]),
+    # per-correspondence rows, weighted sums, scan coresets (include/pcr.h)
+    "pcr_linearize_rows": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "pcr_linearize_weighted": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, _f64p, _f64p]),
+    "pcr_scan_coreset": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, C.c_int, C.c_int64, _i64p, _f64p,
+                                   C.POINTER(C.c_int64)]),
     # batches: many scans / start poses against one target in one launch (include/pcr.h)
     "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
     "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -596,6 +602,7 @@ class Scan:
     def __init__(self, ctx, xyz=None, flags=0, device_ptr=None, n=None):
         self.ctx = ctx
         self.ghandle = None
+        self.flags = int(flags)
         h = _vp()
         if isinstance(ctx, Group):
             # a group scan: cut into one contiguous shard per member inside pcr_group_scan_create
@@ -783,6 +790,37 @@ def hash64(arr):
     h = C.c_uint64(0)
     check(lib().pcr_hash64(arr.ctypes.data_as(_vp), arr.nbytes, C.byref(h)))
     return h.value
+
+
+def linearize_rows(target, scan, kind, T, max_dist, flags=FLAG_ICP_RR_QUIRK, want_index=False):
+    """pcr_linearize_rows -> (J (n, m, 6), r (n, m), w (n), W (n, 3, 3) or None, idx (n) or None), caller order."""
+    n, m = scan.n, (1 if kind in (PLANE, VPLANE) else 3)
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    J, r, w = np.zeros((n, m, 6)), np.zeros((n, m)), np.zeros(n)
+    W = np.zeros((n, 3, 3)) if kind == NDT else None
+    idx = np.full(n, -1, np.int64) if want_index else None
+    check(lib().pcr_linearize_rows(target.handle, scan.handle, int(kind), T, float(max_dist), int(flags), _ptr(J), _ptr(r), _ptr(w),
+                                   _ptr(W) if W is not None else None, _ptr(idx) if idx is not None else None))
+    return J, r, w, W, idx
+
+
+def linearize_weighted(target, scan, kind, T, max_dist, weights, flags=FLAG_ICP_RR_QUIRK):
+    """pcr_linearize_weighted -> the 28 weighted sums and the sum of the gated-in weights (see include/pcr.h)."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty(29)
+    check(lib().pcr_linearize_weighted(target.handle, scan.handle, int(kind), T, float(max_dist), int(flags),
+                                       np.ascontiguousarray(weights, dtype=np.float64), out))
+    return out
+
+
+def scan_coreset(target, scan, kind, T, max_dist, k, n_target, flags=FLAG_ICP_RR_QUIRK):
+    """pcr_scan_coreset -> (idx (n_out) ascending caller indices, w (n_out))."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    cap = max(min(int(n_target), scan.n), 1)
+    idx, w, n_out = np.empty(cap, np.int64), np.empty(cap), C.c_int64(0)
+    check(lib().pcr_scan_coreset(target.handle, scan.handle, int(kind), T, float(max_dist), int(flags), int(k), int(n_target), idx, w,
+                                 C.byref(n_out)))
+    return idx[:n_out.value].copy(), w[:n_out.value].copy()
 
 
 _linearize_fast = None

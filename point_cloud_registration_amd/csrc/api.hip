@@ -735,6 +735,41 @@ extern "C" pcr_status pcr_linearize(pcr_target *t, pcr_scan *s, int kind, const 
     return pcr_run_linearize(t, s, kind, T, max_dist, flags, out);
 }
 
+// ---- per-correspondence rows, weighted sums and scan coresets (pass.hip: pcr_run_rows / pcr_run_terms) ----
+extern "C" pcr_status pcr_linearize_rows(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                         double *J, double *r, double *w, double *W_or_null, int64_t *idx_or_null) {
+    PCR_REQUIRE(t && s && T, "NULL argument");
+    PCR_REQUIRE(s->n == 0 || (J && r && w), "NULL output");
+    CtxScope scope(t->ctx);
+    return pcr_run_rows(t, s, kind, T, max_dist, flags, J, r, w, W_or_null, idx_or_null);
+}
+
+extern "C" pcr_status pcr_linearize_weighted(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                             const double *weights, double out[29]) {
+    PCR_REQUIRE(t && s && T && out && (weights || s->n == 0), "NULL argument");
+    for (int64_t i = 0; i < s->n; ++i)
+        PCR_REQUIRE(isfinite(weights[i]) && weights[i] >= 0.0, "weights must be finite and non-negative");
+    CtxScope scope(t->ctx);
+    DevBuf<double> P;
+    DevBuf<int64_t> col_idx;
+    int64_t stride = 0, n_in = 0;
+    PCR_TRY(pcr_run_terms(t, s, kind, T, max_dist, flags, &P, &stride, &col_idx, &n_in));
+    return pcr_terms_weighted_sum(t->ctx, P.p, stride, col_idx.p, n_in, weights, s->n, out);
+}
+
+extern "C" pcr_status pcr_scan_coreset(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                       int k, int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out) {
+    PCR_REQUIRE(t && s && T && idx_out && w_out && n_out, "NULL argument");
+    PCR_REQUIRE(k > 29, "k must exceed 29 (the 28 sums + 1)");
+    PCR_REQUIRE(n_target >= 29, "n_target must be at least 29");
+    CtxScope scope(t->ctx);
+    DevBuf<double> P;
+    DevBuf<int64_t> col_idx;
+    int64_t stride = 0, n_in = 0;
+    PCR_TRY(pcr_run_terms(t, s, kind, T, max_dist, flags, &P, &stride, &col_idx, &n_in));
+    return pcr_terms_coreset(t->ctx, P.p, stride, col_idx.p, n_in, k, n_target, idx_out, w_out, n_out);
+}
+
 // ---- Gauss-Newton driver behind the boundary (registration.py:71-113) -------------------------
 // Default: the device-resident loop (pass.hip: pcr_run_align).  PCR_FLAG_HOST_LOOP keeps the
 // host-driven form (one pcr_linearize + host solve per iteration), the same arithmetic from gn_math.h.

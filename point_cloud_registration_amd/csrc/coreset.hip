@@ -314,46 +314,39 @@ extern "C" pcr_status pcr_gn_set(pcr_context *ctx, const void *J, int J_is_f64, 
     return PCR_OK;
 }
 
+// out[q] = map[idx[q]]
+__global__ void __launch_bounds__(CS_BLOCK) k_take_i64(const int64_t *__restrict__ map, const int64_t *__restrict__ idx, int64_t n_out,
+                                                       int64_t *__restrict__ out) {
+    for (int64_t q = (int64_t)blockIdx.x * CS_BLOCK + threadIdx.x; q < n_out; q += (int64_t)gridDim.x * CS_BLOCK)
+        out[q] = idx ? map[idx[q]] : map[q];
+}
+
+// u[q] = weights[map[q]] (fill: u[q] = value)
+__global__ void __launch_bounds__(CS_BLOCK) k_gather_f64(const double *__restrict__ weights, const int64_t *__restrict__ map, int64_t n,
+                                                         double value, double *__restrict__ u) {
+    for (int64_t q = (int64_t)blockIdx.x * CS_BLOCK + threadIdx.x; q < n; q += (int64_t)gridDim.x * CS_BLOCK)
+        u[q] = weights ? weights[map[q]] : value;
+}
+
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int64_t n, const double *u, int k, int64_t n_target,
-                                  int64_t *n_out, double *w_out, int64_t *idx_out, double *P_sel_out) {
-    PCR_REQUIRE(ctx && n_out && n >= 0 && (n == 0 || (P && u)), "NULL argument or negative n");
-    const int d = gn_dim(m);
-    PCR_REQUIRE(d > 0, "m must be D (D + 1) / 2 + D + 1 for some D in [1, 12]");
-    PCR_REQUIRE(k > m + 1, "k must exceed m + 1");
-    PCR_REQUIRE(n_target >= m + 1, "n_target must be at least m + 1");
-    PCR_REQUIRE(w_out && idx_out && P_sel_out, "NULL output");
-    for (int64_t i = 0; i < n; ++i)
-        PCR_REQUIRE(isfinite(u[i]) && u[i] > 0.0, "u must be finite and positive");
-    if (n <= n_target) {                                   // caratheodory.py:67-69
-        for (int64_t i = 0; i < n; ++i) { w_out[i] = u[i]; idx_out[i] = i; }
-        std::copy(P, P + (size_t)m * n, P_sel_out);
-        *n_out = n;
-        return PCR_OK;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    static const bool stats = getenv("PCR_CORESET_STATS") && atoi(getenv("PCR_CORESET_STATS"));
-    const auto t_all = std::chrono::steady_clock::now();
-    double ms_up = 0, ms_elim = 0, ms_down = 0;
+// The levels of fast_caratheodory over a DEVICE-RESIDENT set: columns 0 .. n-1 of d_P (m rows, `stride` doubles apart) with
+// weights d_u0, n > n_target.  Shared by pcr_coreset (P uploaded by the caller) and pcr_scan_coreset (P written by the terms
+// kernel).  d_col_map (or NULL): idx_out names the selected columns through it; P_sel_out may be NULL.
+static pcr_status coreset_core(pcr_context *ctx, int d, int m, const double *d_P, int64_t stride, int64_t n, const double *d_u0, int k,
+                               int64_t n_target, const int64_t *d_col_map, int64_t *n_out, double *w_out, int64_t *idx_out,
+                               double *P_sel_out, double *ms_elim, double *ms_down, int *levels) {
     const int m1 = m + 1;
-    DevBuf<double> d_P, d_u0, d_u[2], d_part, d_sums, d_sel;
-    DevBuf<int64_t> d_idx[2], d_bounds;
+    DevBuf<double> d_u[2], d_part, d_sums, d_sel;
+    DevBuf<int64_t> d_idx[2], d_bounds, d_named;
     DevBuf<CsSeg> d_segs;
-    HIP_TRY(d_P.alloc((size_t)m * n));
-    HIP_TRY(d_u0.alloc(n));
     auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(d_P.p, P, 8 * (size_t)m * n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_u0.p, u, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (stats) { HIP_TRY(hipStreamSynchronize(ctx->stream)); ms_up = ms_since(t0); }
-
     const int64_t *idx_cur = nullptr;                     // level 0: member q is column q
-    const double *u_cur = d_u0.p;
+    const double *u_cur = d_u0;
     int64_t cur = n;
-    int ping = 0, levels = 0;
+    int ping = 0;
     std::vector<int64_t> bounds;
     std::vector<double> sums, Ps, u_sub, w_sub;
     std::vector<int> alive;
@@ -374,7 +367,7 @@ extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int6
         HIP_TRY(d_part.alloc((size_t)kk * bpc * m1));
         HIP_TRY(d_sums.alloc((size_t)kk * m1));
         HIP_TRY(hipMemcpyAsync(d_bounds.p, bounds.data(), 8 * (size_t)(kk + 1), hipMemcpyHostToDevice, ctx->stream));
-        PCR_TRY(chunk_sums(ctx, d, d_P.p, n, idx_cur, u_cur, d_bounds.p, kk, bpc, d_part.p));
+        PCR_TRY(chunk_sums(ctx, d, d_P, stride, idx_cur, u_cur, d_bounds.p, kk, bpc, d_part.p));
         hipLaunchKernelGGL(k_chunk_fold, dim3((unsigned)(((int64_t)kk * m1 + CS_BLOCK - 1) / CS_BLOCK)), dim3(CS_BLOCK), 0, ctx->stream,
                            (const double *)d_part.p, kk, bpc, m1, d_sums.p);
         HIP_TRY(hipGetLastError());
@@ -382,8 +375,8 @@ extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int6
         t0 = std::chrono::steady_clock::now();
         HIP_TRY(hipMemcpyAsync(sums.data(), d_sums.p, 8 * sums.size(), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ms_down += ms_since(t0);
-        if (levels == 0) {
+        *ms_down += ms_since(t0);
+        if (*levels == 0) {
             // every column of P is in some chunk and u > 0: a non-finite entry of P makes its chunk's sums non-finite
             for (double s : sums)
                 if (!isfinite(s)) {
@@ -410,7 +403,7 @@ extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int6
             segs[s] = {bounds[c], dst, w_sub[s] / u_sub[c]};
             dst += bounds[c + 1] - bounds[c];
         }
-        ms_elim += ms_since(t0);
+        *ms_elim += ms_since(t0);
         HIP_TRY(d_segs.alloc(segs.size()));
         if (!d_idx[ping].p) HIP_TRY(d_idx[ping].alloc(dst));
         if (!d_u[ping].p) HIP_TRY(d_u[ping].alloc(dst));
@@ -423,23 +416,118 @@ extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int6
         u_cur = d_u[ping].p;
         ping ^= 1;
         cur = dst;
-        ++levels;
+        ++*levels;
     }
-    // P_sel = P[:, idx]
-    HIP_TRY(d_sel.alloc((size_t)m * cur));
     const dim3 tgrid((unsigned)std::min<int64_t>((cur + CS_BLOCK - 1) / CS_BLOCK, (int64_t)ctx->num_cu * 8));
-    hipLaunchKernelGGL(k_take_columns, tgrid, dim3(CS_BLOCK), 0, ctx->stream, (const double *)d_P.p, n, m, idx_cur, cur, d_sel.p);
-    HIP_TRY(hipGetLastError());
+    if (P_sel_out) {                                       // P_sel = P[:, idx]
+        HIP_TRY(d_sel.alloc((size_t)m * cur));
+        hipLaunchKernelGGL(k_take_columns, tgrid, dim3(CS_BLOCK), 0, ctx->stream, d_P, stride, m, idx_cur, cur, d_sel.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_col_map) {                                       // columns -> what the caller calls them (ascending, like the columns)
+        HIP_TRY(d_named.alloc((size_t)cur));
+        hipLaunchKernelGGL(k_take_i64, tgrid, dim3(CS_BLOCK), 0, ctx->stream, d_col_map, idx_cur, cur, d_named.p);
+        HIP_TRY(hipGetLastError());
+    }
     t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(P_sel_out, d_sel.p, 8 * (size_t)m * cur, hipMemcpyDeviceToHost, ctx->stream));
+    if (P_sel_out) HIP_TRY(hipMemcpyAsync(P_sel_out, d_sel.p, 8 * (size_t)m * cur, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(w_out, u_cur, 8 * (size_t)cur, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(idx_out, idx_cur, 8 * (size_t)cur, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(idx_out, d_col_map ? (const int64_t *)d_named.p : idx_cur, 8 * (size_t)cur, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ms_down += ms_since(t0);
+    *ms_down += ms_since(t0);
     *n_out = cur;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int64_t n, const double *u, int k, int64_t n_target,
+                                  int64_t *n_out, double *w_out, int64_t *idx_out, double *P_sel_out) {
+    PCR_REQUIRE(ctx && n_out && n >= 0 && (n == 0 || (P && u)), "NULL argument or negative n");
+    const int d = gn_dim(m);
+    PCR_REQUIRE(d > 0, "m must be D (D + 1) / 2 + D + 1 for some D in [1, 12]");
+    PCR_REQUIRE(k > m + 1, "k must exceed m + 1");
+    PCR_REQUIRE(n_target >= m + 1, "n_target must be at least m + 1");
+    PCR_REQUIRE(w_out && idx_out && P_sel_out, "NULL output");
+    for (int64_t i = 0; i < n; ++i)
+        PCR_REQUIRE(isfinite(u[i]) && u[i] > 0.0, "u must be finite and positive");
+    if (n <= n_target) {                                   // caratheodory.py:67-69
+        for (int64_t i = 0; i < n; ++i) { w_out[i] = u[i]; idx_out[i] = i; }
+        std::copy(P, P + (size_t)m * n, P_sel_out);
+        *n_out = n;
+        return PCR_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    static const bool stats = getenv("PCR_CORESET_STATS") && atoi(getenv("PCR_CORESET_STATS"));
+    const auto t_all = std::chrono::steady_clock::now();
+    double ms_up = 0, ms_elim = 0, ms_down = 0;
+    int levels = 0;
+    DevBuf<double> d_P, d_u0;
+    HIP_TRY(d_P.alloc((size_t)m * n));
+    HIP_TRY(d_u0.alloc(n));
+    auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpyAsync(d_P.p, P, 8 * (size_t)m * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_u0.p, u, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (stats) { HIP_TRY(hipStreamSynchronize(ctx->stream)); ms_up = ms_since(t0); }
+    PCR_TRY(coreset_core(ctx, d, m, d_P.p, n, n, d_u0.p, k, n_target, nullptr, n_out, w_out, idx_out, P_sel_out, &ms_elim, &ms_down,
+                         &levels));
     if (stats)
         fprintf(stderr, "pcr_coreset: n %lld m %d levels %d -> %lld points; total %.3f ms: upload %.3f, host elimination %.3f, "
                         "read-backs (incl. waiting for the kernels before them) %.3f\n",
-                (long long)n, m, levels, (long long)cur, ms_since(t_all), ms_up, ms_elim, ms_down);
+                (long long)n, m, levels, (long long)*n_out, ms_since(t_all), ms_up, ms_elim, ms_down);
+    return PCR_OK;
+}
+
+// ---- the scan routes: the terms kernel's columns never leave HBM ---------------------------------------------------------
+// sum_c weights[col_idx[c]] P[:, c] and the sum of those weights: k_chunk_sums with ONE chunk (fixed order, no float atomics)
+pcr_status pcr_terms_weighted_sum(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in,
+                                  const double *weights, int64_t n, double out[29]) {
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    if (n_in == 0) return PCR_OK;
+    DevBuf<double> d_w, d_u, d_part, d_sums;
+    DevBuf<int64_t> d_bounds;
+    HIP_TRY(d_w.alloc((size_t)n)); HIP_TRY(d_u.alloc((size_t)n_in));
+    HIP_TRY(hipMemcpyAsync(d_w.p, weights, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grid((unsigned)std::min<int64_t>((n_in + CS_BLOCK - 1) / CS_BLOCK, (int64_t)ctx->num_cu * 8));
+    hipLaunchKernelGGL(k_gather_f64, grid, dim3(CS_BLOCK), 0, ctx->stream, (const double *)d_w.p, d_col_idx, n_in, 0.0, d_u.p);
+    HIP_TRY(hipGetLastError());
+    const int64_t bounds[2] = {0, n_in};
+    const int bpc = (int)std::max<int64_t>(1, std::min<int64_t>(4 * (int64_t)ctx->num_cu, (n_in + 1023) / 1024));
+    HIP_TRY(d_bounds.alloc(2)); HIP_TRY(d_part.alloc((size_t)bpc * 29)); HIP_TRY(d_sums.alloc(29));
+    HIP_TRY(hipMemcpyAsync(d_bounds.p, bounds, sizeof bounds, hipMemcpyHostToDevice, ctx->stream));
+    PCR_TRY(chunk_sums(ctx, 6, d_P, stride, nullptr, d_u.p, d_bounds.p, 1, bpc, d_part.p));
+    hipLaunchKernelGGL(k_chunk_fold, dim3(1), dim3(CS_BLOCK), 0, ctx->stream, (const double *)d_part.p, 1, bpc, 29, d_sums.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_sums.p, 8 * 29, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+pcr_status pcr_terms_coreset(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in, int k,
+                             int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out) {
+    static const bool stats = getenv("PCR_CORESET_STATS") && atoi(getenv("PCR_CORESET_STATS"));
+    const auto t_all = std::chrono::steady_clock::now();
+    double ms_elim = 0, ms_down = 0;
+    int levels = 0;
+    if (n_in <= n_target) {                                // every gated-in point, weight 1
+        if (n_in > 0) {
+            HIP_TRY(hipMemcpyAsync(idx_out, d_col_idx, 8 * (size_t)n_in, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+        for (int64_t i = 0; i < n_in; ++i) w_out[i] = 1.0;
+        *n_out = n_in;
+    } else {
+        DevBuf<double> d_u0;
+        HIP_TRY(d_u0.alloc((size_t)n_in));
+        const dim3 grid((unsigned)std::min<int64_t>((n_in + CS_BLOCK - 1) / CS_BLOCK, (int64_t)ctx->num_cu * 8));
+        hipLaunchKernelGGL(k_gather_f64, grid, dim3(CS_BLOCK), 0, ctx->stream, (const double *)nullptr, (const int64_t *)nullptr, n_in, 1.0,
+                           d_u0.p);
+        HIP_TRY(hipGetLastError());
+        PCR_TRY(coreset_core(ctx, 6, 28, d_P, stride, n_in, d_u0.p, k, n_target, d_col_idx, n_out, w_out, idx_out, nullptr, &ms_elim,
+                             &ms_down, &levels));
+    }
+    if (stats)
+        fprintf(stderr, "pcr_scan_coreset: n %lld m 28 levels %d -> %lld points; after the terms kernel %.3f ms: upload 0.000, "
+                        "host elimination %.3f, read-backs (incl. waiting for the kernels before them) %.3f\n",
+                (long long)n_in, levels, (long long)*n_out, ms_since(t_all), ms_elim, ms_down);
     return PCR_OK;
 }

@@ -1183,10 +1183,15 @@ pcr_status pcr_sort_scan(pcr_context *ctx, const float *d_xyz, int64_t n, unsign
         const char *be = getenv("PCR_MORTON_BITS");
         if (be && atoi(be) >= 1 && atoi(be) <= 21) bits = atoi(be);
         HIP_TRY(k1.alloc(nn)); HIP_TRY(k2.alloc(nn));
-        HIP_TRY(i1.alloc(nn)); HIP_TRY(i2.alloc(nn));
+        HIP_TRY(i1.alloc(nn));
+        // PCR_FLAG_KEEP_ORDER: the sorted permutation lands in a block the scan keeps instead of a temporary
+        uint32_t *perm = nullptr;
+        if (flags & PCR_FLAG_KEEP_ORDER) { HIP_TRY(pcr_scan_alloc(s, (void **)&s->order, 4 * nn)); perm = s->order; }
+        else { HIP_TRY(i2.alloc(nn)); perm = i2.p; }
         hipLaunchKernelGGL(k_morton, dim3(nb), dim3(256), 0, ctx->stream, d_xyz, n, (const unsigned *)d_box.p, bits, k1.p, i1.p);
-        PCR_TRY(sort_pairs<unsigned long long>(ctx, k1, k2, i1, i2, n, 3 * bits));
-        hipLaunchKernelGGL(k_to_soa, dim3(nb), dim3(256), 0, ctx->stream, d_xyz, (const uint32_t *)i2.p, n, s->x, s->y, s->z);
+        PCR_TRY(sort_pairs<unsigned long long>(ctx, k1, k2, i1, perm, n, 3 * bits));
+        hipLaunchKernelGGL(k_to_soa, dim3(nb), dim3(256), 0, ctx->stream, d_xyz, (const uint32_t *)perm, n, s->x, s->y, s->z);
+        s->sorted = true;
     }
     HIP_TRY(hipGetLastError());
     unsigned hb[7];

@@ -77,7 +77,7 @@ bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s) {
 static void set_filter_bound(LinArgs &a, double bound);
 // (bits 27-29 of LinArgs::flags are internal -- the gate switch of quirk Q6, two developer timing switches; a
 // caller-supplied word must not reach them)
-#define PCR_PUBLIC_FLAGS (PCR_FLAG_ICP_RR_QUIRK | PCR_FLAG_NO_SCAN_SORT | PCR_FLAG_LOCAL_ONLY | PCR_FLAG_HOST_LOOP | PCR_FLAG_DEVICE_LOOP)
+#define PCR_PUBLIC_FLAGS (PCR_FLAG_ICP_RR_QUIRK | PCR_FLAG_NO_SCAN_SORT | PCR_FLAG_LOCAL_ONLY | PCR_FLAG_HOST_LOOP | PCR_FLAG_DEVICE_LOOP | PCR_FLAG_KEEP_ORDER)
 
 // ---- pass_setup, step by step (in the order they run) ----
 static pcr_status pass_validate(const pcr_target *t, const pcr_scan *s, int kind, double max_dist) {
@@ -814,6 +814,127 @@ pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int
         HIP_TRY(hipMemcpyAsync(trace_or_null, ws.p + off_trace, B * trace_rows * 45 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
+    return PCR_OK;
+}
+
+// ---- rows passes: the search half of a search + reduce pass, then k_rows where the reduce kernel would go (rows.hip) ----
+// The search is an ordinary FULL search (variant 1 whatever the scan size: the fused small-scan kernel keeps its matches in
+// registers) into a match buffer of THIS call, so the scan's own nn_j / lb2 / umask and its reuse state (track_valid,
+// pose_valid, nn_serial) stay exactly as the previous pass left them, and none of the target's lazily built structures is
+// built or counted here: a following pcr_linearize / pcr_align runs the kernels, and returns the bits, it would have without
+// the rows call.  Tiles are dealt block-locally (nn_tile_loop<1>): the global tile counters are re-armed by the reduce
+// kernel's fold, which does not run here.  Voxel targets are searched in float64 (no float32 filter, hence no pending
+// points): the filter is exact by construction, so the matches are the ones pcr_linearize finds.
+// NOT measured: the block-local deal at EVERY scan size.  pass_enqueue records it as the loser once a wave gets tens of
+// tiles (scans of ~10 M points and more); such a rows pass is correct but its search is slower than pcr_linearize's.
+static pcr_status rows_search(Pass *ps, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
+                              unsigned flags) {
+    PCR_TRY(pass_validate(t, s, kind, max_dist));
+    pcr_context *ctx = t->ctx;
+    if (ctx->comm != nullptr) {
+        pcr_set_error("rows passes are not available on a context with a communicator attached (pcr_comm_*, pcr_group)");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    if (kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr) {
+        pcr_set_error("PlaneICP rows are not available over a float64 point target (quirk Q6)");
+        return PCR_ERR_UNSUPPORTED;
+    }
+    PCR_REQUIRE(!s->sorted || s->order != nullptr, "a Morton-sorted scan needs PCR_FLAG_KEEP_ORDER (or PCR_FLAG_NO_SCAN_SORT) for rows in the caller's order");
+    HIP_TRY(hipSetDevice(ctx->device));
+    PCR_TRY(pcr_ensure_scratch(ctx, s->n));
+    memset(ps, 0, sizeof *ps);
+    ps->ctx = ctx; ps->t = t; ps->s = s; ps->kind = kind; ps->fused_fin = true; ps->motion = -1.0;
+    HIP_TRY(nn->alloc((size_t)(s->n > 0 ? s->n : 1)));
+    pass_fill_lin(ps, max_dist, flags & PCR_PUBLIC_FLAGS, false, false, 8);
+    LinArgs &a = ps->a;
+    a.nn_j = nn->p; a.lb2 = nullptr; a.umask = nullptr; a.ucnt = nullptr;
+    host_pose_k(T, &a.hp);
+    pass_set_mode(ps, PCR_NN_FULL);
+    a.sched_local = 1;
+    if (s->n == 0) return PCR_OK;
+    const bool vox = t->is_voxel != 0;
+    const bool lb = !vox && a.gf.lbox != nullptr;
+    const int64_t tiles = (a.n + 63) / 64, need = (tiles + 3) / 4;
+    int64_t nb = (int64_t)ctx->num_cu * (lb ? ctx->nn_blocks_lb : ctx->nn_blocks_per_cu[vox ? 1 : 0]);
+    const dim3 nn_grid((unsigned)grid8(nb < need ? nb : need));
+    RoctxRange range("pcr:rows_search");
+    if (!vox) launch_nn_scan(0, PCR_NN_FULL, t->cs_h != nullptr, 1, nn_grid, ctx->stream, a);
+    else if (t->gd.rowocc != nullptr && (ctx->vox_occ >= 0 ? ctx->vox_occ != 0 : a.md_d / t->gd.h + 2.0 >= 5.0))
+        launch_nn_scan(2, PCR_NN_FULL, false, 1, nn_grid, ctx->stream, a);
+    else launch_nn_scan(1, PCR_NN_FULL, false, 1, nn_grid, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return PCR_OK;
+}
+
+static dim3 rows_grid(const pcr_context *ctx, int64_t n) {
+    const int64_t want = (n + 255) / 256, cap = (int64_t)ctx->num_cu * 8;
+    return dim3((unsigned)(want < 1 ? 1 : (want < cap ? want : cap)));
+}
+
+pcr_status pcr_run_rows(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double *J,
+                        double *r, double *w, double *W_or_null, int64_t *idx_or_null) {
+    Pass ps;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(rows_search(&ps, &nn, t, s, kind, T, max_dist, flags));
+    pcr_context *ctx = ps.ctx;
+    const int64_t n = s->n;
+    if (n == 0) return PCR_OK;
+    const size_t m = (kind == PCR_PLANE || kind == PCR_VPLANE) ? 1 : 3;
+    const bool want_W = kind == PCR_NDT && W_or_null != nullptr;
+    DevBuf<double> d_J, d_r, d_w, d_W;
+    DevBuf<int64_t> d_idx;
+    HIP_TRY(d_J.alloc((size_t)n * m * 6)); HIP_TRY(d_r.alloc((size_t)n * m)); HIP_TRY(d_w.alloc((size_t)n));
+    if (want_W) HIP_TRY(d_W.alloc((size_t)n * 9));
+    if (idx_or_null) HIP_TRY(d_idx.alloc((size_t)n));
+    RowArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.order = s->order; ra.J = d_J.p; ra.r = d_r.p; ra.w = d_w.p; ra.W = d_W.p; ra.idx = d_idx.p;
+    {
+        RoctxRange range("pcr:rows");
+        launch_rows(kind, 0, rows_grid(ctx, n), ctx->stream, ps.a, ra);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(J, d_J.p, 8 * (size_t)n * m * 6, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(r, d_r.p, 8 * (size_t)n * m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(w, d_w.p, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (want_W) HIP_TRY(hipMemcpyAsync(W_or_null, d_W.p, 8 * (size_t)n * 9, hipMemcpyDeviceToHost, ctx->stream));
+    if (idx_or_null) HIP_TRY(hipMemcpyAsync(idx_or_null, d_idx.p, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+pcr_status pcr_run_terms(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                         DevBuf<double> *P, int64_t *stride, DevBuf<int64_t> *col_idx, int64_t *n_in) {
+    Pass ps;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(rows_search(&ps, &nn, t, s, kind, T, max_dist, flags));
+    pcr_context *ctx = ps.ctx;
+    const int64_t n = s->n;
+    *n_in = 0; *stride = n > 0 ? n : 1;
+    if (n == 0) return PCR_OK;
+    DevBuf<uint32_t> d_flag, d_off, d_inv;
+    HIP_TRY(d_flag.alloc((size_t)n + 1)); HIP_TRY(d_off.alloc((size_t)n + 1));
+    if (s->order) HIP_TRY(d_inv.alloc((size_t)n));
+    HIP_TRY(hipMemsetAsync(d_flag.p + n, 0, sizeof(uint32_t), ctx->stream));
+    RowArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ra.order = s->order; ra.flag = d_flag.p; ra.inv = d_inv.p;
+    RoctxRange range("pcr:terms");
+    launch_rows(kind, 2, rows_grid(ctx, n), ctx->stream, ps.a, ra);
+    HIP_TRY(hipGetLastError());
+    PCR_TRY(pcr_rows_offsets(ctx, d_flag.p, d_off.p, n + 1));
+    // the column stride is the scan size, so the terms kernel does not wait for the count to cross PCIe.  The price is memory:
+    // P is 28 x n doubles whatever the gated-in count (224 bytes per SCAN point: 237 MB at 1.06 M points, 2.2 GB at 10 M), and
+    // it, the flags, offsets, inverse permutation, column indices and the match buffer (another 24 bytes per point) are
+    // allocated by every call -- from the context's block cache after the first one (include/pcr.h says so to callers)
+    HIP_TRY(P->alloc((size_t)28 * (size_t)n)); HIP_TRY(col_idx->alloc((size_t)n));
+    ra.off = d_off.p; ra.P = P->p; ra.stride = n; ra.col_idx = col_idx->p;
+    launch_rows(kind, 1, rows_grid(ctx, n), ctx->stream, ps.a, ra);
+    HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_off.p + n, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n_in = (int64_t)total;
     return PCR_OK;
 }
 

@@ -71,6 +71,22 @@ struct LinArgs {
     const float4 *lbox_h2, *gbox_h2;     // leaf / group boxes of the deeper lists (heavy targets)
 };
 
+// what the rows kernels (rows.hip: k_rows<KIND, MODE>) read and write besides LinArgs; every array is in CALLER order
+struct RowArgs {
+    const uint32_t *order;   // scan device position -> caller index (pcr_scan::order); NULL: the scan is in caller order
+    // MODE 0 (rows): J [n][m][6], r [n][m], w [n], W [n][9] (NDT) or NULL, idx [n] or NULL
+    double *J, *r, *w, *W;
+    int64_t *idx;
+    // MODE 2 (flags) writes, MODE 1 (terms) reads: flag[c] = caller point c is gated in, inv[c] = its device position
+    // (NULL: caller order); off = exclusive sums of flag
+    uint32_t *flag, *inv;
+    const uint32_t *off;
+    // MODE 1 (terms): row-major P[28][stride], column off[c] = point c; col_idx[column] = c
+    double *P;
+    int64_t stride;
+    int64_t *col_idx;
+};
+
 // the geometry a point search of this launch reads: gf, with the deeper lists swapped in when the device-resident loop
 // asked for them (wave-uniform: a handful of scalar selects at kernel start)
 __device__ __forceinline__ Geom<float> select_lists(const LinArgs &a) {
@@ -1025,6 +1041,9 @@ void launch_batch_init(hipStream_t st, const BatchItem *items, unsigned n_items,
 void launch_publish(hipStream_t st, const double *out, double *host_out, volatile uint32_t *host_flag, uint32_t seq);
 void launch_nn_query(const pcr_target *t, int form, hipStream_t st, const float *q, int64_t m, double bound2, double rmax, void *dist,
                      int64_t *idx);
+// rows.hip
+void launch_rows(int kind, int mode, dim3 grid, hipStream_t st, const LinArgs &a, const RowArgs &ra);
+pcr_status pcr_rows_offsets(pcr_context *ctx, const uint32_t *flag, uint32_t *off, int64_t n_plus_1);
 enum { PCR_OCC_POINT, PCR_OCC_VOXEL, PCR_OCC_FILTER, PCR_OCC_POINT_LB, PCR_OCC_MFMA };
 int nn_blocks_per_cu(int which);
 

@@ -324,6 +324,8 @@ struct pcr_scan {
     pcr_context *ctx = nullptr;
     int64_t n = 0;
     float *x = nullptr, *y = nullptr, *z = nullptr;   // SoA, Morton-sorted unless PCR_FLAG_NO_SCAN_SORT
+    bool sorted = false;                              // the points were Morton-sorted: device order != caller order
+    uint32_t *order = nullptr;                        // PCR_FLAG_KEEP_ORDER on a sorted scan: device position -> caller index
     // matched cell-sorted index per scan point (PCR_NONE = gated out), written by k_nn_scan and read
     // by the reduce kernel; kept across passes: the previous match is an exact upper bound for the
     // next search against the SAME target (nn_serial)
@@ -396,6 +398,18 @@ pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int
                          double tol, double max_dist, unsigned flags, double *out29, double *T_out, int *iterations,
                          pcr_status *item_status, double *trace_or_null);
 pcr_status pcr_ensure_scratch(pcr_context *ctx, int64_t n_points);
+// rows passes (rows.hip kernels behind a full search into a match buffer of their own: the scan's reuse state is not touched).
+// pcr_run_rows: host arrays in caller order (W / idx may be NULL).  pcr_run_terms: the 28 terms of every gated-in point as
+// columns of the device-resident P[28][*stride] (ascending caller index; col_idx[column] = caller index), *n_in of them.
+pcr_status pcr_run_rows(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double *J,
+                        double *r, double *w, double *W_or_null, int64_t *idx_or_null);
+pcr_status pcr_run_terms(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                         DevBuf<double> *P, int64_t *stride, DevBuf<int64_t> *col_idx, int64_t *n_in);
+// ---- coreset.hip: what pcr_linearize_weighted / pcr_scan_coreset do with those columns
+pcr_status pcr_terms_weighted_sum(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in,
+                                  const double *weights, int64_t n, double out[29]);
+pcr_status pcr_terms_coreset(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in, int k,
+                             int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 
 // ---- roctx ranges around the hot-path launches (PCR_ROCTX=1; libroctx64 bound with dlopen, so the

@@ -122,24 +122,80 @@ class Registration:
         # registration.py:36-43: an unimplemented stub in the reference as well
         raise NotImplementedError("update_target is not implemented.")
 
-    def linearize(self, cur_T, source):
-        # registration.py:45-53: no subclass of the reference implements it either (dead path)
-        raise NotImplementedError("linearize is not implemented.")
+    def linearize(self, cur_T, source, return_index=False):
+        """Per-point Jacobians, residuals and weights at ``cur_T`` (registration.py:45-53, which no class of the reference
+        implements) -> ``(Js (N, m, 6), rs (N, m), ws)``, in the order of ``source``; m = 1 (PlaneICP, VPlaneICP) or 3 (ICP, NDT).
 
-    def calc_H_g_e2(self, cur_T, source):
-        """Hessian (6x6), gradient (6) and squared error at ``cur_T`` for ``source`` (N,3)."""
+        ``ws`` is (N,): 1.0 where the point has a correspondence inside ``max_dist``, else 0.0 with zero rows.  For NDT ``ws``
+        is (N, 3, 3) = mask x the matched voxel's inverse covariance, and the sums are
+        ``H = einsum("nij,nik,nkl->jl", Js, ws, Js)``, ``g = einsum("nij,nik,nk->j", Js, ws, rs)``,
+        ``e2 = einsum("ni,nij,nj->", rs, ws, rs)``.  For the other classes the reference's generic ``calc_H_g_e2``
+        (registration.py:62-67: ``H = sum w J^T J``, ``g = sum w J^T r``, ``e2 = sum w r^T r``) applied to the result reproduces
+        the class's own sums up to rounding -- except ICP under the default compat flag (quirk Q1), whose own ``g[3:]`` is
+        ``sum p x (R r)`` where the rows give ``sum p x (R^T r)``.
+        PlaneICP / VPlaneICP: ``J = [n, p x (R^T n)]``, ``r = n . (R p + t - q)``; ICP / NDT: ``J = [I, -R skew(p)]``,
+        ``r = R p + t - q``.  ``return_index=True`` appends ``idx`` (N,) int64: the matched target point / voxel (its position
+        in ``pcr_target_voxels_get``'s order), -1 where there is none."""
+        scan = self._rows_scan(source)
+        J, r, w, W, idx = _capi.linearize_rows(self._target, scan, self.KIND, np.asarray(cur_T, dtype=np.float64), self._max_dist(),
+                                               self._flags, want_index=return_index)
+        ws = w[:, None, None] * W if W is not None else w
+        return (J, r, ws, idx) if return_index else (J, r, ws)
+
+    def calc_H_g_e2(self, cur_T, source, weights=None):
+        """Hessian (6x6), gradient (6) and squared error at ``cur_T`` for ``source`` (N,3).  ``weights`` (N,), finite and
+        >= 0, in the order of ``source``: every point's terms are multiplied by its weight (a caller's own robust kernel is
+        ``linearize`` -> weights -> this); ``last_weight_sum`` then holds the sum of the gated-in weights."""
+        if weights is None:
+            if not self._is_target_set:
+                raise ValueError("Target is not set.")
+            scan = self._scan_for(source)
+            return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
+        n = source.shape[0] if isinstance(source, UploadedScan) else np.asarray(source).shape[0]
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (n,):
+            raise ValueError(f"weights must have shape ({n},)")
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("weights must be finite and >= 0")
+        scan = self._rows_scan(source)
+        out = _capi.linearize_weighted(self._target, scan, self.KIND, np.asarray(cur_T, dtype=np.float64), self._max_dist(), w, self._flags)
+        H, g, e2, _ = _capi.unpack29(out)
+        self.last_weight_sum = float(out[28])
+        return H, g, e2
+
+    def coreset(self, cur_T, source, N_target=1024, k=64):
+        """Exact downsampling of ``source`` at ``cur_T`` (K. Koide, arXiv 2307.02948; the reference's
+        fast_voxelized_plane_icp.py) -> ``(indices, weights)``: at most ``N_target`` of the points that have a correspondence,
+        ``indices`` ascending, ``weights > 0``, such that ``calc_H_g_e2(cur_T, source[indices], weights=weights)`` equals
+        ``calc_H_g_e2(cur_T, source)`` up to rounding.  The per-point terms are computed and reduced on the GPU; only the
+        selection crosses PCIe.  ``N_target >= 29`` and ``k > 29`` (28 sums + 1)."""
+        if int(N_target) < 29:
+            raise ValueError("N_target must be at least 29")
+        if int(k) <= 29:
+            raise ValueError("k must exceed 29")
+        scan = self._rows_scan(source)
+        return _capi.scan_coreset(self._target, scan, self.KIND, np.asarray(cur_T, dtype=np.float64), self._max_dist(), int(k),
+                                  int(N_target), self._flags)
+
+    def _rows_scan(self, source):
+        """The scan of ``linearize`` / weighted ``calc_H_g_e2`` / ``coreset``: uploaded with the caller's order kept."""
+        if self._comm is not None or self._group is not None:
+            raise ValueError("per-point rows, weights and coresets run on one GPU of one process: not with comm= or devices=")
         if not self._is_target_set:
             raise ValueError("Target is not set.")
-        scan = self._scan_for(source)
-        return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
+        if isinstance(source, UploadedScan) and not (source._scan.flags & (_capi.FLAG_KEEP_ORDER | _capi.FLAG_NO_SCAN_SORT)):
+            raise ValueError("this UploadedScan does not remember the caller's order: upload(source, keep_order=True)")
+        return self._scan_for(source, flags=_capi.FLAG_KEEP_ORDER)
 
-    def upload(self, source):
+    def upload(self, source, keep_order=False):
         """Upload (and Morton-sort) ``source`` once; the returned handle can stand in for the array in
-        ``calc_H_g_e2`` / ``align`` (the caller then owns the "has it changed?" question)."""
+        ``calc_H_g_e2`` / ``align`` (the caller then owns the "has it changed?" question).  ``keep_order=True``: the device
+        copy remembers the order of ``source`` (4 bytes per point), which ``linearize`` / ``coreset`` / weights need."""
         src = np.asarray(source)
         if src.ndim != 2 or src.shape[1] != 3:
             raise ValueError("source must have shape (N, 3)")
-        return UploadedScan(_capi.Scan(self._ctx(), src.astype(np.float32, copy=False)), src.shape)
+        flags = _capi.FLAG_KEEP_ORDER if keep_order else 0
+        return UploadedScan(_capi.Scan(self._ctx(), src.astype(np.float32, copy=False), flags=flags), src.shape)
 
     def align(self, source, init_T=np.eye(4), verbose=False):
         """Gauss-Newton alignment of ``source`` onto the target; returns the 4x4 float64 pose."""
@@ -255,23 +311,28 @@ class Registration:
             return _capi.hash64(src.T) ^ 0x5bd1e995
         return _capi.hash64(np.ascontiguousarray(src))
 
-    def _scan_for(self, source, fresh=False):
+    def _scan_for(self, source, fresh=False, flags=0):
         """Upload (and Morton-sort) the scan; ``calc_H_g_e2`` called repeatedly with the same array
         (the Gauss-Newton pattern) reuses the device copy.  "Same" = same shape, dtype and content:
         the whole buffer is hashed on every call, so an in-place edit is always seen
         (``calc_H_g_e2`` stays pure in its inputs, as in the reference); ``align`` always uploads
-        afresh."""
+        afresh.  ``flags``: what the caller needs of the scan (``FLAG_KEEP_ORDER`` for rows, weights and coresets).  One
+        scan is cached; it is reused when its flags INCLUDE the requested ones, so an order-keeping scan also serves
+        plain calls.  The other way round it cannot: a plain scan cached first is closed and the array uploaded again,
+        with its order kept, on the first rows call (once; later calls of either sort reuse that copy)."""
         if isinstance(source, UploadedScan):
             return source._scan
         src = np.asarray(source)
         if src.ndim != 2 or src.shape[1] != 3:
             raise ValueError("source must have shape (N, 3)")
         key = None if fresh else (src.shape, src.dtype.str, self._digest(src))
-        if key is not None and self._scan is not None and self._scan_key == key:
+        # (a cached scan that remembers the caller's order is the same device copy plus the permutation: it serves a plain
+        # request too, so linearize / weights / coreset alternating with plain calc_H_g_e2 upload and sort once)
+        if key is not None and self._scan is not None and self._scan_key == key and (self._scan.flags & flags) == flags:
             return self._scan
         if self._scan is not None:
             self._scan.close()
-        self._scan = _capi.Scan(self._ctx(), src.astype(np.float32, copy=False))   # registration.py:83
+        self._scan = _capi.Scan(self._ctx(), src.astype(np.float32, copy=False), flags=flags)   # registration.py:83
         self._scan_key = key
         return self._scan
 
