@@ -565,16 +565,6 @@ __global__ void __launch_bounds__(256) k_nn_query_q6(Geom<float> gf, const PtF *
 // =============================================================================================
 // launch functions: run-time arguments -> kernel instantiation (declared in pass_device.h, called from pass.hip)
 // =============================================================================================
-// The one idiom for it: f(std::integral_constant<int, v>) for v in [0, N); any other value counts as 0.  A combination
-// that must not exist as a kernel is kept out with `if constexpr` inside f.
-template <int N, typename F>
-static void with_const(int v, F &&f) {
-    if constexpr (N > 1) {
-        if (v != N - 1) return with_const<N - 1>(v, f);
-    }
-    f(std::integral_constant<int, N - 1>{});
-}
-
 static const dim3 kBlock(256);
 
 void launch_certify(bool voxel, dim3 grid, hipStream_t st, const LinArgs &a) {

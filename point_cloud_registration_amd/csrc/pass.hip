@@ -1,5 +1,5 @@
 // The host side of a pass: what one calc_H_g_e2 / one align / one batch puts on the stream and how it waits for the result
-// (Pass, pass_setup, pass_enqueue, pcr_run_linearize / _align / _batch / _nn).  No kernel lives here and no kernel template is
+// (Pass, pass_setup, pass_enqueue = enqueue_fused | enqueue_search + enqueue_reduce, pcr_run_linearize / _align / _batch / _rows / _nn).  No kernel lives here and no kernel template is
 // named: every launch goes through the launch_* functions of kernels.hip (pass_device.h), so an edit of this file compiles in
 // seconds.
 #include <stdlib.h>
@@ -46,11 +46,12 @@ pcr_status pcr_ensure_scratch(pcr_context *ctx, int64_t n_points) {
     return PCR_OK;
 }
 
-int choose_blocks(const pcr_context *ctx, int64_t n) {
-    // enough 256-thread blocks to fill every CU several times over, never more than the work (odd CU counts round down)
+// enough 256-thread blocks to fill every CU several times over, never more than the work
+static int64_t blocks_wanted(const pcr_context *ctx, int64_t n) {
     const int64_t want = (n + 255) / 256, cap = (int64_t)ctx->num_cu * 8;
-    return grid8(want < cap ? want : cap, ctx->max_blocks);
+    return want < cap ? want : cap;
 }
+int choose_blocks(const pcr_context *ctx, int64_t n) { return grid8(blocks_wanted(ctx, n), ctx->max_blocks); }   // (odd CU counts round down)
 
 // ---- one pass = NN kernel + reduce kernel (variant 1) or the fused kernel (variant 0) ------------
 struct Pass {
@@ -79,7 +80,31 @@ static void set_filter_bound(LinArgs &a, double bound);
 // caller-supplied word must not reach them)
 #define PCR_PUBLIC_FLAGS (PCR_FLAG_ICP_RR_QUIRK | PCR_FLAG_NO_SCAN_SORT | PCR_FLAG_LOCAL_ONLY | PCR_FLAG_HOST_LOOP | PCR_FLAG_DEVICE_LOOP | PCR_FLAG_KEEP_ORDER)
 
+// quirk Q6: a PlaneICP pass over a float64 point target searches in float64 (pcr_target::pts64)
+static bool pass_is_q6(const pcr_target *t, int kind) { return kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr; }
+
+// what the batched and the rows passes refuse: a communicator, and Q6 (the nouns and the note are the caller's, for the message)
+static pcr_status refuse_comm_and_q6(const pcr_target *t, int kind, const char *passes, const char *plane_passes, const char *q6_note) {
+    if (t->ctx->comm != nullptr) pcr_set_error("%s are not available on a context with a communicator attached (pcr_comm_*, pcr_group)", passes);
+    else if (pass_is_q6(t, kind)) pcr_set_error("%s are not available over a float64 point target (%s)", plane_passes, q6_note);
+    else return PCR_OK;
+    return PCR_ERR_UNSUPPORTED;
+}
+
 // ---- pass_setup, step by step (in the order they run) ----
+// what every Pass starts from (pass_setup, rows_search); reads the context only, touches neither the scan nor the target
+static void pass_init(Pass *ps, pcr_target *t, pcr_scan *s, int kind, bool one_kernel, bool q6) {
+    memset(ps, 0, sizeof *ps);
+    ps->ctx = t->ctx; ps->t = t; ps->s = s; ps->kind = kind; ps->one_kernel = one_kernel; ps->q6 = q6;
+#ifdef PCR_DEV
+    ps->fused_fin = t->ctx->fuse_finalize;
+#else
+    ps->fused_fin = true;                       // (the unfused folds live in kernels_dev.hip: developer build only)
+#endif
+    ps->nn_mode = PCR_NN_FULL;
+    ps->motion = -1.0;
+}
+
 static pcr_status pass_validate(const pcr_target *t, const pcr_scan *s, int kind, double max_dist) {
     PCR_REQUIRE(s->ctx == t->ctx, "scan and target belong to different contexts");
     PCR_REQUIRE(kind >= PCR_ICP && kind <= PCR_NDT, "unknown kind");
@@ -220,10 +245,10 @@ static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, dou
     PCR_TRY(pcr_ensure_scratch(ctx, s->n));
     // one fused kernel or search + reduce?  variant 2 (default) decides by size: a small scan is latency-bound
     // and runs fused (tools/variant_crossover.py: 100 k points 74 vs 80 us per pass, 300 k 97 vs 92, 1.06 M 190 vs 151)
-    // quirk Q6: a PlaneICP pass over a float64 point target searches in float64 -- always search + reduce, always a full search
-    const bool q6 = kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr;
+    // quirk Q6: always search + reduce, always a full search
+    const bool q6 = pass_is_q6(t, kind);
     const bool one_kernel = (force_fused || pcr_pass_is_fused(ctx, s)) && !q6;
-    ps->ctx = ctx; ps->t = t; ps->s = s; ps->kind = kind; ps->one_kernel = one_kernel; ps->q6 = q6;
+    pass_init(ps, t, s, kind, one_kernel, q6);
     // k_reduce streams: 4 blocks/CU
     const int nblocks_split = grid8(choose_blocks(ctx, s->n), ctx->num_cu * 4);
     PCR_TRY(pass_scan_buffers(ps, nblocks_split));
@@ -233,14 +258,6 @@ static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, dou
     const bool deep_ok = !t->is_voxel && !one_kernel && !q6 && t->cs_h && nn_plain(ctx);
     if (deep_ok) pass_lazy_deep_lists(ctx, t);
     pass_fill_lin(ps, max_dist, flags & PCR_PUBLIC_FLAGS, filter_ok && t->filter, deep_ok, one_kernel ? choose_blocks(ctx, s->n) : nblocks_split);
-#ifdef PCR_DEV
-    ps->fused_fin = ctx->fuse_finalize;
-#else
-    ps->fused_fin = true;                       // (the unfused folds live in kernels_dev.hip: developer build only)
-#endif
-    ps->nn_mode = PCR_NN_FULL;
-    ps->motion = -1.0;
-    ps->gn_inline = false;
     pass_fill_fin(ps);
     return PCR_OK;
 }
@@ -307,7 +324,130 @@ static FusedVariant fused_variant(const Pass *ps) {
     return v;
 }
 
-// enqueue the kernels of one pass on the context's stream (no waiting)
+// ---- pass_enqueue: the kernels of one pass onto the context's stream (no waiting) ----
+static void enqueue_fused(Pass *ps, dim3 grid) {
+    pcr_context *ctx = ps->ctx;
+    ProfEvent ev;
+    pcr_prof_begin(ctx, PCR_K_LINEARIZE, &ev);
+    RoctxRange range("pcr:linearize");
+    const FusedVariant v = fused_variant(ps);
+#ifdef PCR_DEV
+    if (!ps->fused_fin) pcr_dev_launch_linearize(ps->kind, v.halo, grid, ctx->stream, ps->a);
+    else
+#endif
+    launch_fused(ps->kind, v, grid, ctx->stream, ps->a, ps->f);
+    pcr_prof_end(ctx, &ev);
+}
+
+// grid of a search launch: exactly one resident generation of waves; they share the tiles dynamically
+// (coop: the developer build's wave-cooperative kernel, which has an occupancy of its own)
+struct SearchGrid { int64_t tiles, need; int nb; };     // tiles of the hand-out, the blocks they can keep busy, the blocks launched
+static SearchGrid search_grid(const Pass *ps, bool filter, int mode, bool coop = false) {
+    const pcr_context *ctx = ps->ctx;
+    const bool vox = ps->t->is_voxel != 0;
+    int64_t nb = (int64_t)ctx->num_cu * ctx->nn_blocks_per_cu[filter ? 3 : vox ? 1 : coop ? 2 : 0];
+    if (!filter && !vox && mode == PCR_NN_FULL && !coop && ps->a.gf.lbox != nullptr) nb = (int64_t)ctx->num_cu * ctx->nn_blocks_lb;
+    // tiles of the hand-out: 64 points per wave, or the 1024-point chunks of a LIST pass (one block per chunk)
+    const int64_t tiles = mode == PCR_NN_LIST ? (ps->a.n + PCR_LIST_CHUNK - 1) / PCR_LIST_CHUNK : (ps->a.n + 63) / 64;
+    const int64_t need = mode == PCR_NN_LIST ? tiles : (tiles + 3) / 4;
+    return SearchGrid{tiles, need, grid8(nb < need ? nb : need)};
+}
+
+// the search without a float32 filter in front: a point target, or the centroids in float64 (through the row occupancy
+// words where the gate spans enough rows of cells); mode and hand-out as ps says
+static void launch_plain_search(const Pass *ps, dim3 nn_grid) {
+    const pcr_context *ctx = ps->ctx;
+    const pcr_target *t = ps->t;
+    const LinArgs &a = ps->a;
+    const int voxel = !t->is_voxel ? 0 : t->gd.rowocc != nullptr && (ctx->vox_occ >= 0 ? ctx->vox_occ != 0 : a.md_d / t->gd.h + 2.0 >= 5.0) ? 2 : 1;
+    launch_nn_scan(voxel, ps->nn_mode, voxel == 0 && t->cs_h != nullptr, a.sched_local, nn_grid, ctx->stream, a);
+}
+
+// filter: the float32 filter search (voxel targets with a filter index, Q6)
+static pcr_status enqueue_search(Pass *ps, dim3 grid, bool filter) {
+    pcr_context *ctx = ps->ctx;
+    const LinArgs &a = ps->a;
+    const bool vox = ps->t->is_voxel != 0;
+    const int mode = ps->nn_mode;
+    ProfEvent ev;
+    if (mode == PCR_NN_LIST) {
+        // the previous matches that are provably still exact need no search (k_certify)
+        pcr_prof_begin(ctx, PCR_K_CERTIFY, &ev);
+        RoctxRange range("pcr:certify");
+        launch_certify(vox, grid, ctx->stream, a);
+        pcr_prof_end(ctx, &ev);
+    }
+    pcr_prof_begin(ctx, PCR_K_NN, &ev);
+    {
+        RoctxRange range("pcr:nn_search");
+        const bool coop = !vox && !ps->q6 && ctx->nn_mode == 2;        // (developer build only: pcr_set_nn_mode)
+        const SearchGrid g = search_grid(ps, filter, mode, coop);
+        const int64_t tiles = g.tiles, nb = g.nb;
+        const dim3 nn_grid((unsigned)nb);
+        // hand-out policy: at most ~1.5 tiles per launched wave -> block-local (nn_tile_loop)
+        // ... or the scan moved little since the previous pass: the far poses are where the cost of a tile varies 10x
+        // and the global counters pay (1.06 M points, per pose: 235 / 185 / 108 / 55 / 52 us with the counters,
+        // 221 / 203 / 111 / 51 / 40 block-local); the device-resident loop decides in k_gn_update (2)
+        int local = tiles * 2 <= nb * 4 * 3 ? 1 : 0;
+        // (only while a wave gets a handful of tiles: with 38 tiles per wave -- the 12.5 M-point shard -- the static
+        // deal loses whatever the pose: plane_100m 2.93 vs 2.82 ms per pass, vplane_10m 1.075 vs 1.06)
+        // Round 5: with the chunk interleave (an XCD's tiles spread over the whole scan) the block-local deal is balanced at the
+        // far poses too and wins at EVERY pose of such scans (1.06 M points, search per trajectory: plane_b01 569 -> 531 us, icp_b01
+        // 2316 -> 2282, resampled 928 -> 874; forced global counters 590 / 2541 / 966) -- but not with tens of tiles per wave
+        // (vplane_10m 3492 -> 5174 us, plane_100m +12 %): profiles/r05_handout_policy.txt
+        if (!local && mode != PCR_NN_LIST && tiles <= nb * 4 * 8) {
+            if (PCR_TILE_INTERLEAVE) local = 1;
+            else if (a.pose != nullptr) local = mode == PCR_NN_FULL ? 2 : 0;
+            else if (ps->motion >= 0.0 && ps->motion < ps->f.local_len) local = 1;
+        }
+        if (ctx->tile_local >= 0) local = ctx->tile_local;
+        ps->a.sched_local = local;
+#ifdef PCR_DEV
+        // (developer build, nn_mode 4: the MFMA-filtered search on every plain full search of a point target)
+        const bool mfma = !vox && !ps->q6 && mode == PCR_NN_FULL && ps->t->n > 0 && ctx->nn_mode == 4;
+        if (coop) {
+            pcr_dev_launch_coop(nn_grid, ctx->stream, a);
+        } else if (mfma) {
+            const int64_t nbm = (int64_t)ctx->num_cu * ctx->nn_blocks_per_cu[4];
+            launch_nn_mfma(ps->t->cs_h != nullptr, ps->a.sched_local == 1 ? 1 : 0, dim3((unsigned)grid8(nbm < g.need ? nbm : g.need)), ctx->stream, a);
+        } else
+#endif
+        if (filter) {
+            if (++ctx->filter_stamp == 0) {                    // (wrapped after 2^32 passes: start over)
+                HIP_TRY(hipMemsetAsync(a.pending, 0, 4, ctx->stream));
+                ctx->filter_stamp = 1;
+            }
+            ps->a.stamp = ctx->filter_stamp;
+            const bool fhalo = ps->q6 ? ps->t->cs_h != nullptr : ps->t->filter->cs_h != nullptr;
+            launch_nn_filter(fhalo, ps->a.sched_local == 1 ? 1 : 0, !ps->fused_fin, ps->q6, nn_grid, ctx->stream, a);
+        } else {
+            // host-driven pass over a point target: the list set by how far the scan moved since the previous pass (unknown: the deeper one)
+            if (!vox && a.pose == nullptr && a.halo2_f > 0.f && mode == PCR_NN_FULL && !(ps->motion >= 0.0 && ps->motion < ps->f.deep_len)) {
+                ps->a.gf.halo = a.halo2_f; ps->a.gf.cs_h = a.cs_h2; ps->a.gf.pts_h = a.pts_h2; ps->a.gf.j_h = a.j_h2;
+                ps->a.gf.lbox_h = a.lbox_h2; ps->a.gf.gbox_h = a.gbox_h2;
+            }
+            launch_plain_search(ps, nn_grid);
+        }
+        ps->s->nn_serial = ps->t->serial;      // nn_j now holds matches against this target
+    }
+    pcr_prof_end(ctx, &ev);
+    return PCR_OK;
+}
+
+// (filter: the pending points of the filter search are settled in the prologue of the reduce kernel)
+static void enqueue_reduce(Pass *ps, dim3 grid, bool filter) {
+    pcr_context *ctx = ps->ctx;
+    ProfEvent ev;
+    pcr_prof_begin(ctx, PCR_K_REDUCE, &ev);
+    RoctxRange range("pcr:reduce");
+#ifdef PCR_DEV
+    if (!ps->fused_fin) pcr_dev_launch_reduce(ps->kind, grid, ctx->stream, ps->a);
+    else
+#endif
+    launch_reduce_kind(ps->kind, filter, grid, ctx->stream, ps->a, ps->f);
+    pcr_prof_end(ctx, &ev);
+}
+
 static pcr_status pass_enqueue(Pass *ps) {
     pcr_context *ctx = ps->ctx;
 #ifdef PCR_DEV
@@ -316,112 +456,25 @@ static pcr_status pass_enqueue(Pass *ps) {
         if (dbg) ps->a.flags |= (unsigned)(dbg & 3) << 28;
     }
 #endif
-    const LinArgs &a = ps->a;
-    const dim3 grid(a.nblocks);
-    ProfEvent ev;
+    const dim3 grid(ps->a.nblocks);
     if (ctx->prof_on) ctx->prof_this_pass = (ctx->prof_pass++ % (uint64_t)ctx->prof_period) == 0;
     if (ps->one_kernel) {
-        pcr_prof_begin(ctx, PCR_K_LINEARIZE, &ev);
-        RoctxRange range("pcr:linearize");
-        const FusedVariant v = fused_variant(ps);
-#ifdef PCR_DEV
-        if (!ps->fused_fin) pcr_dev_launch_linearize(ps->kind, v.halo, grid, ctx->stream, a);
-        else
-#endif
-        launch_fused(ps->kind, v, grid, ctx->stream, a, ps->f);
-        pcr_prof_end(ctx, &ev);
+        enqueue_fused(ps, grid);
     } else {
-        const bool vox = ps->t->is_voxel != 0;
-        const int mode = ps->nn_mode;
-        const bool filter = (vox && mode == PCR_NN_FULL && a.band_f > 0.f) || ps->q6;
-        if (mode == PCR_NN_LIST) {
-            // the previous matches that are provably still exact need no search (k_certify)
-            pcr_prof_begin(ctx, PCR_K_CERTIFY, &ev);
-            RoctxRange range("pcr:certify");
-            launch_certify(vox, grid, ctx->stream, a);
-            pcr_prof_end(ctx, &ev);
-        }
-        pcr_prof_begin(ctx, PCR_K_NN, &ev);
-        {   // exactly one resident generation of waves; they share the tiles dynamically
-            RoctxRange range("pcr:nn_search");
-            int64_t nb = (int64_t)ctx->num_cu * ctx->nn_blocks_per_cu[filter ? 3 : vox ? 1 : (ctx->nn_mode == 2 && !ps->q6 ? 2 : 0)];
-            if (!filter && !vox && mode == PCR_NN_FULL && ctx->nn_mode != 2 && a.gf.lbox != nullptr)
-                nb = (int64_t)ctx->num_cu * ctx->nn_blocks_lb;
-            // tiles of the hand-out: 64 points per wave, or the 1024-point chunks of a LIST pass (one block per chunk)
-            const int64_t tiles = mode == PCR_NN_LIST ? (a.n + PCR_LIST_CHUNK - 1) / PCR_LIST_CHUNK : (a.n + 63) / 64;
-            const int64_t need = mode == PCR_NN_LIST ? tiles : (tiles + 3) / 4;
-            nb = grid8(nb < need ? nb : need);
-            const dim3 nn_grid((unsigned)nb);
-            // hand-out policy: at most ~1.5 tiles per launched wave -> block-local (nn_tile_loop)
-            // ... or the scan moved little since the previous pass: the far poses are where the cost of a tile varies 10x
-            // and the global counters pay (1.06 M points, per pose: 235 / 185 / 108 / 55 / 52 us with the counters,
-            // 221 / 203 / 111 / 51 / 40 block-local); the device-resident loop decides in k_gn_update (2)
-            int local = tiles * 2 <= nb * 4 * 3 ? 1 : 0;
-            // (only while a wave gets a handful of tiles: with 38 tiles per wave -- the 12.5 M-point shard -- the static
-            // deal loses whatever the pose: plane_100m 2.93 vs 2.82 ms per pass, vplane_10m 1.075 vs 1.06)
-            // Round 5: with the chunk interleave (an XCD's tiles spread over the whole scan) the block-local deal is balanced at the
-            // far poses too and wins at EVERY pose of such scans (1.06 M points, search per trajectory: plane_b01 569 -> 531 us, icp_b01
-            // 2316 -> 2282, resampled 928 -> 874; forced global counters 590 / 2541 / 966) -- but not with tens of tiles per wave
-            // (vplane_10m 3492 -> 5174 us, plane_100m +12 %): profiles/r05_handout_policy.txt
-            if (!local && mode != PCR_NN_LIST && tiles <= nb * 4 * 8) {
-                if (PCR_TILE_INTERLEAVE) local = 1;
-                else if (a.pose != nullptr) local = mode == PCR_NN_FULL ? 2 : 0;
-                else if (ps->motion >= 0.0 && ps->motion < ps->f.local_len) local = 1;
-            }
-            if (ctx->tile_local >= 0) local = ctx->tile_local;
-            ps->a.sched_local = local;
-#ifdef PCR_DEV
-            // (developer build, nn_mode 4: the MFMA-filtered search on every plain full search of a point target)
-            const bool mfma = !vox && !ps->q6 && mode == PCR_NN_FULL && ps->t->n > 0 && ctx->nn_mode == 4;
-            if (!vox && !ps->q6 && ctx->nn_mode == 2) {
-                pcr_dev_launch_coop(nn_grid, ctx->stream, a);
-            } else if (mfma) {
-                const int64_t nbm = (int64_t)ctx->num_cu * ctx->nn_blocks_per_cu[4];
-                launch_nn_mfma(ps->t->cs_h != nullptr, ps->a.sched_local == 1 ? 1 : 0, dim3((unsigned)grid8(nbm < need ? nbm : need)), ctx->stream, a);
-            } else
-#endif
-            if (!vox && !ps->q6) {
-                // host-driven pass: the list set by how far the scan moved since the previous pass (unknown: the deeper one)
-                if (a.pose == nullptr && a.halo2_f > 0.f && mode == PCR_NN_FULL && !(ps->motion >= 0.0 && ps->motion < ps->f.deep_len)) {
-                    ps->a.gf.halo = a.halo2_f; ps->a.gf.cs_h = a.cs_h2; ps->a.gf.pts_h = a.pts_h2; ps->a.gf.j_h = a.j_h2;
-                    ps->a.gf.lbox_h = a.lbox_h2; ps->a.gf.gbox_h = a.gbox_h2;
-                }
-                launch_nn_scan(0, mode, ps->t->cs_h != nullptr, ps->a.sched_local, nn_grid, ctx->stream, a);
-            } else if (filter) {
-                if (++ctx->filter_stamp == 0) {                    // (wrapped after 2^32 passes: start over)
-                    HIP_TRY(hipMemsetAsync(a.pending, 0, 4, ctx->stream));
-                    ctx->filter_stamp = 1;
-                }
-                ps->a.stamp = ctx->filter_stamp;
-                const bool fhalo = ps->q6 ? ps->t->cs_h != nullptr : ps->t->filter->cs_h != nullptr;
-                launch_nn_filter(fhalo, ps->a.sched_local == 1 ? 1 : 0, !ps->fused_fin, ps->q6, nn_grid, ctx->stream, a);
-            } else if (ps->t->gd.rowocc != nullptr && (ctx->vox_occ >= 0 ? ctx->vox_occ != 0 : a.md_d / ps->t->gd.h + 2.0 >= 5.0)) {
-                launch_nn_scan(2, mode, false, ps->a.sched_local, nn_grid, ctx->stream, a);
-            } else {
-                launch_nn_scan(1, mode, false, ps->a.sched_local, nn_grid, ctx->stream, a);
-            }
-            ps->s->nn_serial = ps->t->serial;      // nn_j now holds matches against this target
-        }
-        pcr_prof_end(ctx, &ev);
-        pcr_prof_begin(ctx, PCR_K_REDUCE, &ev);
-        RoctxRange range("pcr:reduce");
-        // (filter: the pending points of the filter search are settled in the prologue of the reduce kernel)
-#ifdef PCR_DEV
-        if (!ps->fused_fin) pcr_dev_launch_reduce(ps->kind, grid, ctx->stream, a);
-        else
-#endif
-        launch_reduce_kind(ps->kind, filter, grid, ctx->stream, a, ps->f);
-        pcr_prof_end(ctx, &ev);
+        const bool filter = (ps->t->is_voxel && ps->nn_mode == PCR_NN_FULL && ps->a.band_f > 0.f) || ps->q6;
+        PCR_TRY(enqueue_search(ps, grid, filter));
+        enqueue_reduce(ps, grid, filter);
     }
     HIP_TRY(hipGetLastError());
-    if (!ps->fused_fin) {
 #ifdef PCR_DEV
+    if (!ps->fused_fin) {
+        ProfEvent ev;
         pcr_prof_begin(ctx, PCR_K_FINALIZE, &ev);
         pcr_dev_launch_finalize(ctx->stream, ps->f);
         pcr_prof_end(ctx, &ev);
-#endif
         HIP_TRY(hipGetLastError());
     }
+#endif
     return PCR_OK;
 }
 
@@ -671,14 +724,7 @@ pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int
                          double tol, double max_dist, unsigned flags, double *out29, double *T_out, int *iterations,
                          pcr_status *item_status, double *trace_or_null) {
     pcr_context *ctx = t->ctx;
-    if (ctx->comm != nullptr) {
-        pcr_set_error("batched passes are not available on a context with a communicator attached (pcr_comm_*, pcr_group)");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    if (kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr) {
-        pcr_set_error("batched PlaneICP passes are not available over a float64 point target (quirk Q6 runs search + reduce)");
-        return PCR_ERR_UNSUPPORTED;
-    }
+    PCR_TRY(refuse_comm_and_q6(t, kind, "batched passes", "batched PlaneICP passes", "quirk Q6 runs search + reduce"));
     PCR_REQUIRE(n_items >= 0 && n_items <= 65535, "a batch call takes at most 65535 items");
     if (n_items == 0) return PCR_OK;
     pcr_scan *big = scans[0];
@@ -831,19 +877,11 @@ static pcr_status rows_search(Pass *ps, DevBuf<uint32_t> *nn, pcr_target *t, pcr
                               unsigned flags) {
     PCR_TRY(pass_validate(t, s, kind, max_dist));
     pcr_context *ctx = t->ctx;
-    if (ctx->comm != nullptr) {
-        pcr_set_error("rows passes are not available on a context with a communicator attached (pcr_comm_*, pcr_group)");
-        return PCR_ERR_UNSUPPORTED;
-    }
-    if (kind == PCR_PLANE && !t->is_voxel && t->pts64 != nullptr) {
-        pcr_set_error("PlaneICP rows are not available over a float64 point target (quirk Q6)");
-        return PCR_ERR_UNSUPPORTED;
-    }
+    PCR_TRY(refuse_comm_and_q6(t, kind, "rows passes", "PlaneICP rows", "quirk Q6"));
     PCR_REQUIRE(!s->sorted || s->order != nullptr, "a Morton-sorted scan needs PCR_FLAG_KEEP_ORDER (or PCR_FLAG_NO_SCAN_SORT) for rows in the caller's order");
     HIP_TRY(hipSetDevice(ctx->device));
     PCR_TRY(pcr_ensure_scratch(ctx, s->n));
-    memset(ps, 0, sizeof *ps);
-    ps->ctx = ctx; ps->t = t; ps->s = s; ps->kind = kind; ps->fused_fin = true; ps->motion = -1.0;
+    pass_init(ps, t, s, kind, false, false);
     HIP_TRY(nn->alloc((size_t)(s->n > 0 ? s->n : 1)));
     pass_fill_lin(ps, max_dist, flags & PCR_PUBLIC_FLAGS, false, false, 8);
     LinArgs &a = ps->a;
@@ -852,23 +890,16 @@ static pcr_status rows_search(Pass *ps, DevBuf<uint32_t> *nn, pcr_target *t, pcr
     pass_set_mode(ps, PCR_NN_FULL);
     a.sched_local = 1;
     if (s->n == 0) return PCR_OK;
-    const bool vox = t->is_voxel != 0;
-    const bool lb = !vox && a.gf.lbox != nullptr;
-    const int64_t tiles = (a.n + 63) / 64, need = (tiles + 3) / 4;
-    int64_t nb = (int64_t)ctx->num_cu * (lb ? ctx->nn_blocks_lb : ctx->nn_blocks_per_cu[vox ? 1 : 0]);
-    const dim3 nn_grid((unsigned)grid8(nb < need ? nb : need));
     RoctxRange range("pcr:rows_search");
-    if (!vox) launch_nn_scan(0, PCR_NN_FULL, t->cs_h != nullptr, 1, nn_grid, ctx->stream, a);
-    else if (t->gd.rowocc != nullptr && (ctx->vox_occ >= 0 ? ctx->vox_occ != 0 : a.md_d / t->gd.h + 2.0 >= 5.0))
-        launch_nn_scan(2, PCR_NN_FULL, false, 1, nn_grid, ctx->stream, a);
-    else launch_nn_scan(1, PCR_NN_FULL, false, 1, nn_grid, ctx->stream, a);
+    launch_plain_search(ps, dim3((unsigned)search_grid(ps, false, PCR_NN_FULL).nb));
     HIP_TRY(hipGetLastError());
     return PCR_OK;
 }
 
+// the streaming grid of k_rows: as many blocks as choose_blocks wants, not rounded to 8 (no per-XCD spans, no fold)
 static dim3 rows_grid(const pcr_context *ctx, int64_t n) {
-    const int64_t want = (n + 255) / 256, cap = (int64_t)ctx->num_cu * 8;
-    return dim3((unsigned)(want < 1 ? 1 : (want < cap ? want : cap)));
+    const int64_t nb = blocks_wanted(ctx, n);
+    return dim3((unsigned)(nb < 1 ? 1 : nb));
 }
 
 pcr_status pcr_run_rows(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double *J,

@@ -6,6 +6,8 @@
 #include <string.h>
 #include <time.h>
 
+#include <type_traits>
+
 #include "gn_math.h"
 #include "nn_device.h"
 
@@ -150,14 +152,51 @@ __device__ __forceinline__ void acc_rank1(double *acc, const double J[6], double
     acc[28] += 1.0;
 }
 
-__device__ __forceinline__ void acc_plane(double *acc, const PoseK &a, double x, double y, double z,
-                                          double n0, double n1, double n2, double d0, double d1, double d2) {
+// J (1 x 6) and r of one point-to-plane correspondence: r is the return value
+__device__ __forceinline__ double plane_row(const PoseK &a, double x, double y, double z, double n0, double n1, double n2,
+                                            double d0, double d1, double d2, double J[6]) {
     const double r = (n0 * d0 + n1 * d1) + n2 * d2;                          // plane_icp.py:49
     const double ra = a.R[0] * n0 + a.R[3] * n1 + a.R[6] * n2;               // R^T n, plane_icp.py:51
     const double rb = a.R[1] * n0 + a.R[4] * n1 + a.R[7] * n2;
     const double rc = a.R[2] * n0 + a.R[5] * n1 + a.R[8] * n2;
-    const double J[6] = {n0, n1, n2, -z * rb + y * rc, z * ra - x * rc, -y * ra + x * rb};   // math_tools.py:22-31
+    J[0] = n0; J[1] = n1; J[2] = n2;                                         // math_tools.py:22-31
+    J[3] = -z * rb + y * rc; J[4] = z * ra - x * rc; J[5] = -y * ra + x * rb;
+    return r;
+}
+
+__device__ __forceinline__ void acc_plane(double *acc, const PoseK &a, double x, double y, double z,
+                                          double n0, double n1, double n2, double d0, double d1, double d2) {
+    double J[6];
+    const double r = plane_row(a, x, y, z, n0, n1, n2, d0, d1, d2, J);
     acc_rank1(acc, J, r);
+}
+
+// A = -R skew(p), the rotation block of J = [I, A] (ICP, NDT; ndt.py:40): row i, and the whole of it
+__device__ __forceinline__ void skew_row(const PoseK &a, int i, double x, double y, double z, double Ai[3]) {
+    const double ri0 = a.R[3 * i], ri1 = a.R[3 * i + 1], ri2 = a.R[3 * i + 2];
+    // -(R S) with S = [[0,-z,y],[z,0,-x],[-y,x,0]]
+    Ai[0] = -(ri1 * z - ri2 * y);
+    Ai[1] = -(-ri0 * z + ri2 * x);
+    Ai[2] = -(ri0 * y - ri1 * x);
+}
+__device__ __forceinline__ void skew_A(const PoseK &a, double x, double y, double z, double A[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) skew_row(a, i, x, y, z, A[i]);
+}
+
+// v of ICP's g[3:] = sum p x v  (returned by value: with reference results the ICP kernels schedule differently)
+__device__ __forceinline__ double3 icp_v(const PoseK &a, unsigned flags, double r0, double r1, double r2) {
+    double3 v;
+    if (flags & PCR_FLAG_ICP_RR_QUIRK) {                                     // quirk Q1, icp.py:53-54
+        v.x = a.R[0] * r0 + a.R[1] * r1 + a.R[2] * r2;
+        v.y = a.R[3] * r0 + a.R[4] * r1 + a.R[5] * r2;
+        v.z = a.R[6] * r0 + a.R[7] * r1 + a.R[8] * r2;
+    } else {                                                                 // consistent J^T r, icp.py:81-87
+        v.x = a.R[0] * r0 + a.R[3] * r1 + a.R[6] * r2;
+        v.y = a.R[1] * r0 + a.R[4] * r1 + a.R[7] * r2;
+        v.z = a.R[2] * r0 + a.R[5] * r1 + a.R[8] * r2;
+    }
+    return v;
 }
 
 __device__ __forceinline__ void acc_icp(double *acc, const PoseK &a, unsigned flags, double x, double y, double z,
@@ -167,17 +206,8 @@ __device__ __forceinline__ void acc_icp(double *acc, const PoseK &a, unsigned fl
     acc[4] = fma(x, x, acc[4]); acc[5] = fma(x, y, acc[5]); acc[6] = fma(x, z, acc[6]);
     acc[7] = fma(y, y, acc[7]); acc[8] = fma(y, z, acc[8]); acc[9] = fma(z, z, acc[9]);
     acc[10] += r0; acc[11] += r1; acc[12] += r2;
-    double v0, v1, v2;
-    if (flags & PCR_FLAG_ICP_RR_QUIRK) {                                     // quirk Q1, icp.py:53-54
-        v0 = a.R[0] * r0 + a.R[1] * r1 + a.R[2] * r2;
-        v1 = a.R[3] * r0 + a.R[4] * r1 + a.R[5] * r2;
-        v2 = a.R[6] * r0 + a.R[7] * r1 + a.R[8] * r2;
-    } else {                                                                 // consistent J^T r, icp.py:81-87
-        v0 = a.R[0] * r0 + a.R[3] * r1 + a.R[6] * r2;
-        v1 = a.R[1] * r0 + a.R[4] * r1 + a.R[7] * r2;
-        v2 = a.R[2] * r0 + a.R[5] * r1 + a.R[8] * r2;
-    }
-    acc[13] += y * v2 - z * v1; acc[14] += z * v0 - x * v2; acc[15] += x * v1 - y * v0;
+    const double3 v = icp_v(a, flags, r0, r1, r2);
+    acc[13] += y * v.z - z * v.y; acc[14] += z * v.x - x * v.z; acc[15] += x * v.y - y * v.x;
     acc[16] += r0 * r0 + r1 * r1 + r2 * r2;
 }
 
@@ -190,14 +220,7 @@ __device__ __forceinline__ void acc_ndt(double *acc, const PoseK &a, double x, d
     // to round 2's for finite inputs.
     const double C[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
     double A[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double ri0 = a.R[3 * i], ri1 = a.R[3 * i + 1], ri2 = a.R[3 * i + 2];
-        // -(R S) with S = [[0,-z,y],[z,0,-x],[-y,x,0]]
-        A[i][0] = -(ri1 * z - ri2 * y);
-        A[i][1] = -(-ri0 * z + ri2 * x);
-        A[i][2] = -(ri0 * y - ri1 * x);
-    }
+    skew_A(a, x, y, z, A);
     double CA[3][3], Cd[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -239,33 +262,62 @@ __device__ __forceinline__ bool gate_f64(const LinArgs &a, double dx, double dy,
     return __builtin_sqrt((dx * dx + dy * dy) + dz * dz) < a.md_d;
 }
 
-// gather the matched record at cell-sorted index j and accumulate (GATE: apply the distance gate here)
+// ---- one correspondence: gather, residual, gate -- the ONE definition the fused, reduce and rows kernels share ----
+// the matched record of a point target at cell-sorted index j (PLANE: point and normal from ONE 32-byte record, two 16-byte
+// loads of the same sector) ...
+template <int KIND>
+__device__ __forceinline__ void load_point(const LinArgs &a, uint32_t j, float4 &q, float4 &nn) {
+    if (KIND == PCR_PLANE) { const float4 *rec = reinterpret_cast<const float4 *>(a.pn + j); q = rec[0]; nn = rec[1]; }
+    else q = a.pts[j];
+}
+// ... and of a lane that may have no match (PCR_NONE: zeros), for the loops that keep several gathers in flight (voxel kinds: nothing)
+template <int KIND>
+__device__ __forceinline__ void gather_point(const LinArgs &a, uint32_t j, float4 &q, float4 &nn) {
+    q = make_float4(0, 0, 0, 0); nn = q;
+    if ((KIND == PCR_ICP || KIND == PCR_PLANE) && j != PCR_NONE) load_point<KIND>(a, j, q, nn);
+}
+// the payload of the voxel at cell-sorted index j
+__device__ __forceinline__ const double *vox_normal(const LinArgs &a, uint32_t j) { return a.vnorm + 3 * (size_t)j; }
+__device__ __forceinline__ const double *vox_icov(const LinArgs &a, uint32_t j) { return a.vicov + 6 * (size_t)j; }
+
+// residual and gate (GATE = false: every match passes).  Point targets: float32, against the gathered record q ...
+template <bool GATE>
+__device__ __forceinline__ bool residual_f32(const LinArgs &a, const float4 &q, float tx, float ty, float tz, float &dx, float &dy, float &dz) {
+    dx = tx - q.x; dy = ty - q.y; dz = tz - q.z;
+    return !GATE || gate_f32(a, dx, dy, dz);
+}
+// ... voxel targets: float64, against the centroid m at cell-sorted index j
+template <bool GATE>
+__device__ __forceinline__ bool residual_f64(const LinArgs &a, uint32_t j, float tx, float ty, float tz, PtD &m, double &dx, double &dy, double &dz) {
+    m = a.means[j];
+    dx = (double)tx - m.x; dy = (double)ty - m.y; dz = (double)tz - m.z;
+    return !GATE || gate_f64(a, dx, dy, dz);
+}
+
+// residual + gate + accumulate for a point target whose record is already here
+template <int KIND, bool GATE>
+__device__ __forceinline__ void accumulate_point(double *acc, const LinArgs &a, const PoseK &P, const float4 &q, const float4 &nn,
+                                                 float x, float y, float z, float tx, float ty, float tz) {
+    float dx, dy, dz;
+    if (!residual_f32<GATE>(a, q, tx, ty, tz, dx, dy, dz)) return;
+    if (KIND == PCR_PLANE) acc_plane(acc, P, x, y, z, nn.x, nn.y, nn.z, (double)dx, (double)dy, (double)dz);
+    else acc_icp(acc, P, a.flags, x, y, z, (double)dx, (double)dy, (double)dz);       // icp.py:39
+}
+
+// gather the matched record at cell-sorted index j and accumulate
 template <int KIND, bool GATE>
 __device__ __forceinline__ void accumulate(double *acc, const LinArgs &a, const PoseK &P, uint32_t j,
                                            float x, float y, float z, float tx, float ty, float tz) {
-    if (KIND == PCR_ICP) {
-        const PtF q = a.pts[j];
-        const float dx = tx - q.x, dy = ty - q.y, dz = tz - q.z;
-        if (GATE && !gate_f32(a, dx, dy, dz)) return;
-        acc_icp(acc, P, a.flags, x, y, z, (double)dx, (double)dy, (double)dz);   // icp.py:39
-    } else if (KIND == PCR_PLANE) {
-        // point and normal from ONE 32-byte record (two 16-byte loads of the same sector)
-        const float4 *rec = reinterpret_cast<const float4 *>(a.pn + j);
-        const float4 q = rec[0], nn = rec[1];
-        const float dx = tx - q.x, dy = ty - q.y, dz = tz - q.z;
-        if (GATE && !gate_f32(a, dx, dy, dz)) return;
-        acc_plane(acc, P, x, y, z, nn.x, nn.y, nn.z, (double)dx, (double)dy, (double)dz);
-    } else if (KIND == PCR_VPLANE) {
-        const PtD q = a.means[j];
-        const double dx = (double)tx - q.x, dy = (double)ty - q.y, dz = (double)tz - q.z;
-        if (GATE && !gate_f64(a, dx, dy, dz)) return;
-        const double *nn = a.vnorm + 3 * (size_t)j;
-        acc_plane(acc, P, x, y, z, nn[0], nn[1], nn[2], dx, dy, dz);
+    if (KIND == PCR_ICP || KIND == PCR_PLANE) {
+        float4 q, nn;
+        load_point<KIND>(a, j, q, nn);
+        accumulate_point<KIND, GATE>(acc, a, P, q, nn, x, y, z, tx, ty, tz);
     } else {
-        const PtD q = a.means[j];
-        const double dx = (double)tx - q.x, dy = (double)ty - q.y, dz = (double)tz - q.z;
-        if (GATE && !gate_f64(a, dx, dy, dz)) return;
-        acc_ndt(acc, P, x, y, z, a.vicov + 6 * (size_t)j, dx, dy, dz);
+        PtD m;
+        double dx, dy, dz;
+        if (!residual_f64<GATE>(a, j, tx, ty, tz, m, dx, dy, dz)) return;
+        if (KIND == PCR_VPLANE) { const double *nn = vox_normal(a, j); acc_plane(acc, P, x, y, z, nn[0], nn[1], nn[2], dx, dy, dz); }
+        else acc_ndt(acc, P, x, y, z, vox_icov(a, j), dx, dy, dz);
     }
 }
 
@@ -307,13 +359,7 @@ __device__ __forceinline__ void reduce_stream(double *acc, const LinArgs &a, con
                 j[u] = iu < end ? stream_load(a.nn_j + iu) : PCR_NONE;
             }
 #pragma unroll
-            for (int u = 0; u < W; ++u) {
-                q[u] = make_float4(0, 0, 0, 0); nr[u] = q[u];
-                if (j[u] != PCR_NONE) {
-                    if (KIND == PCR_PLANE) { const float4 *r = reinterpret_cast<const float4 *>(a.pn + j[u]); q[u] = r[0]; nr[u] = r[1]; }
-                    else q[u] = a.pts[j[u]];
-                }
-            }
+            for (int u = 0; u < W; ++u) gather_point<KIND>(a, j[u], q[u], nr[u]);
 #pragma unroll
             for (int u = 0; u < W; ++u) {
                 if (j[u] == PCR_NONE) continue;
@@ -321,11 +367,7 @@ __device__ __forceinline__ void reduce_stream(double *acc, const LinArgs &a, con
                 const float x = stream_load(a.sx + iu), y = stream_load(a.sy + iu), z = stream_load(a.sz + iu);
                 float tx, ty, tz;
                 xform(P, x, y, z, tx, ty, tz);
-                const float dx = tx - q[u].x, dy = ty - q[u].y, dz = tz - q[u].z;
-                if (gate_f32(a, dx, dy, dz)) {
-                    if (KIND == PCR_PLANE) acc_plane(acc, P, x, y, z, nr[u].x, nr[u].y, nr[u].z, (double)dx, (double)dy, (double)dz);
-                    else acc_icp(acc, P, a.flags, x, y, z, (double)dx, (double)dy, (double)dz);
-                }
+                accumulate_point<KIND, true>(acc, a, P, q[u], nr[u], x, y, z, tx, ty, tz);
             }
         }
     } else {
@@ -1019,7 +1061,17 @@ __device__ __forceinline__ bool ticket_fold_emit(double *acc, const LinArgs &a, 
     return true;
 }
 
-// ---- launch functions of kernels.hip: run-time arguments -> kernel instantiation (the host side of a pass is pass.hip) ----
+// ---- launch functions of kernels.hip and rows.hip: run-time arguments -> kernel instantiation (the host side of a pass is pass.hip) ----
+// The one idiom for it: f(std::integral_constant<int, v>) for v in [0, N); any other value counts as 0.  A combination
+// that must not exist as a kernel is kept out with `if constexpr` inside f.
+template <int N, typename F>
+static void with_const(int v, F &&f) {
+    if constexpr (N > 1) {
+        if (v != N - 1) return with_const<N - 1>(v, f);
+    }
+    f(std::integral_constant<int, N - 1>{});
+}
+
 #define PCR_LIST_CHUNK 1024          // scan points per chunk of a LIST pass (kernels.hip: nn_chunk_list)
 // Which fused kernel (k_linearize_finalize / k_linearize_batch) a pass over a target runs, the kind aside.  Point targets:
 // halo = the target has the extended lists, lb = heavy target (ranges through their leaf / group boxes); voxel targets: filt =

@@ -1,7 +1,9 @@
-// Per-correspondence rows: the sibling of the reduce kernel that WRITES what k_reduce_finalize accumulates.
+// Per-correspondence rows: the kernel that WRITES what k_reduce_finalize accumulates.
 //
-// k_rows<KIND, MODE> streams what the reduce kernel streams -- nn_j, the scan SoA, the matched record -- through the same
-// xform and the same gate_f32 / gate_f64, so a point is in or out exactly as in pcr_linearize.
+// k_rows<KIND, MODE> sits where the reduce kernel would: it streams nn_j, the scan SoA and the matched record, and takes the
+// correspondence (gather_point, residual_f32 / _f64: residual and gate) and every Jacobian expression (plane_row, skew_A / skew_row,
+// icp_v, acc_plane, acc_ndt) from pass_device.h, where the reduce and fused kernels take them: a point is in or out exactly as in
+// pcr_linearize, and nothing below restates an expression of the sums.
 //   MODE 0 (rows):  per scan point J (m x 6), r (m), w (1 in / 0 out), idx (target index, -1 out) and, for NDT, the
 //                   symmetric 3 x 3 inverse covariance; rows of a gated-out point are zero.  Runs in the scan's DEVICE
 //                   order (lane l of a wave = point l of 64 consecutive ones, like reduce_stream) and scatters each
@@ -29,6 +31,7 @@ struct RowCorr {
     int64_t tidx;            // caller's target index / voxel position
 };
 
+// fills RowCorr from the shared residual + gate (pass_device.h: residual_f32 / residual_f64)
 template <int KIND>
 __device__ __forceinline__ RowCorr row_corr(const LinArgs &a, const PoseK &P, int64_t i, uint32_t j, const float4 &q, const float4 &nr) {
     RowCorr c;
@@ -38,22 +41,18 @@ __device__ __forceinline__ RowCorr row_corr(const LinArgs &a, const PoseK &P, in
     float tx, ty, tz;
     xform(P, x, y, z, tx, ty, tz);
     if (KIND == PCR_ICP || KIND == PCR_PLANE) {
-        const float dx = tx - q.x, dy = ty - q.y, dz = tz - q.z;
-        if (!gate_f32(a, dx, dy, dz)) return c;
+        float dx, dy, dz;
+        if (!residual_f32<true>(a, q, tx, ty, tz, dx, dy, dz)) return c;
         c.d0 = (double)dx; c.d1 = (double)dy; c.d2 = (double)dz;
         if (KIND == PCR_PLANE) { c.n0 = nr.x; c.n1 = nr.y; c.n2 = nr.z; }
         c.tidx = (int64_t)__float_as_uint(q.w);
     } else {
-        const PtD m = a.means[j];
-        const double dx = (double)tx - m.x, dy = (double)ty - m.y, dz = (double)tz - m.z;
-        if (!gate_f64(a, dx, dy, dz)) return c;
+        PtD m;
+        double dx, dy, dz;
+        if (!residual_f64<true>(a, j, tx, ty, tz, m, dx, dy, dz)) return c;
         c.d0 = dx; c.d1 = dy; c.d2 = dz;
-        if (KIND == PCR_VPLANE) {
-            const double *nn = a.vnorm + 3 * (size_t)j;
-            c.n0 = nn[0]; c.n1 = nn[1]; c.n2 = nn[2];
-        } else {
-            c.c6 = a.vicov + 6 * (size_t)j;
-        }
+        if (KIND == PCR_VPLANE) { const double *nn = vox_normal(a, j); c.n0 = nn[0]; c.n1 = nn[1]; c.n2 = nn[2]; }
+        else c.c6 = vox_icov(a, j);
         c.tidx = (int64_t)__double_as_longlong(m.w);
     }
     c.ok = true; c.x = x; c.y = y; c.z = z;
@@ -68,25 +67,23 @@ __device__ __forceinline__ void rows_store(const RowArgs &ra, const PoseK &P, co
     ra.w[dest] = c.ok ? 1.0 : 0.0;
     if (ra.idx) ra.idx[dest] = c.tidx;
     if (KIND == PCR_PLANE || KIND == PCR_VPLANE) {
-        const double r = (c.n0 * c.d0 + c.n1 * c.d1) + c.n2 * c.d2;                         // acc_plane's expressions
-        const double ta = P.R[0] * c.n0 + P.R[3] * c.n1 + P.R[6] * c.n2;
-        const double tb = P.R[1] * c.n0 + P.R[4] * c.n1 + P.R[7] * c.n2;
-        const double tc = P.R[2] * c.n0 + P.R[5] * c.n1 + P.R[8] * c.n2;
+        double Jr[6];
+        const double r = plane_row(P, c.x, c.y, c.z, c.n0, c.n1, c.n2, c.d0, c.d1, c.d2, Jr);
         double *J = ra.J + 6 * dest;                                                        // 48 bytes: three 16-byte stores
-        store2(J, c.n0, c.n1);
-        store2(J + 2, c.n2, -c.z * tb + c.y * tc);
-        store2(J + 4, c.z * ta - c.x * tc, -c.y * ta + c.x * tb);
+        store2(J, Jr[0], Jr[1]);
+        store2(J + 2, Jr[2], Jr[3]);
+        store2(J + 4, Jr[4], Jr[5]);
         ra.r[dest] = r;
     } else {
         const double one = c.ok ? 1.0 : 0.0;
         double *J = ra.J + 18 * dest;                                                       // 144 bytes: nine 16-byte stores
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double ri0 = P.R[3 * i], ri1 = P.R[3 * i + 1], ri2 = P.R[3 * i + 2];
-            const double a0 = -(ri1 * c.z - ri2 * c.y), a1 = -(-ri0 * c.z + ri2 * c.x), a2 = -(ri0 * c.y - ri1 * c.x);   // acc_ndt's A
+        for (int i = 0; i < 3; ++i) {                                                       // (row by row: nine values never live at once)
+            double Ai[3];
+            skew_row(P, i, c.x, c.y, c.z, Ai);
             store2(J + 6 * i, i == 0 ? one : 0.0, i == 1 ? one : 0.0);
-            store2(J + 6 * i + 2, i == 2 ? one : 0.0, a0);
-            store2(J + 6 * i + 4, a1, a2);
+            store2(J + 6 * i + 2, i == 2 ? one : 0.0, Ai[0]);
+            store2(J + 6 * i + 4, Ai[1], Ai[2]);
         }
         double *r = ra.r + 3 * dest;
         r[0] = c.d0; r[1] = c.d1; r[2] = c.d2;
@@ -115,13 +112,7 @@ __device__ __forceinline__ void terms_store(const LinArgs &a, const RowArgs &ra,
     } else {
         // ICP, written out from J = [I, A], A = -R skew(p): H = [[I, A], [., A^T A]], g = [r, p x v], e2 = r . r
         double A[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double ri0 = P.R[3 * i], ri1 = P.R[3 * i + 1], ri2 = P.R[3 * i + 2];
-            A[i][0] = -(ri1 * c.z - ri2 * c.y);
-            A[i][1] = -(-ri0 * c.z + ri2 * c.x);
-            A[i][2] = -(ri0 * c.y - ri1 * c.x);
-        }
+        skew_A(P, c.x, c.y, c.z, A);
         int p = 0;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -135,18 +126,9 @@ __device__ __forceinline__ void terms_store(const LinArgs &a, const RowArgs &ra,
 #pragma unroll
             for (int j = i; j < 3; ++j) { acc[p] = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j]; ++p; }
         const double r0 = c.d0, r1 = c.d1, r2 = c.d2;
-        double v0, v1, v2;
-        if (a.flags & PCR_FLAG_ICP_RR_QUIRK) {                                   // quirk Q1: p x (R r), as acc_icp
-            v0 = P.R[0] * r0 + P.R[1] * r1 + P.R[2] * r2;
-            v1 = P.R[3] * r0 + P.R[4] * r1 + P.R[5] * r2;
-            v2 = P.R[6] * r0 + P.R[7] * r1 + P.R[8] * r2;
-        } else {                                                                 // J^T r: p x (R^T r)
-            v0 = P.R[0] * r0 + P.R[3] * r1 + P.R[6] * r2;
-            v1 = P.R[1] * r0 + P.R[4] * r1 + P.R[7] * r2;
-            v2 = P.R[2] * r0 + P.R[5] * r1 + P.R[8] * r2;
-        }
+        const double3 v = icp_v(P, a.flags, r0, r1, r2);
         acc[21] = r0; acc[22] = r1; acc[23] = r2;
-        acc[24] = c.y * v2 - c.z * v1; acc[25] = c.z * v0 - c.x * v2; acc[26] = c.x * v1 - c.y * v0;
+        acc[24] = c.y * v.z - c.z * v.y; acc[25] = c.z * v.x - c.x * v.z; acc[26] = c.x * v.y - c.y * v.x;
         acc[27] = r0 * r0 + r1 * r1 + r2 * r2;
     }
 #pragma unroll
@@ -178,13 +160,7 @@ __global__ void __launch_bounds__(256) k_rows(const LinArgs a, const RowArgs ra)
             }
         }
 #pragma unroll
-        for (int u = 0; u < W; ++u) {
-            q[u] = make_float4(0, 0, 0, 0); nr[u] = q[u];
-            if (POINT && j[u] != PCR_NONE) {
-                if (KIND == PCR_PLANE) { const float4 *rec = reinterpret_cast<const float4 *>(a.pn + j[u]); q[u] = rec[0]; nr[u] = rec[1]; }
-                else q[u] = a.pts[j[u]];
-            }
-        }
+        for (int u = 0; u < W; ++u) gather_point<KIND>(a, j[u], q[u], nr[u]);
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const int64_t t = t0 + u * stride;
@@ -203,11 +179,9 @@ __global__ void __launch_bounds__(256) k_rows(const LinArgs a, const RowArgs ra)
 }
 
 void launch_rows(int kind, int mode, dim3 grid, hipStream_t st, const LinArgs &a, const RowArgs &ra) {
-#define ROWS_CASE(K, M) if (kind == K && mode == M) { hipLaunchKernelGGL((k_rows<K, M>), grid, dim3(256), 0, st, a, ra); return; }
-#define ROWS_KIND(K) ROWS_CASE(K, 0) ROWS_CASE(K, 1) ROWS_CASE(K, 2)
-    ROWS_KIND(PCR_ICP) ROWS_KIND(PCR_PLANE) ROWS_KIND(PCR_VPLANE) ROWS_KIND(PCR_NDT)
-#undef ROWS_KIND
-#undef ROWS_CASE
+    with_const<4>(kind, [&](auto K) {
+        with_const<3>(mode, [&](auto M) { hipLaunchKernelGGL((k_rows<K(), M()>), grid, dim3(256), 0, st, a, ra); });
+    });
 }
 
 // off[0 .. n] = exclusive sums of flag[0 .. n] (flag[n] = 0, so off[n] is the number of gated-in points)

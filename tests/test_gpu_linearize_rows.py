@@ -207,6 +207,66 @@ def test_rows_against_sums(regs, rows, g2, name):
     assert_sums((Hq, gq, e2q), (H, gw, e2), (mags[0], mg, mags[2]), n, "icp quirk")
 
 
+# ----------------------------------------------------------------------------- 3b. terms against rows
+@pytest.mark.parametrize("name", NAMES)
+def test_terms_are_products_of_the_rows(regs, g2, name):
+    """The rows and the terms of a point come from one definition: calc_H_g_e2 with a one-hot weight (the fixed-order sum is
+    then fma(1, P, 0) plus zeros: the point's own terms, exactly) equals the products of linearize's row of that point, each
+    rounded once -- `==` throughout, which takes -0.0 for +0.0.  65 points: one full wave and a tail through the two-in-flight
+    loop.  Every one of g2's first 65 points has a correspondence, so point 40 of the copy is lifted 50 m off the street:
+    the gated-out point, all of whose 29 outputs are zero.  (Written without a GPU at hand: not yet run on hardware.)"""
+    import point_cloud_registration_amd as pcr
+    T = g2["T"]
+    src = np.ascontiguousarray(g2["source"][:65]).copy()
+    src[40, 2] += 50.0
+    reg = regs[name]
+    if name == "icp":                                   # the rows are J = [I, A], r: the flag-0 sums (Q1 changes g[3:] only)
+        reg = pcr.ICP(max_dist=float(g2["max_dist"]), compat_flags=0)
+        reg._set_target_handle(regs[name]._target)
+    try:
+        J, r, ws, idx = reg.linearize(T, src, return_index=True)
+        mask = idx >= 0
+        assert np.array_equal(np.flatnonzero(~mask), [40])
+        inside = np.flatnonzero(mask)
+        chosen = list(inside[np.round(np.linspace(0, len(inside) - 1, 16)).astype(int)]) + [40]
+        assert len(set(chosen)) == 17 and 0 in chosen and 64 in chosen
+        for c in chosen:
+            onehot = np.zeros(len(src))
+            onehot[c] = 1.0
+            H, g, e2 = reg.calc_H_g_e2(T, src, weights=onehot)
+            if not mask[c]:
+                assert not H.any() and not g.any() and e2 == 0.0 and reg.last_weight_sum == 0.0, (name, c)
+                continue
+            assert reg.last_weight_sum == 1.0 and np.array_equal(H, H.T)
+            if name in ("plane", "vplane"):
+                Jc, rc = J[c, 0], r[c, 0]
+                assert np.array_equal(H, Jc[:, None] * Jc[None, :]), (name, c)
+                assert np.array_equal(g, Jc * rc) and e2 == rc * rc, (name, c)
+                continue
+            A, d = J[c, :, 3:], r[c]
+            assert np.array_equal(J[c, :, :3], np.eye(3))
+            if name == "icp":
+                assert np.array_equal(H[:3, :3], np.eye(3)) and np.array_equal(H[:3, 3:], A), (name, c)
+                AtA = (A[0][:, None] * A[0][None, :] + A[1][:, None] * A[1][None, :]) + A[2][:, None] * A[2][None, :]
+                assert np.array_equal(H[3:, 3:], AtA), (name, c)
+                assert e2 == (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2] and np.array_equal(g[:3], d), (name, c)
+                continue
+            C = ws[c]
+            CA = (C[:, 0, None] * A[0][None, :] + C[:, 1, None] * A[1][None, :]) + C[:, 2, None] * A[2][None, :]
+            assert np.array_equal(H[:3, :3], C) and np.array_equal(H[:3, 3:], CA), (name, c)
+            # everything else: test_values' bound, 4 * 2^-53 * sum |products|, against acc_ndt's expressions over the row
+            Cd = (C[:, 0] * d[0] + C[:, 1] * d[1]) + C[:, 2] * d[2]
+            aC, aA, ad = np.abs(C), np.abs(A), np.abs(d)
+            AtCA = (A[0][:, None] * CA[0][None, :] + A[1][:, None] * CA[1][None, :]) + A[2][:, None] * CA[2][None, :]
+            want = (AtCA[np.triu_indices(3)], Cd, (A[0] * Cd[0] + A[1] * Cd[1]) + A[2] * Cd[2], (d[0] * Cd[0] + d[1] * Cd[1]) + d[2] * Cd[2])
+            mags = ((aA.T @ (aC @ aA))[np.triu_indices(3)], aC @ ad, aA.T @ (aC @ ad), ad @ (aC @ ad))
+            for got, w, m in zip((H[3:, 3:][np.triu_indices(3)], g[:3], g[3:], e2), want, mags):
+                assert np.all(np.abs(got - w) <= 4 * EPS * m), (name, c)
+    finally:
+        if name == "icp":
+            reg._target = None                          # (borrowed handle)
+
+
 # ----------------------------------------------------------------------------- 4. order and edges
 def bits_equal(a, b):
     return all(x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x.view(np.uint64) if x.dtype == np.float64 else x,
