@@ -354,6 +354,12 @@ PCR_API pcr_status pcr_align_batch(pcr_target *t, pcr_scan_batch *b, int kind, i
 PCR_API pcr_status pcr_nn_query(pcr_target *t, const float *q, int64_t m, float r_max, float *dist, int64_t *idx);
 PCR_API pcr_status pcr_nn_query_f64(pcr_target *t, const float *q, int64_t m, double r_max, double *dist, int64_t *idx);
 PCR_API pcr_status pcr_knn_query(pcr_target *t, const float *q, int64_t m, int k, float *dist, int64_t *idx);
+/* float64 QUERIES: a voxel target, or a point target with float64 coordinates (pcr_target_points_set_f64).  The query is
+ * never rounded: the result is the (float64 distance, index) minimum over the float64 coordinates, what a tree built on
+ * the float64 array returns -- also for queries far outside the data.  pcr_knn_query_f64: 1 <= k <= 64, rows nearest first,
+ * padded with dist = inf, idx = n when the target holds fewer than k.  PCR_ERR_INVALID for a float32-only point target. */
+PCR_API pcr_status pcr_nn_query_dd(pcr_target *t, const double *q, int64_t m, double r_max, double *dist, int64_t *idx);
+PCR_API pcr_status pcr_knn_query_f64(pcr_target *t, const double *q, int64_t m, int k, double *dist, int64_t *idx);
 
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the

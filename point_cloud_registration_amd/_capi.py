@@ -79,6 +79,8 @@ PROTOTYPES = {
     "pcr_nn_query": (C.c_int, [_vp, _f32p, C.c_int64, C.c_float, _f32p, _i64p]),
     "pcr_nn_query_f64": (C.c_int, [_vp, _f32p, C.c_int64, C.c_double, _f64p, _i64p]),
     "pcr_knn_query": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, _i64p]),
+    "pcr_nn_query_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _f64p, _i64p]),
+    "pcr_knn_query_f64": (C.c_int, [_vp, _f64p, C.c_int64, C.c_int, _f64p, _i64p]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -564,11 +566,25 @@ class Target:
                 "halo2": halo2.value, "halo2_records": nh2.value,
                 "pop_max": pmax.value, "pop_p99": p99.value, "heavy": bool(heavy.value)}
 
+    def searches_f64(self):
+        """True when the target answers in float64: a voxel target, or a point target that holds the float64 coordinates
+        of its points (``set_points_f64`` succeeded)."""
+        return bool(self.is_voxel or getattr(self, "has_f64", False))
+
     def nn_query(self, q, r_max=np.inf):
+        """Nearest neighbour of every query.  A float64 array on a target that answers in float64 is searched as it is
+        (pcr_nn_query_dd); every other array as float32, by the calls it has always taken."""
+        q = np.asarray(q)
+        if q.dtype == np.float64 and self.searches_f64():
+            q = np.ascontiguousarray(q)
+            m = q.shape[0]
+            dist, idx = np.empty(m, np.float64), np.empty(m, np.int64)
+            check(lib().pcr_nn_query_dd(self.handle, q, m, float(r_max), dist, idx))
+            return dist, idx
         q = np.ascontiguousarray(q, dtype=np.float32)
         m = q.shape[0]
         idx = np.empty(m, np.int64)
-        if self.is_voxel or getattr(self, "has_f64", False):
+        if self.searches_f64():
             dist = np.empty(m, np.float64)
             check(lib().pcr_nn_query_f64(self.handle, q, m, float(r_max), dist, idx))
         else:
@@ -577,6 +593,14 @@ class Target:
         return dist, idx
 
     def knn_query(self, q, k):
+        """k nearest neighbours, rows nearest first.  On a target that answers in float64 every query array is taken to
+        float64 (exact for float32) and the float64 coordinates are searched (pcr_knn_query_f64): float64 distances."""
+        if self.searches_f64():
+            q = np.ascontiguousarray(q, dtype=np.float64)
+            m = q.shape[0]
+            dist, idx = np.empty((m, k), np.float64), np.empty((m, k), np.int64)
+            check(lib().pcr_knn_query_f64(self.handle, q, m, int(k), dist, idx))
+            return dist, idx
         q = np.ascontiguousarray(q, dtype=np.float32)
         m = q.shape[0]
         dist = np.empty((m, k), np.float32)

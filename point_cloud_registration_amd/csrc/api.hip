@@ -935,3 +935,41 @@ extern "C" pcr_status pcr_nn_query(pcr_target *t, const float *q, int64_t m, flo
 extern "C" pcr_status pcr_nn_query_f64(pcr_target *t, const float *q, int64_t m, double r_max, double *dist, int64_t *idx) {
     return nn_query_common(t, q, m, r_max, dist, idx, 1);
 }
+
+// float64 queries (seam64.hip): k = 0 is pcr_nn_query_dd, else pcr_knn_query_f64 with that k
+static pcr_status query_f64_common(pcr_target *t, const double *q, int64_t m, double r_max, int k, double *dist, int64_t *idx) {
+    PCR_REQUIRE(t && (q || m == 0) && (dist || m == 0) && (idx || m == 0), "NULL argument");
+    PCR_REQUIRE(m >= 0, "negative query count");
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    const size_t per = k ? (size_t)k : 1;
+    DevBuf<double> d_q, d_dist;
+    DevBuf<int64_t> d_idx;
+    if (m > 0) {
+        PCR_TRY(upload<double>(ctx, q, (size_t)m * 3, &d_q));
+        if (d_dist.alloc((size_t)m * per) != hipSuccess || d_idx.alloc((size_t)m * per) != hipSuccess) {
+            pcr_set_error("hipMalloc failed for %lld query results", (long long)m);
+            return PCR_ERR_NOMEM;
+        }
+    }
+    // (m == 0 still checks the target and k)
+    PCR_TRY(k ? pcr_run_knn_f64(t, d_q.p, m, k, d_dist.p, d_idx.p) : pcr_run_nn_dd(t, d_q.p, m, r_max, d_dist.p, d_idx.p));
+    if (m == 0) return PCR_OK;
+    if (hipMemcpyAsync(dist, d_dist.p, 8 * (size_t)m * per, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(idx, d_idx.p, 8 * (size_t)m * per, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        pcr_set_error("copy-back of query results failed: %s", hipGetErrorString(hipGetLastError()));
+        return PCR_ERR_HIP;
+    }
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_nn_query_dd(pcr_target *t, const double *q, int64_t m, double r_max, double *dist, int64_t *idx) {
+    return query_f64_common(t, q, m, r_max, 0, dist, idx);
+}
+
+extern "C" pcr_status pcr_knn_query_f64(pcr_target *t, const double *q, int64_t m, int k, double *dist, int64_t *idx) {
+    if (k < 1 || k > 64) { pcr_set_error("k must be in [1, 64]"); return PCR_ERR_INVALID; }     // (before anything is sized by it)
+    return query_f64_common(t, q, m, 0.0, k, dist, idx);
+}

@@ -392,6 +392,10 @@ pcr_status pcr_run_linearize(pcr_target *t, pcr_scan *s, int kind, const double 
 pcr_status pcr_run_align(pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
                          double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 pcr_status pcr_run_nn(pcr_target *t, const float *d_q, int64_t m, double r_max, void *d_dist, int64_t *d_idx, int f64);
+// ---- seam64.hip: float64 QUERIES against a voxel target or a point target with float64 coordinates (device arrays; the
+// launches are enqueued on the context's stream, the caller synchronises)
+pcr_status pcr_run_nn_dd(pcr_target *t, const double *d_q, int64_t m, double r_max, double *d_dist, int64_t *d_idx);
+pcr_status pcr_run_knn_f64(pcr_target *t, const double *d_q, int64_t m, int k, double *d_dist, int64_t *d_idx);
 // the batched fused pass: item i = scans[i] at pose T[16 i ..].  align = false: one launch, out29[29 i ..]; align = true: the
 // device-resident Gauss-Newton loop of every item, one launch per iteration for the whole batch
 pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int kind, const double *T, bool align, int max_iter,
