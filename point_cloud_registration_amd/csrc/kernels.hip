@@ -413,7 +413,8 @@ __device__ __forceinline__ void fix_pending(const LinArgs &a, const PoseK &P, co
 // a 40 MB read of nn_j); here the chains of the few waves that have one overlap with the streaming of all the others,
 // and the search's registers are dead before the 32 accumulators come alive.  The order of the sums is unchanged.
 template <int KIND, int FIX>
-__global__ void __launch_bounds__(256, FIX ? 4 : 1) k_reduce_finalize(const LinArgs a, const FinArgs f) {   // (FIX: stay at <= 128 VGPRs)
+// (FIX and the point kinds stay at <= 128 VGPRs: the 4 blocks per CU of the reduce grid are then one resident generation)
+__global__ void __launch_bounds__(256, (FIX || KIND == PCR_ICP || KIND == PCR_PLANE) ? 4 : 1) k_reduce_finalize(const LinArgs a, const FinArgs f) {
     PoseK P;
     if (!load_pose<true>(a, P)) return;
     const TileIter it(a);
@@ -424,7 +425,9 @@ __global__ void __launch_bounds__(256, FIX ? 4 : 1) k_reduce_finalize(const LinA
     double acc[32];
 #pragma unroll
     for (int i = 0; i < 32; ++i) acc[i] = 0.0;
-    reduce_stream<KIND>(acc, a, P, it.base, it.end, it.stride);
+    // (<PLANE, FIX>, quirk Q6: one point less per trip -- five points' loads beside the sums do not fit its 128 registers
+    // without scratch; the order of the sums does not depend on W)
+    reduce_stream<KIND, (FIX && KIND == PCR_PLANE) ? PCR_RED_W - 1 : PCR_RED_W>(acc, a, P, it.base, it.end, it.stride);
     (void)ticket_fold_emit(acc, a, f);
     // (the Gauss-Newton step is NOT inlined here: its straight-line float64 code needs 136 VGPRs, which
     // would cap this streaming kernel at 3 blocks per CU; k_gn_update runs it as a 1-wave launch)

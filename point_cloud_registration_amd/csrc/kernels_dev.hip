@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(1024) k_finalize(const FinArgs f) {
 }
 
 template <int KIND>
-__global__ void __launch_bounds__(256) k_reduce(const LinArgs a) {
+__global__ void __launch_bounds__(256, (KIND == PCR_ICP || KIND == PCR_PLANE) ? 4 : 1) k_reduce(const LinArgs a) {   // (as k_reduce_finalize)
     PoseK P;
     if (!load_pose<true>(a, P)) return;
     double acc[32];

@@ -321,17 +321,26 @@ __device__ __forceinline__ void accumulate(double *acc, const LinArgs &a, const 
     }
 }
 
-// The streaming loop of the reduce kernels.  Point targets: the matched records of TWO scan points are
-// gathered before either is accumulated (two independent 16/32-byte gathers in flight per lane: at
-// 1e8 target points every gather is an HBM miss and the kernel is bound by misses in flight); the
-// points are still accumulated in index order, so the sums are bit-identical to the one-at-a-time loop.
+// The streaming loop of the reduce kernels.  Point targets: a lane handles PCR_RED_W scan points per trip (lane l of a
+// tile = point l of 64 consecutive ones, the tiles `stride` apart), and a trip is two round trips to memory, not one per
+// load: every load of a phase is issued before anything waits, and no branch lies between two loads of a phase.
+//   phase A  index and coordinates of all W points (the coordinates do not depend on the match).  A point past the end
+//            reads the lane's own first point instead of branching around the load, and is skipped in phase C.
+//   phase B  the W matched records (PLANE: 32 bytes as two loads of one sector, ICP: 16 bytes).  A point without a match
+//            gathers record 0 through a select on the index -- always readable -- and is skipped in phase C.
+//   phase C  residual, gate and accumulate in index order (u ascending): the same operands in the same order as the
+//            one-at-a-time loop, so the sums are bit-identical to it.
+// The compiler, left alone, sinks each load to its first use and guards it with the `no match` branch: the loop of
+// PCR_RED_W = 2 up to round 6 read as "two gathers in flight" and compiled to about six dependent round trips per trip
+// (docs/EXPERIMENTS.md).  reduce_phase() between the phases keeps the loads where they are written.
+// W = 5: a 1.06 M-point scan is 4.04 tiles per thread of the 1024-block grid, so no block makes a second trip
+// (k_reduce_finalize<PLANE, FIX> passes W = 4: five points spill under its 128 registers).
 // Round 5, measured and NOT kept: FOUR CONSECUTIVE scan points per lane (index and coordinates as 16-byte
 // loads, four gathers in flight) is slower -- 24.9 vs 20.8 us at 1.06 M points, 150 vs 117 / 351 vs 270 us at 1e8 -- because a
 // wave-level gather then covers every 4th of 256 points instead of 64 neighbours: ~3x the distinct lines per instruction, and
-// the L1 tag rate is what gathers pay with (docs/EXPERIMENTS.md).  PCR_RED_W selects how many scan points' gathers a lane has in
-// flight in the neighbour-preserving mapping below (lane l of a tile = point l of 64 consecutive ones).
+// the L1 tag rate is what gathers pay with (docs/EXPERIMENTS.md).  The mapping here keeps the neighbours together.
 #ifndef PCR_RED_W
-#define PCR_RED_W 2
+#define PCR_RED_W 5
 #endif
 #ifndef PCR_RED_NT
 #define PCR_RED_NT 0
@@ -344,30 +353,58 @@ __device__ __forceinline__ T stream_load(const T *p) {
     return *p;
 #endif
 }
-
+// the matched record of slot u of a trip, for a lane that may have nothing to gather there (`use` false: record 0)
 template <int KIND>
+__device__ __forceinline__ void gather_slot(const LinArgs &a, uint32_t j, bool use, float4 &q, float4 &nn) {
+    nn = make_float4(0, 0, 0, 0);
+    load_point<KIND>(a, use ? j : 0u, q, nn);
+}
+// phase boundary: no load moves across it, in the optimizer (memory clobber) or in the instruction scheduler
+__device__ __forceinline__ void reduce_phase() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+// ... and nothing computed from v moves in front of it (a compare of a loaded index against PCR_NONE, hoisted to right
+// behind its load, puts a wait between the loads of phase A)
+__device__ __forceinline__ void reduce_pin(uint32_t &v) { asm volatile("" : "+v"(v)); }
+
+template <int KIND, int W = PCR_RED_W>
 __device__ __forceinline__ void reduce_stream(double *acc, const LinArgs &a, const PoseK &P, int64_t base, int64_t end,
                                               int64_t stride) {
     if (KIND == PCR_ICP || KIND == PCR_PLANE) {
-        constexpr int W = PCR_RED_W;
         for (int64_t i = base; i < end; i += W * stride) {
             uint32_t j[W];
+            float x[W], y[W], z[W];
             float4 q[W], nr[W];
+            bool use[W];
+            int64_t is[W];
 #pragma unroll
             for (int u = 0; u < W; ++u) {
                 const int64_t iu = i + u * stride;
-                j[u] = iu < end ? stream_load(a.nn_j + iu) : PCR_NONE;
+                use[u] = iu < end;
+                is[u] = use[u] ? iu : i;
+                j[u] = stream_load(a.nn_j + is[u]);
             }
-#pragma unroll
-            for (int u = 0; u < W; ++u) gather_point<KIND>(a, j[u], q[u], nr[u]);
+            // (behind the indices: loads return in order, so phase B waits for the W indices only)
 #pragma unroll
             for (int u = 0; u < W; ++u) {
-                if (j[u] == PCR_NONE) continue;
-                const int64_t iu = i + u * stride;
-                const float x = stream_load(a.sx + iu), y = stream_load(a.sy + iu), z = stream_load(a.sz + iu);
+                x[u] = stream_load(a.sx + is[u]); y[u] = stream_load(a.sy + is[u]); z[u] = stream_load(a.sz + is[u]);
+            }
+            reduce_phase();
+#pragma unroll
+            for (int u = 0; u < W; ++u) reduce_pin(j[u]);
+#pragma unroll
+            for (int u = 0; u < W; ++u) {
+                use[u] = use[u] && j[u] != PCR_NONE;
+                gather_slot<KIND>(a, j[u], use[u], q[u], nr[u]);
+            }
+            reduce_phase();
+#pragma unroll
+            for (int u = 0; u < W; ++u) {
+                if (!use[u]) continue;
                 float tx, ty, tz;
-                xform(P, x, y, z, tx, ty, tz);
-                accumulate_point<KIND, true>(acc, a, P, q[u], nr[u], x, y, z, tx, ty, tz);
+                xform(P, x[u], y[u], z[u], tx, ty, tz);
+                accumulate_point<KIND, true>(acc, a, P, q[u], nr[u], x[u], y[u], z[u], tx, ty, tz);
             }
         }
     } else {
