@@ -308,6 +308,47 @@ PCR_API pcr_status pcr_align(pcr_target *t, pcr_scan *s, int kind, const double 
                              int max_iter, double tol, double max_dist, unsigned flags,
                              double T_out[16], int *iterations, double *trace_or_null);
 
+/* ---- Generalized ICP: distribution to distribution ------------------------------------------
+ * No reference counterpart (the reference only borrows small_gicp's tree, kdtree.py:26-57).  Every point of the target AND of
+ * the scan carries a covariance, float32 (N, 6) = xx xy xz yy yz zz, supplied by the caller or estimated on the GPU; a
+ * correspondence (p, Cp) -> (q, Cq) at pose T = (R, t) is weighed with M = (Cq + R Cp R^T)^-1:
+ *   H = sum J^T M J,  g = sum J^T M d,  e2 = sum d^T M d,  J = [I, -R skew(p)],  d = R p + t - q,  count = matches kept.
+ * Correspondence and gate are exactly PCR_ICP's: float32 transform, exact 1-NN over the float32 target, kept iff the float32
+ * distance is < max_dist; d is formed in float32, then widened.  M is float64: R the float64 rotation of T, the inverse by
+ * the closed form of the voxel targets (adjugate / determinant, voxel.py:69-102) INCLUDING its rule for det == 0 -- the
+ * adjugate is divided by 1e6 instead, so a degenerate pair (e.g. two PCR_COV_RAW covariances of one-point neighbourhoods)
+ * contributes (almost) nothing where a plain inverse would give Inf / NaN.  Conventions are PCR_NDT's: translation Jacobian I
+ * with a right-multiplicative update (quirk Q2), dM/dT ignored (as every GICP implementation does), so the Gauss-Newton step
+ * of pcr_align drives the loop unchanged (quirks Q3, Q4, Q7).
+ * pcr_*_estimate_covariances: the k nearest neighbours of every point within its OWN cloud, the point itself included
+ *   (1 <= k <= 64, else PCR_ERR_INVALID; a cloud of fewer than k points uses the neighbours found), two-pass float64
+ *   covariance with divisor = neighbours found, then
+ *     PCR_COV_PLANE  C = I - (1 - eps) n n^T, n = eigenvector of the smallest eigenvalue: the usual "eigenvalues -> (eps, 1, 1)"
+ *                    regularisation, which depends on the normal only; 0 < eps <= 1
+ *     PCR_COV_RAW    the covariance itself (eps ignored).
+ *   A scan builds a temporary index over its own device points for this and releases it before returning.
+ * Arrays that cross the boundary (set, get, cov_out) are in the CALLER's order; a scan must know that order for them
+ *   (PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT, else PCR_ERR_INVALID).  Estimating without cov_out works on any scan.
+ *   set: non-finite values give PCR_ERR_INVALID.  get: PCR_ERR_NO_TARGET when there are none.
+ * pcr_gicp_linearize: out[29] as pcr_linearize; PCR_ERR_NO_TARGET when either side has no covariances.  A full search into a
+ *   match buffer of the call (the scan's reuse state is left alone, as for pcr_linearize_rows), then a reduce launch that
+ *   writes one row of sums per block and a one-block fold that adds the rows in order: no atomics, and the grid depends on
+ *   the scan size and the device only -- two calls return the same bits.  An empty scan gives zeros without a launch.
+ * pcr_gicp_align: the host-driven loop of pcr_align(PCR_FLAG_HOST_LOOP) over pcr_gicp_linearize: same step, same trace rows
+ *   (16 + 29 doubles), PCR_ERR_SINGULAR as there.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group).                        */
+enum { PCR_COV_PLANE = 0, PCR_COV_RAW = 1 };
+PCR_API pcr_status pcr_target_estimate_covariances(pcr_target *t, int k, int mode, double eps, float *cov_out_or_null);
+PCR_API pcr_status pcr_target_set_covariances(pcr_target *t, const float *cov6);
+PCR_API pcr_status pcr_target_get_covariances(pcr_target *t, float *cov6);
+PCR_API pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode, double eps, float *cov_out_or_null);
+PCR_API pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6);
+PCR_API pcr_status pcr_scan_get_covariances(pcr_scan *s, float *cov6);
+PCR_API pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags,
+                                      double out[29]);
+PCR_API pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                  unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

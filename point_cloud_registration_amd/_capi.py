@@ -30,6 +30,7 @@ FLAG_KEEP_ORDER = 32         # pcr_scan_create: a sorted scan remembers the call
 K_LINEARIZE, K_FINALIZE, K_NN, K_REDUCE, K_ALLREDUCE, K_CERTIFY, K_COUNT = 0, 1, 2, 3, 4, 5, 6
 KERNEL_NAMES = ("linearize", "finalize", "nn", "reduce", "allreduce", "certify")
 NN_FULL, NN_TRACK, NN_LIST = 0, 1, 2      # what the search of a pass did (certified reuse, include/pcr.h)
+COV_PLANE, COV_RAW = 0, 1                 # GICP covariance modes (include/pcr.h)
 
 _lib = None
 _torch_lib_dir = None           # set when torch's bundled HIP runtime was pre-loaded (see below)
@@ -117,6 +118,15 @@ PROTOTYPES = {
     "pcr_linearize_weighted": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, _f64p, _f64p]),
     "pcr_scan_coreset": (C.c_int, [_vp, _vp, C.c_int, _f64p, C.c_double, C.c_uint, C.c_int, C.c_int64, _i64p, _f64p,
                                    C.POINTER(C.c_int64)]),
+    # Generalized ICP: per-point covariances and the distribution-to-distribution pass (include/pcr.h)
+    "pcr_target_estimate_covariances": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "pcr_target_set_covariances": (C.c_int, [_vp, _f32p]),
+    "pcr_target_get_covariances": (C.c_int, [_vp, _f32p]),
+    "pcr_scan_estimate_covariances": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "pcr_scan_set_covariances": (C.c_int, [_vp, _f32p]),
+    "pcr_scan_get_covariances": (C.c_int, [_vp, _f32p]),
+    "pcr_gicp_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
+    "pcr_gicp_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
     # batches: many scans / start poses against one target in one launch (include/pcr.h)
     "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
     "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -540,6 +550,23 @@ class Target:
         check(lib().pcr_target_get_normals(self.handle, out))
         return out
 
+    # -- GICP covariances: float32 (N, 6) = xx xy xz yy yz zz, in the caller's order (include/pcr.h)
+    def estimate_covariances(self, k=10, mode=COV_PLANE, eps=1e-3, want=True):
+        out = np.empty((self.size(), 6), np.float32) if want else None
+        check(lib().pcr_target_estimate_covariances(self.handle, int(k), int(mode), float(eps), _ptr(out)))
+        return out
+
+    def set_covariances(self, cov):
+        cov = cov6(cov)
+        if cov.shape != (self.size(), 6):
+            raise ValueError("covariances must have shape (N, 6) or (N, 3, 3)")
+        check(lib().pcr_target_set_covariances(self.handle, cov))
+
+    def get_covariances(self):
+        out = np.empty((self.size(), 6), np.float32)
+        check(lib().pcr_target_get_covariances(self.handle, out))
+        return out
+
     def voxel_stats(self, names=("mean", "cov", "norm", "icov", "counts", "keys")):
         n = self.size()
         bufs = {"mean": np.empty((n, 3)), "cov": np.empty((n, 3, 3)), "norm": np.empty((n, 3)),
@@ -666,6 +693,23 @@ class Scan:
         m = out.astype(np.int64)
         m[out == 0xFFFFFFFF] = -1
         return m
+
+    # -- GICP covariances: float32 (N, 6) = xx xy xz yy yz zz, in the caller's order (include/pcr.h)
+    def estimate_covariances(self, k=10, mode=COV_PLANE, eps=1e-3, want=True):
+        out = np.empty((self.n, 6), np.float32) if want else None
+        check(lib().pcr_scan_estimate_covariances(self.handle, int(k), int(mode), float(eps), _ptr(out)))
+        return out
+
+    def set_covariances(self, cov):
+        cov = cov6(cov)
+        if cov.shape != (self.n, 6):
+            raise ValueError("covariances must have shape (N, 6) or (N, 3, 3)")
+        check(lib().pcr_scan_set_covariances(self.handle, cov))
+
+    def get_covariances(self):
+        out = np.empty((self.n, 6), np.float32)
+        check(lib().pcr_scan_get_covariances(self.handle, out))
+        return out
 
     def member(self, i):
         """Member i's shard of a group scan (borrowed: destroyed with the group scan; ``ctx`` is the member's context).  A plain
@@ -845,6 +889,36 @@ def scan_coreset(target, scan, kind, T, max_dist, k, n_target, flags=FLAG_ICP_RR
     check(lib().pcr_scan_coreset(target.handle, scan.handle, int(kind), T, float(max_dist), int(flags), int(k), int(n_target), idx, w,
                                  C.byref(n_out)))
     return idx[:n_out.value].copy(), w[:n_out.value].copy()
+
+
+def cov6(cov):
+    """Covariances as C-contiguous float32 (N, 6) = xx xy xz yy yz zz; (N, 3, 3) input contributes its upper triangle."""
+    cov = np.asarray(cov)
+    if cov.ndim == 3 and cov.shape[1:] == (3, 3):
+        cov = cov[:, (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)]
+    return np.ascontiguousarray(cov, dtype=np.float32)
+
+
+def gicp_linearize(target, scan, T, max_dist, flags=0):
+    """pcr_gicp_linearize -> the 29 sums of one GICP pass (see include/pcr.h)."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty(29)
+    check(lib().pcr_gicp_linearize(target.handle, scan.handle, T, float(max_dist), int(flags), out))
+    return out
+
+
+def gicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
+    """pcr_gicp_align: the host-driven Gauss-Newton loop over pcr_gicp_linearize, behind the boundary."""
+    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
+    T = np.zeros(16)
+    iters = C.c_int(0)
+    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
+    check(lib().pcr_gicp_align(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), int(flags), T,
+                               C.byref(iters), _ptr(trace)))
+    T = T.reshape(4, 4)
+    if want_trace:
+        return T, iters.value, trace[:iters.value]
+    return T, iters.value
 
 
 _linearize_fast = None

@@ -453,7 +453,7 @@ static void target_free(pcr_target *t) { pcr_target_release(t); }
 void pcr_target_release(pcr_target *t) {
     if (!t) return;
     target_free(t->filter);
-    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->lbox_h2, t->gbox_h2, t->cs_h, t->pts_h, t->j_h, t->cs_h2, t->pts_h2, t->j_h2, t->pts, t->pn, t->pts64, t->means, t->vnorm, t->vicov,
+    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->lbox_h2, t->gbox_h2, t->cs_h, t->pts_h, t->j_h, t->cs_h2, t->pts_h2, t->j_h2, t->pts, t->pn, t->gcov, t->pts64, t->means, t->vnorm, t->vicov,
                     t->st_mean, t->st_cov, t->st_norm, t->st_icov, t->st_counts, t->st_keys};
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     for (void *p : ptrs) pcr_persist_free(t->ctx, p);
@@ -773,15 +773,15 @@ extern "C" pcr_status pcr_scan_coreset(pcr_target *t, pcr_scan *s, int kind, con
 // ---- Gauss-Newton driver behind the boundary (registration.py:71-113) -------------------------
 // Default: the device-resident loop (pass.hip: pcr_run_align).  PCR_FLAG_HOST_LOOP keeps the
 // host-driven form (one pcr_linearize + host solve per iteration), the same arithmetic from gn_math.h.
-static pcr_status align_host_loop(pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
-                                  double max_dist, unsigned flags, double T_out[16], int *iterations,
-                                  double *trace_or_null) {
+// `pass`: what one iteration evaluates (pcr_run_linearize; gicp.hip passes its own)
+pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
+                               double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     double T[16];
     memcpy(T, T_init, sizeof T);
     int it = 0;
     for (; it < max_iter; ++it) {
         double o[29];
-        PCR_TRY(pcr_run_linearize(t, s, kind, T, max_dist, flags, o));
+        PCR_TRY(pass(t, s, kind, T, max_dist, flags, o));
         if (trace_or_null) {
             memcpy(trace_or_null + (size_t)it * 45, T, 16 * sizeof(double));
             memcpy(trace_or_null + (size_t)it * 45 + 16, o, 29 * sizeof(double));
@@ -812,7 +812,7 @@ extern "C" pcr_status pcr_align(pcr_target *t, pcr_scan *s, int kind, const doub
     const bool use_comm = t->ctx->comm != nullptr && !(flags & PCR_FLAG_LOCAL_ONLY);
     const bool small_host = !(flags & PCR_FLAG_DEVICE_LOOP) && !use_comm && pcr_pass_is_fused(t->ctx, s);
     if ((flags & PCR_FLAG_HOST_LOOP) || t->ctx->reuse == 2 || small_host)
-        return align_host_loop(t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+        return pcr_align_host_loop(pcr_run_linearize, t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
     return pcr_run_align(t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }
 

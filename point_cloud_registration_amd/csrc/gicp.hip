@@ -1,0 +1,454 @@
+// Generalized ICP (distribution to distribution; Segal, Haehnel, Thrun 2009): per-point covariances and the pass that weighs
+// every correspondence with M = (Cq + R Cp R^T)^-1.  Built BESIDE the hot path: its own kernels, its own entry points, no new
+// kind in the templated pass kernels (kernels.hip / pass_device.h are included, not edited).
+//
+//   k_gicp_cov<REG>   sibling of k_knn_normals<REG> (knn_normals.hip): the k nearest neighbours of every point of an indexed
+//                     cloud within that cloud (the point itself included), two-pass float64 covariance with divisor =
+//                     neighbours found, then PCR_COV_PLANE: C = I - (1 - eps) n n^T with n = smallest_eigvec3(cov) -- the
+//                     usual "eigenvalues -> (eps, 1, 1)", which depends on the normal only -- or PCR_COV_RAW: cov itself.
+//                     Six floats (xx xy xz yy yz zz) per point, written through pt_orig: the INPUT order of the indexed cloud.
+//   k_gicp_reduce     sits where k_rows sits: behind a full search (pass.hip: pcr_rows_search) into a match buffer of the call.
+//                     Streams nn_j, the scan SoA and the scan covariances in the scan's device order (lane = consecutive
+//                     point), GICP_W points per lane in flight: indices, coordinates and scan covariances of all of them, then
+//                     all gathers, then the arithmetic.  The correspondence is ICP's (xform, the matched PtF,
+//                     residual_f32<true>), the sums are acc_ndt's with M6 from icov_closed_form: nothing is restated here.
+//                     Fold: wave shuffles in a fixed order, LDS across the waves in wave order, ONE row of 32 doubles per
+//                     block with plain stores (block_store_partials).  No tickets, no atomics, no in-launch hand-off.
+//   k_gicp_fold       one block: thread e < 29 adds rows 0 .. nb-1 in order.  The kernel boundary is the only ordering
+//                     between the two launches; the grid depends on n and the device only, so two calls return the same bits.
+//
+// Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
+// correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line, through
+// a select on the index like reduce_stream's gather_slot: no branch between the gathers of a phase); its first 16 bytes are the
+// index's own PtF, so residual_f32<true> sees exactly what gather_point<PCR_ICP> would have handed it.
+// det == 0 of Cq + R Cp R^T (e.g. two RAW covariances of single-point neighbourhoods): icov_closed_form's rule applies, the
+// adjugate is divided by 1e6 instead -- such a correspondence contributes (almost) nothing instead of Inf / NaN.
+#include <math.h>
+#include <string.h>
+
+#include "eigen3.h"
+#include "knn_device.h"
+#include "pass_device.h"
+
+extern __shared__ __attribute__((aligned(16))) char gicp_smem[];
+
+// ---- covariances ------------------------------------------------------------------------------------------------------
+template <typename LIST>
+__device__ __forceinline__ void gicp_cov_finish(const PtF *pts, const PtF me, int mode, double eps, float *cov, LIST &L) {
+    // two-pass float64 covariance over the neighbours found (knn_normals.hip: the compat == 0 branch of knn_normals_finish)
+    double mx = 0, my = 0, mz = 0;
+    L.for_each([&](int, float, uint32_t js) { const PtF p = pts[js]; mx += p.x; my += p.y; mz += p.z; });
+    const double kd = (double)(L.cnt > 0 ? L.cnt : 1);
+    mx /= kd; my /= kd; mz /= kd;
+    double c[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) c[a] = 0;
+    L.for_each([&](int, float, uint32_t js) {
+        const PtF p = pts[js];
+        const double dx = p.x - mx, dy = p.y - my, dz = p.z - mz;
+        c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
+    });
+#pragma unroll
+    for (int a = 0; a < 6; ++a) c[a] /= kd;
+    if (mode == PCR_COV_PLANE) {
+        double n[3];
+        smallest_eigvec3(c, n);
+        const double s = 1.0 - eps;
+        c[0] = 1.0 - s * n[0] * n[0]; c[1] = -s * n[0] * n[1]; c[2] = -s * n[0] * n[2];
+        c[3] = 1.0 - s * n[1] * n[1]; c[4] = -s * n[1] * n[2]; c[5] = 1.0 - s * n[2] * n[2];
+    }
+    float *dst = cov + 6 * (size_t)pt_orig(me);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) dst[a] = (float)c[a];
+}
+
+// REG = 1: the collect path (k <= 16); 0: the LDS list -- launch shape and LDS sizing of k_knn_normals
+template <int REG>
+__global__ void __launch_bounds__(KNN_BLOCK) k_gicp_cov(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, int k, int mode,
+                                                        double eps, float *cov) {
+    const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const PtF me = pts[i];
+    if (REG) {
+        KnnOut L;
+        L.init(gicp_smem);
+        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
+        gicp_cov_finish(pts, me, mode, eps, cov, L);
+    } else {
+        KnnList L;
+        L.k = k; L.cnt = 0; L.lane = threadIdx.x;
+        L.d = (float *)gicp_smem;
+        L.j = (uint32_t *)(gicp_smem + sizeof(float) * k * KNN_BLOCK);
+        L.pts = pts;
+        knn_search(g, pts, cs, me.x, me.y, me.z, L);
+        gicp_cov_finish(pts, me, mode, eps, cov, L);
+    }
+}
+
+// the covariances of the n points behind the index (g, pts, cs), into cov[6 n] in the index's INPUT order
+static pcr_status gicp_estimate(pcr_context *ctx, const Geom<float> &g, const PtF *pts, const uint32_t *cs, int64_t n, int k, int mode,
+                                double eps, float *cov) {
+    if (n <= 0) return PCR_OK;
+    const dim3 grid((unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK));
+    if (k <= KNN_REG_K)
+        hipLaunchKernelGGL(k_gicp_cov<1>, grid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream, g, pts, cs, n, k, mode, eps, cov);
+    else
+        hipLaunchKernelGGL(k_gicp_cov<0>, grid, dim3(KNN_BLOCK), 2 * sizeof(float) * (size_t)k * KNN_BLOCK, ctx->stream, g, pts, cs, n, k,
+                           mode, eps, cov);
+    HIP_TRY(hipGetLastError());
+    return PCR_OK;
+}
+
+// the GICP gather record of a point target, cell-sorted, one 64-byte line: the index's PtF (xyz + original index), then the
+// covariance xx xy xz yy | yz zz, then padding
+struct __attribute__((aligned(64))) GicpRec {
+    float4 p, c0, c1, pad;
+};
+static_assert(sizeof(GicpRec) == 64, "one line per correspondence");
+
+// target: caller order (6 floats) <-> cell-sorted records
+__global__ void __launch_bounds__(256) k_gicp_tcov_in(const float *__restrict__ in, int64_t n, const PtF *__restrict__ pts, GicpRec *out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const PtF p = pts[j];
+    const float *c = in + 6 * (size_t)pt_orig(p);
+    GicpRec r;
+    r.p = p;
+    r.c0 = make_float4(c[0], c[1], c[2], c[3]);
+    r.c1 = make_float4(c[4], c[5], 0.f, 0.f);
+    r.pad = make_float4(0.f, 0.f, 0.f, 0.f);
+    out[j] = r;
+}
+__global__ void __launch_bounds__(256) k_gicp_tcov_out(const GicpRec *__restrict__ in, int64_t n, float *out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float4 p = in[j].p, a = in[j].c0, b = in[j].c1;
+    float *c = out + 6 * (size_t)pt_orig(p);
+    c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y;
+}
+// scan: caller order <-> device order through pcr_scan::order (NULL: the same order); TO_DEVICE: dev[i] = caller[order[i]]
+template <bool TO_DEVICE>
+__global__ void __launch_bounds__(256) k_gicp_scov_perm(const float *__restrict__ in, int64_t n, const uint32_t *__restrict__ order, float *out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const size_t c = order ? (size_t)order[i] : (size_t)i;
+    const float *src = in + 6 * (TO_DEVICE ? c : (size_t)i);
+    float *dst = out + 6 * (TO_DEVICE ? (size_t)i : c);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) dst[a] = src[a];
+}
+__global__ void __launch_bounds__(256) k_gicp_soa_to_aos(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                                         int64_t n, float *xyz) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    xyz[3 * i] = x[i]; xyz[3 * i + 1] = y[i]; xyz[3 * i + 2] = z[i];
+}
+
+static dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+static pcr_status check_cov_args(int k, int mode, double eps) {
+    if (k < 1 || k > KNN_MAX_K) { pcr_set_error("k must be in [1, %d]", KNN_MAX_K); return PCR_ERR_INVALID; }
+    PCR_REQUIRE(mode == PCR_COV_PLANE || mode == PCR_COV_RAW, "mode must be PCR_COV_PLANE or PCR_COV_RAW");
+    PCR_REQUIRE(mode == PCR_COV_RAW || (eps > 0.0 && eps <= 1.0), "eps must be in (0, 1]");
+    return PCR_OK;
+}
+static pcr_status check_finite(const float *v, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (!isfinite(v[i])) { pcr_set_error("invalid argument: covariances must be finite"); return PCR_ERR_INVALID; }
+    return PCR_OK;
+}
+static bool scan_knows_order(const pcr_scan *s) { return !s->sorted || s->order != nullptr; }
+#define GICP_NEED_ORDER "the scan must know the caller's order: PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT"
+
+static pcr_status target_cov_alloc(pcr_target *t) {
+    if (!t->gcov) HIP_TRY(pcr_persist_alloc((void **)&t->gcov, sizeof(GicpRec) * (size_t)(t->n ? t->n : 1)));
+    return PCR_OK;
+}
+static pcr_status scan_cov_alloc(pcr_scan *s) {
+    if (!s->cov) HIP_TRY(pcr_scan_alloc(s, (void **)&s->cov, 24 * (size_t)(s->n ? s->n : 1)));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_estimate_covariances(pcr_target *t, int k, int mode, double eps, float *cov_out_or_null) {
+    PCR_REQUIRE(t, "NULL argument");
+    PCR_REQUIRE(!t->is_voxel, "covariances belong to point targets");
+    PCR_TRY(check_cov_args(k, mode, eps));
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    PCR_TRY(target_cov_alloc(t));
+    if (t->n == 0) return PCR_OK;
+    DevBuf<float> d_cov;                             // caller order
+    HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
+    PCR_TRY(gicp_estimate(ctx, t->gf, t->pts, t->cell_start, t->n, k, mode, eps, d_cov.p));
+    hipLaunchKernelGGL(k_gicp_tcov_in, grid256(t->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
+    HIP_TRY(hipGetLastError());
+    if (cov_out_or_null) HIP_TRY(hipMemcpyAsync(cov_out_or_null, d_cov.p, 24 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_set_covariances(pcr_target *t, const float *cov6) {
+    PCR_REQUIRE(t && (cov6 || t->n == 0), "NULL argument");
+    PCR_REQUIRE(!t->is_voxel, "covariances belong to point targets");
+    PCR_TRY(check_finite(cov6, 6 * (size_t)t->n));
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    PCR_TRY(target_cov_alloc(t));
+    if (t->n == 0) return PCR_OK;
+    DevBuf<float> d_cov;
+    HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
+    HIP_TRY(hipMemcpyAsync(d_cov.p, cov6, 24 * (size_t)t->n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_gicp_tcov_in, grid256(t->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_get_covariances(pcr_target *t, float *cov6) {
+    PCR_REQUIRE(t && (cov6 || t->n == 0), "NULL argument");
+    if (t->is_voxel || !t->gcov) { pcr_set_error("target has no per-point covariances"); return PCR_ERR_NO_TARGET; }
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (t->n == 0) return PCR_OK;
+    CtxScope scope(ctx);
+    DevBuf<float> d_cov;
+    HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
+    hipLaunchKernelGGL(k_gicp_tcov_out, grid256(t->n), dim3(256), 0, ctx->stream, (const GicpRec *)t->gcov, t->n, d_cov.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cov6, d_cov.p, 24 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+// device-order covariances of a scan -> the caller's array
+static pcr_status scan_cov_read(pcr_scan *s, float *cov6) {
+    pcr_context *ctx = s->ctx;
+    if (s->n == 0) return PCR_OK;
+    DevBuf<float> d_cov;
+    HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
+    hipLaunchKernelGGL(k_gicp_scov_perm<false>, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)s->cov, s->n, (const uint32_t *)s->order,
+                       d_cov.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cov6, d_cov.p, 24 * (size_t)s->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+// a temporary point index over a scan's own device points, released on scope exit (its blocks go back to the context's cache)
+struct TmpIndex {
+    pcr_target *t = nullptr;
+    ~TmpIndex() { pcr_target_release(t); }
+};
+
+extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode, double eps, float *cov_out_or_null) {
+    PCR_REQUIRE(s, "NULL argument");
+    PCR_TRY(check_cov_args(k, mode, eps));
+    PCR_REQUIRE(!cov_out_or_null || scan_knows_order(s), GICP_NEED_ORDER);
+    pcr_context *ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    if (s->n == 0) return scan_cov_alloc(s);
+    // into the scan's array when it has one, else into a block the scan takes over only once the estimate is complete: a
+    // failure on the way must not leave a scan that "has covariances" holding uninitialised ones
+    float *dst = s->cov;
+    bool fresh = false;
+    if (!dst) {
+        HIP_TRY(pcr_scan_alloc(s, (void **)&dst, 24 * (size_t)s->n));
+        fresh = true;
+    }
+    struct Undo {
+        pcr_scan *s; float *p; bool armed;
+        ~Undo() { if (armed) { pcr_scan_free(s, p); } }
+    } undo{s, dst, fresh};
+    if (!fresh) { s->cov = nullptr; undo.armed = true; }      // (re-estimating: a failure leaves the scan without covariances)
+    {
+        DevBuf<float> xyz;
+        HIP_TRY(xyz.alloc(3 * (size_t)s->n));
+        hipLaunchKernelGGL(k_gicp_soa_to_aos, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)s->x, (const float *)s->y, (const float *)s->z,
+                           s->n, xyz.p);
+        HIP_TRY(hipGetLastError());
+        TmpIndex idx;
+        idx.t = new pcr_target();
+        idx.t->ctx = ctx; idx.t->n = s->n;
+        // (no extended lists: the k-NN search reads cell_start and the cell-sorted points only)
+        PCR_TRY(pcr_build_point_grid(ctx, xyz.p, s->n, 0.f, idx.t, false, 0.0));
+        // the index's input order is the scan's device order: pt_orig lands every point's six floats in the scan's array directly
+        PCR_TRY(gicp_estimate(ctx, idx.t->gf, idx.t->pts, idx.t->cell_start, s->n, k, mode, eps, dst));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    undo.armed = false;
+    s->cov = dst;
+    if (cov_out_or_null) return scan_cov_read(s, cov_out_or_null);
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
+    PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
+    PCR_REQUIRE(scan_knows_order(s), GICP_NEED_ORDER);
+    PCR_TRY(check_finite(cov6, 6 * (size_t)s->n));
+    pcr_context *ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    PCR_TRY(scan_cov_alloc(s));
+    if (s->n == 0) return PCR_OK;
+    DevBuf<float> d_cov;
+    HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
+    HIP_TRY(hipMemcpyAsync(d_cov.p, cov6, 24 * (size_t)s->n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_gicp_scov_perm<true>, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, s->n, (const uint32_t *)s->order,
+                       s->cov);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_scan_get_covariances(pcr_scan *s, float *cov6) {
+    PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
+    if (!s->cov) { pcr_set_error("scan has no per-point covariances"); return PCR_ERR_NO_TARGET; }
+    PCR_REQUIRE(scan_knows_order(s), GICP_NEED_ORDER);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    CtxScope scope(s->ctx);
+    return scan_cov_read(s, cov6);
+}
+
+// ---- the pass ---------------------------------------------------------------------------------------------------------
+struct GicpArgs {
+    const float *scov;       // scan covariances, device order, 6 floats per point
+    const GicpRec *trec;     // target records, cell-sorted: point + covariance in one line
+    double *rows;            // [gridDim.x][32]
+};
+
+// points per lane in flight.  3: the per-correspondence arithmetic (R Cp R^T, the closed-form inverse, acc_ndt) needs its
+// registers beside 32 float64 sums; see docs/EXPERIMENTS.md for the register figures
+#ifndef GICP_W
+#define GICP_W 3
+#endif
+
+// M6 = (Cq + R Cp R^T)^-1 as xx xy xz yy yz zz, float64
+__device__ __forceinline__ void gicp_weight(const PoseK &P, const float cp[6], const float cq[6], double m6[6]) {
+    const double Cp[3][3] = {{cp[0], cp[1], cp[2]}, {cp[1], cp[3], cp[4]}, {cp[2], cp[4], cp[5]}};
+    double B[3][3];                                  // R Cp
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i][j] = (P.R[3 * i] * Cp[0][j] + P.R[3 * i + 1] * Cp[1][j]) + P.R[3 * i + 2] * Cp[2][j];
+    double S[3][3];                                  // (R Cp) R^T, upper triangle mirrored: symmetric by construction
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            S[i][j] = (B[i][0] * P.R[3 * j] + B[i][1] * P.R[3 * j + 1]) + B[i][2] * P.R[3 * j + 2];
+            S[j][i] = S[i][j];
+        }
+    const double m[9] = {(double)cq[0] + S[0][0], (double)cq[1] + S[0][1], (double)cq[2] + S[0][2],
+                         (double)cq[1] + S[1][0], (double)cq[3] + S[1][1], (double)cq[4] + S[1][2],
+                         (double)cq[2] + S[2][0], (double)cq[4] + S[2][1], (double)cq[5] + S[2][2]};
+    double o[9];
+    icov_closed_form(m, o);
+    m6[0] = o[0]; m6[1] = o[1]; m6[2] = o[2]; m6[3] = o[4]; m6[4] = o[5]; m6[5] = o[8];
+}
+
+__global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) {
+    const PoseK &P = a.hp;                           // host-driven: the pose came by value
+    constexpr int W = GICP_W;
+    double acc[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < a.n; t0 += W * stride) {
+        uint32_t j[W];
+        float x[W], y[W], z[W];
+        float2 cp[W][3];
+        float4 q[W], cq0[W], cq1[W];
+        bool use[W];
+        // phase A: index, coordinates and covariance of all W points (a point past the end reads the lane's first point)
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            const int64_t t = t0 + u * stride;
+            use[u] = t < a.n;
+            const int64_t i = use[u] ? t : t0;
+            j[u] = a.nn_j[i];
+            x[u] = a.sx[i]; y[u] = a.sy[i]; z[u] = a.sz[i];
+            const float2 *c = reinterpret_cast<const float2 *>(ga.scov + 6 * i);
+            cp[u][0] = c[0]; cp[u][1] = c[1]; cp[u][2] = c[2];
+        }
+        reduce_phase();
+#pragma unroll
+        for (int u = 0; u < W; ++u) reduce_pin(j[u]);
+        // phase B: the matched records, one line each (no match: record 0 through a select on the index -- always there --
+        // and skipped in phase C; no branch between the gathers)
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            use[u] = use[u] && j[u] != PCR_NONE;
+            const GicpRec *r = ga.trec + (use[u] ? j[u] : 0u);
+            q[u] = r->p; cq0[u] = r->c0; cq1[u] = r->c1;
+        }
+        reduce_phase();
+        // phase C: residual, gate, weight, sums -- in index order
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            if (!use[u]) continue;
+            float tx, ty, tz, dx, dy, dz;
+            xform(P, x[u], y[u], z[u], tx, ty, tz);
+            if (!residual_f32<true>(a, q[u], tx, ty, tz, dx, dy, dz)) continue;
+            const float cpv[6] = {cp[u][0].x, cp[u][0].y, cp[u][1].x, cp[u][1].y, cp[u][2].x, cp[u][2].y};
+            const float cqv[6] = {cq0[u].x, cq0[u].y, cq0[u].z, cq0[u].w, cq1[u].x, cq1[u].y};
+            double m6[6];
+            gicp_weight(P, cpv, cqv, m6);
+            acc_ndt(acc, P, (double)x[u], (double)y[u], (double)z[u], m6, (double)dx, (double)dy, (double)dz);
+        }
+    }
+    block_store_partials<false>(acc, ga.rows);
+}
+
+__global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) {
+    const int e = threadIdx.x;
+    if (e >= 29) return;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += rows[(size_t)b * 32 + e];
+    out[e] = s;
+}
+
+// search + reduce + fold + 29 doubles back: one stream synchronisation, device blocks from the context's block cache
+pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
+    if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+    if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_ICP, T, max_dist, flags, false));
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    if (s->n == 0) return PCR_OK;
+    pcr_context *ctx = t->ctx;
+    const int nb = choose_blocks(ctx, s->n);         // n and the device only
+    DevBuf<double> rows, sums;
+    HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
+    GicpArgs ga;
+    ga.scov = s->cov; ga.trec = (const GicpRec *)t->gcov; ga.rows = rows.p;
+    {
+        RoctxRange range("pcr:gicp_reduce");
+        hipLaunchKernelGGL(k_gicp_reduce, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, ga);
+        hipLaunchKernelGGL(k_gicp_fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, sums.p, 29 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    CtxScope scope(t->ctx);
+    return pcr_run_gicp(t, s, T, max_dist, flags, out);
+}
+
+// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over pcr_run_gicp: same gn_step, same trace rows
+static pcr_status gicp_pass(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
+    return pcr_run_gicp(t, s, T, max_dist, flags, out);
+}
+extern "C" pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                     unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(gicp_pass, t, s, PCR_ICP, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}

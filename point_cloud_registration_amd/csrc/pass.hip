@@ -874,11 +874,11 @@ pcr_status pcr_run_batch(pcr_target *t, pcr_scan *const *scans, int n_items, int
 // NOT measured: the block-local deal at EVERY scan size.  pass_enqueue records it as the loser once a wave gets tens of
 // tiles (scans of ~10 M points and more); such a rows pass is correct but its search is slower than pcr_linearize's.
 static pcr_status rows_search(Pass *ps, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
-                              unsigned flags) {
+                              unsigned flags, bool caller_order = true) {
     PCR_TRY(pass_validate(t, s, kind, max_dist));
     pcr_context *ctx = t->ctx;
     PCR_TRY(refuse_comm_and_q6(t, kind, "rows passes", "PlaneICP rows", "quirk Q6"));
-    PCR_REQUIRE(!s->sorted || s->order != nullptr, "a Morton-sorted scan needs PCR_FLAG_KEEP_ORDER (or PCR_FLAG_NO_SCAN_SORT) for rows in the caller's order");
+    PCR_REQUIRE(!caller_order || !s->sorted || s->order != nullptr, "a Morton-sorted scan needs PCR_FLAG_KEEP_ORDER (or PCR_FLAG_NO_SCAN_SORT) for rows in the caller's order");
     HIP_TRY(hipSetDevice(ctx->device));
     PCR_TRY(pcr_ensure_scratch(ctx, s->n));
     pass_init(ps, t, s, kind, false, false);
@@ -893,6 +893,15 @@ static pcr_status rows_search(Pass *ps, DevBuf<uint32_t> *nn, pcr_target *t, pcr
     RoctxRange range("pcr:rows_search");
     launch_plain_search(ps, dim3((unsigned)search_grid(ps, false, PCR_NN_FULL).nb));
     HIP_TRY(hipGetLastError());
+    return PCR_OK;
+}
+
+// the same for a kernel of another translation unit (gicp.hip, which reads the scan in device order: caller_order = false)
+pcr_status pcr_rows_search(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
+                           unsigned flags, bool caller_order) {
+    Pass ps;
+    PCR_TRY(rows_search(&ps, nn, t, s, kind, T, max_dist, flags, caller_order));
+    *a = ps.a;
     return PCR_OK;
 }
 

@@ -293,6 +293,8 @@ struct pcr_target {
     Geom<float> gf;
     PtF *pts = nullptr;        // cell-sorted (the NN search reads these 16-byte records)
     PtN *pn = nullptr;         // cell-sorted point + normal records (PlaneICP gathers these); NULL = no normals
+    float *gcov = nullptr;     // GICP: cell-sorted 64-byte records {xyz, orig, xx xy xz yy yz zz, padding} (gicp.hip: GicpRec, one
+                               // line per correspondence); NULL = no covariances
     uint64_t serial = 0;
     // quirk Q6 (plane_icp.py:20-22: PlaneICP builds its tree on the ORIGINAL array, so a float64 target is searched in
     // float64 while the records are gathered from the float32 copy): the float64 coordinates of the same points, in the
@@ -326,6 +328,7 @@ struct pcr_scan {
     float *x = nullptr, *y = nullptr, *z = nullptr;   // SoA, Morton-sorted unless PCR_FLAG_NO_SCAN_SORT
     bool sorted = false;                              // the points were Morton-sorted: device order != caller order
     uint32_t *order = nullptr;                        // PCR_FLAG_KEEP_ORDER on a sorted scan: device position -> caller index
+    float *cov = nullptr;                             // GICP: covariances in DEVICE order, 6 floats per point (xx xy xz yy yz zz); NULL = none
     // matched cell-sorted index per scan point (PCR_NONE = gated out), written by k_nn_scan and read
     // by the reduce kernel; kept across passes: the previous match is an exact upper bound for the
     // next search against the SAME target (nn_serial)
@@ -414,6 +417,17 @@ pcr_status pcr_terms_weighted_sum(pcr_context *ctx, const double *d_P, int64_t s
                                   const double *weights, int64_t n, double out[29]);
 pcr_status pcr_terms_coreset(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in, int k,
                              int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out);
+// the search half of a rows pass on its own (kind's full search at pose T into *nn, the call's match buffer); *a = what the
+// kernel behind it reads.  caller_order = false drops the "scan must know the caller's order" requirement (gicp.hip)
+struct LinArgs;
+pcr_status pcr_rows_search(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
+                           unsigned flags, bool caller_order);
+// ---- api.hip: the host-driven Gauss-Newton loop (align_host_loop of pcr_align) over a pass of the caller's choice
+typedef pcr_status (*pcr_pass_fn)(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double out[29]);
+pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
+                               double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
+// ---- gicp.hip: search + k_gicp_reduce + k_gicp_fold (both sides must hold covariances)
+pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 
 // ---- roctx ranges around the hot-path launches (PCR_ROCTX=1; libroctx64 bound with dlopen, so the

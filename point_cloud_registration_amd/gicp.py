@@ -1,0 +1,177 @@
+"""Generalized ICP (Segal, Haehnel, Thrun: "Generalized-ICP", RSS 2009) behind the ``Registration`` interface.
+
+The reference has no GICP class (it only borrows small_gicp's tree as a KD-tree back end, ``kdtree.py:26-57``); this one follows
+the conventions of its ``NDT``: ``J = [I, -R skew(p)]`` with the right-multiplicative update of ``plus``, and the dependence of
+the weight matrix on the pose ignored, as every GICP implementation does.  Every correspondence -- found and gated exactly as
+``ICP`` finds and gates it -- is weighed with ``M = (Cq + R Cp R^T)^-1``, ``Cq`` / ``Cp`` the covariances of the matched target
+point and of the scan point: float32 ``(N, 6)`` = xx xy xz yy yz zz, given by the caller or estimated on the GPU from the ``k``
+nearest neighbours (``regularization="plane"``: ``I - (1 - eps) n n^T``, eigenvalues ``(eps, 1, 1)``; ``"raw"``: the k-NN
+covariance itself).  A singular ``Cq + R Cp R^T`` (determinant exactly 0) is divided by 1e6 instead of its determinant, the
+rule of the voxel targets' ``calc_icov``: such a pair contributes next to nothing instead of Inf / NaN.
+"""
+
+import numpy as np
+
+from . import _capi
+from .kdtree import KDTree
+from .math_tools import plus, skew
+from .registration import Registration
+
+_MODES = {"plane": _capi.COV_PLANE, "raw": _capi.COV_RAW}
+
+
+class GICP(Registration):
+    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_gicp_*)
+
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
+        if kw.get("devices") is not None or kw.get("comm") is not None:
+            raise ValueError("GICP runs on one GPU of one process: not with comm= or devices=")
+        if regularization not in _MODES:
+            raise ValueError(f"regularization must be one of {sorted(_MODES)}, not {regularization!r}")
+        if not 1 <= int(k) <= 64:
+            raise ValueError("k must be in [1, 64]")
+        super().__init__(max_iter=max_iter, tol=tol, **kw)
+        self.max_dist = max_dist
+        self.k = int(k)
+        self.eps = float(eps)
+        self.regularization = regularization
+        self._covariance = None
+
+    # -- target ----------------------------------------------------------------------------------
+    def set_target(self, target, kdree=None, cov=None):
+        """float32 copy of the target, an exact-NN index on the GPU and one covariance per point: ``cov`` (N, 6) or
+        (N, 3, 3) when given, else estimated from the ``k`` nearest neighbours.  ``kdree`` keeps the keyword of
+        ``PlaneICP.set_target``; as there, a foreign tree is never searched."""
+        target = np.asarray(target).astype(np.float32)
+        c = None
+        if cov is not None:                         # (checked before anything of the previous target is replaced)
+            c = _capi.cov6(cov)
+            if c.shape != (target.shape[0], 6):
+                raise ValueError("cov must have shape (N, 6) or (N, 3, 3)")
+        tree = KDTree(target, device=self._device, _ctx=self._ctx())
+        if c is None:
+            tree._target.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
+        else:
+            tree._target.set_covariances(c)
+        self.kdtree, self.target = tree, target
+        self._covariance = c                        # None: read back the first time somebody asks, as PlaneICP.normal is
+        self._target = self.kdtree._target
+        self._is_target_set = True
+
+    @property
+    def covariance(self):
+        """The target's covariances, float32 (N, 6) = xx xy xz yy yz zz, in the order of the target."""
+        if self._covariance is None and self._target is not None:
+            self._covariance = self._target.get_covariances()
+        return self._covariance
+
+    def source_covariance(self, source):
+        """The covariances ``calc_H_g_e2`` / ``align`` use for ``source`` (estimated now if they have not been), in its order."""
+        return self._gicp_scan(source, None).get_covariances()
+
+    # -- passes ----------------------------------------------------------------------------------
+    def calc_H_g_e2(self, cur_T, source, source_cov=None, weights=None):
+        """Hessian (6x6), gradient (6) and squared (Mahalanobis) error at ``cur_T``.  ``source_cov``: (N, 6) or (N, 3, 3) in
+        the order of ``source``; default: estimated once per uploaded scan with this object's ``k`` / ``regularization``."""
+        if weights is not None:
+            raise NotImplementedError("GICP does not support weights=")
+        scan = self._gicp_scan(source, source_cov)
+        return self._gicp_linearize(np.asarray(cur_T, dtype=np.float64), scan)
+
+    def align(self, source, init_T=np.eye(4), verbose=False, source_cov=None):
+        if self.is_target_set() is False:
+            raise ValueError("Target is not set.")
+        scan = self._gicp_scan(source, source_cov, fresh=True)
+        cur_T = np.array(init_T, dtype=np.float64)
+        if self._native_loop and not verbose:
+            T, iters, trace = _capi.gicp_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
+                                               self._flags, want_trace=True)
+            self.last_iterations = iters
+            if iters:
+                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
+            return T
+        it = 0
+        for it in range(self.max_iter):
+            H, g, e2 = self._gicp_linearize(cur_T, scan)
+            if verbose:
+                print(f"iter {it}, error {e2}")
+            dx = -np.linalg.solve(H, g)
+            if np.linalg.norm(dx) < self.tol:
+                break
+            cur_T = plus(cur_T, dx)
+        self.last_iterations = it + 1 if self.max_iter > 0 else 0
+        return cur_T
+
+    def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_cov=None):
+        """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
+        (``self.kdtree.query``) and covariances, the inverse by ``numpy.linalg.inv``."""
+        cur_T = np.asarray(cur_T, dtype=np.float64)
+        R = cur_T[:3, :3]
+        source = np.asarray(source)
+        Cp = self.source_covariance(source) if source_cov is None else _capi.cov6(source_cov)
+        Cq = self.covariance
+        src_trans = _xform32(cur_T, source.astype(np.float32))
+        dist, idx = self.kdtree.query(src_trans)
+        H, g, e2 = np.zeros((6, 6)), np.zeros(6), 0.0
+        for i in np.nonzero(dist < np.float32(self.max_dist))[0]:
+            M = np.linalg.inv(_full(Cq[idx[i]]) + R @ _full(Cp[i]) @ R.T)
+            J = np.hstack([np.eye(3), -R @ skew(np.asarray(source[i], dtype=np.float64))])
+            d = (src_trans[i] - self.target[idx[i]]).astype(np.float64)
+            H += J.T @ M @ J
+            g += J.T @ M @ d
+            e2 += d @ M @ d
+        return H, g, e2
+
+    # -- out of scope ----------------------------------------------------------------------------
+    def linearize(self, *a, **kw):
+        raise NotImplementedError("GICP does not support linearize()")
+
+    def coreset(self, *a, **kw):
+        raise NotImplementedError("GICP does not support coreset()")
+
+    def align_batch(self, *a, **kw):
+        raise NotImplementedError("GICP does not support align_batch()")
+
+    def calc_H_g_e2_batch(self, *a, **kw):
+        raise NotImplementedError("GICP does not support calc_H_g_e2_batch()")
+
+    # -- internals -------------------------------------------------------------------------------
+    def _gicp_scan(self, source, source_cov, fresh=False):
+        """The device copy of ``source`` with covariances on it.  They belong to the ``_capi.Scan``: estimated (or uploaded)
+        once per uploaded scan, gone with it."""
+        if not self._is_target_set:
+            raise ValueError("Target is not set.")
+        # the caller's order is kept (4 bytes per point): given covariances and source_covariance() cross the boundary in it
+        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
+        if source_cov is not None:
+            c = _capi.cov6(source_cov)
+            if c.shape != (scan.n, 6):
+                raise ValueError("source_cov must have shape (N, 6) or (N, 3, 3)")
+            tag = ("given", self._digest(c))
+            if getattr(scan, "_gicp_cov", None) != tag:
+                scan.set_covariances(c)
+                scan._gicp_cov = tag
+        else:
+            tag = ("estimated", self.k, self.regularization, self.eps)
+            if getattr(scan, "_gicp_cov", None) != tag:
+                scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
+                scan._gicp_cov = tag
+        return scan
+
+    def _gicp_linearize(self, cur_T, scan):
+        out = _capi.gicp_linearize(self._target, scan, cur_T, self._max_dist(), self._flags)
+        H, g, e2, cnt = _capi.unpack29(out)
+        self.last_correspondences = cnt
+        return H, g, e2
+
+
+def _xform32(T, p):
+    """The kernels' float32 transform, in their order of operations: ((R0 x + R1 y) + R2 z) + t (BLAS may fuse or reorder)."""
+    T = np.asarray(T, dtype=np.float64).astype(np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) + T[i, 3] for i in range(3)], axis=1)
+
+
+def _full(c6):
+    c = np.asarray(c6, dtype=np.float64)
+    return np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]])
