@@ -349,6 +349,42 @@ PCR_API pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T
 PCR_API pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                   unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 
+/* ---- Voxelized GICP: distribution to voxel ---------------------------------------------------
+ * No reference counterpart (Koide, Yokozuka, Oishi, Banno: "Voxelized GICP", ICRA 2021; small_gicp / fast_gicp).  GICP's
+ * weighting on a VOXEL target: a scan point p (float32, untransformed) with covariance Cp (float32, six values xx xy xz yy yz
+ * zz: exactly GICP's scan covariances, pcr_scan_*_covariances) at pose T = (R, t) is matched to the nearest kept centroid mu
+ * and weighed with M = (Cv + R Cp R^T)^-1, Cv the float64 covariance of that voxel:
+ *   H = sum J^T M J,  g = sum J^T M d,  e2 = sum d^T M d,  J = [I, -R skew(p)],  d = R p + t - mu,  count = matches kept.
+ * Correspondence and gate are exactly PCR_NDT's / PCR_VPLANE's: float32 transform, exact nearest kept centroid in float64,
+ * d = (double)xform(p) - mu formed in float64, kept iff sqrt(d . d) < max_dist (strict, float64).  M is float64: Cp widened,
+ * R Cp R^T evaluated in the order GICP evaluates it, the inverse by the closed form of the voxel targets INCLUDING its rule
+ * for det == 0 (the adjugate is divided by 1e6 instead).  Unlike PCR_NDT's bare voxel covariance, the summed matrix is well
+ * conditioned as soon as either side is regularised.  Conventions and the Gauss-Newton step are PCR_NDT's.
+ * pcr_target_voxels_set_covariances: one Cv per kept voxel, (n, 6) float64 xx xy xz yy yz zz, from
+ *     PCR_COV_RAW    the voxel's own covariance (the bits pcr_target_voxels_get returns as cov; eps ignored)
+ *     PCR_COV_PLANE  I - (1 - eps) n n^T with n the voxel's normal, evaluated in float64: eigenvalues (eps, 1, 1), the sign
+ *                    of n does not matter; 0 < eps <= 1
+ *     cov6_or_null   non-NULL overrides mode: the caller's own, n x 6 in the order of pcr_target_voxels_get (ascending key)
+ *                    -- e.g. the mean of the point covariances in the voxel.  A non-finite entry gives PCR_ERR_INVALID and
+ *                    leaves the old covariances in place.
+ *   A point target, or a voxel target that does not hold what the mode needs, gives PCR_ERR_NO_TARGET.  The inverse
+ *   covariances pcr_linearize(PCR_NDT) reads are not touched.
+ * pcr_target_voxels_get_covariances: the same rows back, key order; PCR_ERR_NO_TARGET when there are none.
+ * pcr_vgicp_linearize: out[29] as pcr_linearize.  PCR_ERR_NO_TARGET for a point target, a voxel target without covariances or
+ *   a scan without covariances.  A full centroid search into a match buffer of the call (the scan's reuse state is left
+ *   alone), then a reduce launch that writes one row of sums per block with plain stores and a one-block fold that adds the
+ *   rows in block order: no atomics, the grid depends on the scan size and the device only -- two calls return the same bits.
+ *   An empty scan gives zeros.
+ * pcr_vgicp_align: the host-driven loop of pcr_align(PCR_FLAG_HOST_LOOP) over pcr_vgicp_linearize: same step, same trace rows
+ *   (16 + 29 doubles), PCR_ERR_SINGULAR as there.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group).                        */
+PCR_API pcr_status pcr_target_voxels_set_covariances(pcr_target *t, int mode, double eps, const double *cov6_or_null);
+PCR_API pcr_status pcr_target_voxels_get_covariances(pcr_target *t, double *cov6);
+PCR_API pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags,
+                                       double out[29]);
+PCR_API pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                   unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

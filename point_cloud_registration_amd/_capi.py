@@ -127,6 +127,11 @@ PROTOTYPES = {
     "pcr_scan_get_covariances": (C.c_int, [_vp, _f32p]),
     "pcr_gicp_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
     "pcr_gicp_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    # Voxelized GICP: per-voxel covariances and the distribution-to-voxel pass (include/pcr.h)
+    "pcr_target_voxels_set_covariances": (C.c_int, [_vp, C.c_int, C.c_double, _vp]),
+    "pcr_target_voxels_get_covariances": (C.c_int, [_vp, _f64p]),
+    "pcr_vgicp_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
+    "pcr_vgicp_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
     # batches: many scans / start poses against one target in one launch (include/pcr.h)
     "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
     "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -567,6 +572,20 @@ class Target:
         check(lib().pcr_target_get_covariances(self.handle, out))
         return out
 
+    # -- VGICP covariances of a voxel target: float64 (Nv, 6) = xx xy xz yy yz zz, in the order of voxel_stats (ascending key)
+    def set_voxel_covariances(self, mode=COV_PLANE, eps=1e-3, cov=None):
+        """``cov`` (Nv, 6) or (Nv, 3, 3) float64 overrides ``mode`` (COV_PLANE: from the voxel normals, COV_RAW: the voxels' own)."""
+        if cov is not None:
+            cov = cov6_f64(cov)
+            if cov.shape != (self.size(), 6):
+                raise ValueError("voxel covariances must have shape (Nv, 6) or (Nv, 3, 3)")
+        check(lib().pcr_target_voxels_set_covariances(self.handle, int(mode), float(eps), _ptr(cov)))
+
+    def get_voxel_covariances(self):
+        out = np.empty((self.size(), 6), np.float64)
+        check(lib().pcr_target_voxels_get_covariances(self.handle, out))
+        return out
+
     def voxel_stats(self, names=("mean", "cov", "norm", "icov", "counts", "keys")):
         n = self.size()
         bufs = {"mean": np.empty((n, 3)), "cov": np.empty((n, 3, 3)), "norm": np.empty((n, 3)),
@@ -915,6 +934,36 @@ def gicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trac
     trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
     check(lib().pcr_gicp_align(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), int(flags), T,
                                C.byref(iters), _ptr(trace)))
+    T = T.reshape(4, 4)
+    if want_trace:
+        return T, iters.value, trace[:iters.value]
+    return T, iters.value
+
+
+def cov6_f64(cov):
+    """Voxel covariances as C-contiguous float64 (N, 6) = xx xy xz yy yz zz; (N, 3, 3) input contributes its upper triangle."""
+    cov = np.asarray(cov)
+    if cov.ndim == 3 and cov.shape[1:] == (3, 3):
+        cov = cov[:, (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)]
+    return np.ascontiguousarray(cov, dtype=np.float64)
+
+
+def vgicp_linearize(target, scan, T, max_dist, flags=0):
+    """pcr_vgicp_linearize -> the 29 sums of one VGICP pass (see include/pcr.h)."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty(29)
+    check(lib().pcr_vgicp_linearize(target.handle, scan.handle, T, float(max_dist), int(flags), out))
+    return out
+
+
+def vgicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
+    """pcr_vgicp_align: the host-driven Gauss-Newton loop over pcr_vgicp_linearize, behind the boundary."""
+    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
+    T = np.zeros(16)
+    iters = C.c_int(0)
+    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
+    check(lib().pcr_vgicp_align(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), int(flags), T,
+                                C.byref(iters), _ptr(trace)))
     T = T.reshape(4, 4)
     if want_trace:
         return T, iters.value, trace[:iters.value]

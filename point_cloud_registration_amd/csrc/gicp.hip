@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "eigen3.h"
+#include "gicp_weight.h"
 #include "knn_device.h"
 #include "pass_device.h"
 
@@ -325,30 +326,7 @@ struct GicpArgs {
 #define GICP_W 3
 #endif
 
-// M6 = (Cq + R Cp R^T)^-1 as xx xy xz yy yz zz, float64
-__device__ __forceinline__ void gicp_weight(const PoseK &P, const float cp[6], const float cq[6], double m6[6]) {
-    const double Cp[3][3] = {{cp[0], cp[1], cp[2]}, {cp[1], cp[3], cp[4]}, {cp[2], cp[4], cp[5]}};
-    double B[3][3];                                  // R Cp
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) B[i][j] = (P.R[3 * i] * Cp[0][j] + P.R[3 * i + 1] * Cp[1][j]) + P.R[3 * i + 2] * Cp[2][j];
-    double S[3][3];                                  // (R Cp) R^T, upper triangle mirrored: symmetric by construction
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            S[i][j] = (B[i][0] * P.R[3 * j] + B[i][1] * P.R[3 * j + 1]) + B[i][2] * P.R[3 * j + 2];
-            S[j][i] = S[i][j];
-        }
-    const double m[9] = {(double)cq[0] + S[0][0], (double)cq[1] + S[0][1], (double)cq[2] + S[0][2],
-                         (double)cq[1] + S[1][0], (double)cq[3] + S[1][1], (double)cq[4] + S[1][2],
-                         (double)cq[2] + S[2][0], (double)cq[4] + S[2][1], (double)cq[5] + S[2][2]};
-    double o[9];
-    icov_closed_form(m, o);
-    m6[0] = o[0]; m6[1] = o[1]; m6[2] = o[2]; m6[3] = o[4]; m6[4] = o[5]; m6[5] = o[8];
-}
-
+// (the weight M6 = (Cq + R Cp R^T)^-1: gicp_weight.h, shared with vgicp.hip)
 __global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) {
     const PoseK &P = a.hp;                           // host-driven: the pose came by value
     constexpr int W = GICP_W;

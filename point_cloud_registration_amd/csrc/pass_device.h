@@ -286,12 +286,17 @@ __device__ __forceinline__ bool residual_f32(const LinArgs &a, const float4 &q, 
     dx = tx - q.x; dy = ty - q.y; dz = tz - q.z;
     return !GATE || gate_f32(a, dx, dy, dz);
 }
-// ... voxel targets: float64, against the centroid m at cell-sorted index j
+// ... voxel targets: float64, against the centroid m (already loaded: vgicp.hip gathers it a phase ahead) ...
+template <bool GATE>
+__device__ __forceinline__ bool residual_f64(const LinArgs &a, const PtD &m, float tx, float ty, float tz, double &dx, double &dy, double &dz) {
+    dx = (double)tx - m.x; dy = (double)ty - m.y; dz = (double)tz - m.z;
+    return !GATE || gate_f64(a, dx, dy, dz);
+}
+// ... or at cell-sorted index j
 template <bool GATE>
 __device__ __forceinline__ bool residual_f64(const LinArgs &a, uint32_t j, float tx, float ty, float tz, PtD &m, double &dx, double &dy, double &dz) {
     m = a.means[j];
-    dx = (double)tx - m.x; dy = (double)ty - m.y; dz = (double)tz - m.z;
-    return !GATE || gate_f64(a, dx, dy, dz);
+    return residual_f64<GATE>(a, m, tx, ty, tz, dx, dy, dz);
 }
 
 // residual + gate + accumulate for a point target whose record is already here

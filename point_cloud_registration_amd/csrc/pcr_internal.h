@@ -308,6 +308,7 @@ struct pcr_target {
     PtD *means = nullptr;      // cell-sorted
     double *vnorm = nullptr;   // [n][3] cell-sorted
     double *vicov = nullptr;   // [n][6] cell-sorted (xx xy xz yy yz zz)
+    double *vcov = nullptr;    // VGICP: [n][6] cell-sorted covariances (xx xy xz yy yz zz; vgicp.hip); NULL = none
     // voxel statistics in key order (device), for read-back
     double *st_mean = nullptr, *st_cov = nullptr, *st_norm = nullptr, *st_icov = nullptr;
     int64_t *st_counts = nullptr, *st_keys = nullptr;
@@ -428,6 +429,8 @@ pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int
                                double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 // ---- gicp.hip: search + k_gicp_reduce + k_gicp_fold (both sides must hold covariances)
 pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]);
+// ---- vgicp.hip: centroid search + k_vgicp_reduce + k_vgicp_fold (a voxel target with covariances, a scan with covariances)
+pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 
 // ---- roctx ranges around the hot-path launches (PCR_ROCTX=1; libroctx64 bound with dlopen, so the

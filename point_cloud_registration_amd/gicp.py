@@ -20,7 +20,38 @@ from .registration import Registration
 _MODES = {"plane": _capi.COV_PLANE, "raw": _capi.COV_RAW}
 
 
-class GICP(Registration):
+class ScanCovariances:
+    """The scan side of GICP and VGICP: covariances on the device copy of a scan.  The host class provides ``k``, ``eps``,
+    ``regularization`` and ``Registration``'s scan cache."""
+
+    def source_covariance(self, source):
+        """The covariances ``calc_H_g_e2`` / ``align`` use for ``source`` (estimated now if they have not been), in its order."""
+        return self._gicp_scan(source, None).get_covariances()
+
+    def _gicp_scan(self, source, source_cov, fresh=False):
+        """The device copy of ``source`` with covariances on it.  They belong to the ``_capi.Scan``: estimated (or uploaded)
+        once per uploaded scan, gone with it."""
+        if not self._is_target_set:
+            raise ValueError("Target is not set.")
+        # the caller's order is kept (4 bytes per point): given covariances and source_covariance() cross the boundary in it
+        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
+        if source_cov is not None:
+            c = _capi.cov6(source_cov)
+            if c.shape != (scan.n, 6):
+                raise ValueError("source_cov must have shape (N, 6) or (N, 3, 3)")
+            tag = ("given", self._digest(c))
+            if getattr(scan, "_gicp_cov", None) != tag:
+                scan.set_covariances(c)
+                scan._gicp_cov = tag
+        else:
+            tag = ("estimated", self.k, self.regularization, self.eps)
+            if getattr(scan, "_gicp_cov", None) != tag:
+                scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
+                scan._gicp_cov = tag
+        return scan
+
+
+class GICP(ScanCovariances, Registration):
     KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_gicp_*)
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
@@ -64,10 +95,6 @@ class GICP(Registration):
         if self._covariance is None and self._target is not None:
             self._covariance = self._target.get_covariances()
         return self._covariance
-
-    def source_covariance(self, source):
-        """The covariances ``calc_H_g_e2`` / ``align`` use for ``source`` (estimated now if they have not been), in its order."""
-        return self._gicp_scan(source, None).get_covariances()
 
     # -- passes ----------------------------------------------------------------------------------
     def calc_H_g_e2(self, cur_T, source, source_cov=None, weights=None):
@@ -136,28 +163,6 @@ class GICP(Registration):
         raise NotImplementedError("GICP does not support calc_H_g_e2_batch()")
 
     # -- internals -------------------------------------------------------------------------------
-    def _gicp_scan(self, source, source_cov, fresh=False):
-        """The device copy of ``source`` with covariances on it.  They belong to the ``_capi.Scan``: estimated (or uploaded)
-        once per uploaded scan, gone with it."""
-        if not self._is_target_set:
-            raise ValueError("Target is not set.")
-        # the caller's order is kept (4 bytes per point): given covariances and source_covariance() cross the boundary in it
-        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
-        if source_cov is not None:
-            c = _capi.cov6(source_cov)
-            if c.shape != (scan.n, 6):
-                raise ValueError("source_cov must have shape (N, 6) or (N, 3, 3)")
-            tag = ("given", self._digest(c))
-            if getattr(scan, "_gicp_cov", None) != tag:
-                scan.set_covariances(c)
-                scan._gicp_cov = tag
-        else:
-            tag = ("estimated", self.k, self.regularization, self.eps)
-            if getattr(scan, "_gicp_cov", None) != tag:
-                scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
-                scan._gicp_cov = tag
-        return scan
-
     def _gicp_linearize(self, cur_T, scan):
         out = _capi.gicp_linearize(self._target, scan, cur_T, self._max_dist(), self._flags)
         H, g, e2, cnt = _capi.unpack29(out)
