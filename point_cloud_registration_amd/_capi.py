@@ -910,64 +910,58 @@ def scan_coreset(target, scan, kind, T, max_dist, k, n_target, flags=FLAG_ICP_RR
     return idx[:n_out.value].copy(), w[:n_out.value].copy()
 
 
-def cov6(cov):
-    """Covariances as C-contiguous float32 (N, 6) = xx xy xz yy yz zz; (N, 3, 3) input contributes its upper triangle."""
+def cov6(cov, dtype=np.float32):
+    """Covariances as C-contiguous ``dtype`` (N, 6) = xx xy xz yy yz zz; (N, 3, 3) input contributes its upper triangle."""
     cov = np.asarray(cov)
     if cov.ndim == 3 and cov.shape[1:] == (3, 3):
         cov = cov[:, (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)]
-    return np.ascontiguousarray(cov, dtype=np.float32)
+    return np.ascontiguousarray(cov, dtype=dtype)
+
+
+def cov6_f64(cov):
+    """Voxel covariances: ``cov6`` in float64."""
+    return cov6(cov, np.float64)
+
+
+def _linearize29(entry, target, scan, T, max_dist, flags):
+    """entry(target, scan, T, max_dist, flags, out) -> the 29 sums of one pass (see include/pcr.h)."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty(29)
+    check(entry(target.handle, scan.handle, T, float(max_dist), int(flags), out))
+    return out
+
+
+def _align(entry, head, T_init, max_iter, tol, max_dist, flags, want_trace):
+    """entry(*head, T_init, max_iter, tol, max_dist, flags, T_out, &iterations, trace) -> (T, iterations[, trace rows])."""
+    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
+    T = np.zeros(16)
+    iters = C.c_int(0)
+    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
+    check(entry(*head, T0, int(max_iter), float(tol), float(max_dist), int(flags), T, C.byref(iters), _ptr(trace)))
+    T = T.reshape(4, 4)
+    if want_trace:
+        return T, iters.value, trace[:iters.value]
+    return T, iters.value
 
 
 def gicp_linearize(target, scan, T, max_dist, flags=0):
-    """pcr_gicp_linearize -> the 29 sums of one GICP pass (see include/pcr.h)."""
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-    out = np.empty(29)
-    check(lib().pcr_gicp_linearize(target.handle, scan.handle, T, float(max_dist), int(flags), out))
-    return out
+    """pcr_gicp_linearize -> the 29 sums of one GICP pass."""
+    return _linearize29(lib().pcr_gicp_linearize, target, scan, T, max_dist, flags)
 
 
 def gicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
     """pcr_gicp_align: the host-driven Gauss-Newton loop over pcr_gicp_linearize, behind the boundary."""
-    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
-    T = np.zeros(16)
-    iters = C.c_int(0)
-    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
-    check(lib().pcr_gicp_align(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), int(flags), T,
-                               C.byref(iters), _ptr(trace)))
-    T = T.reshape(4, 4)
-    if want_trace:
-        return T, iters.value, trace[:iters.value]
-    return T, iters.value
-
-
-def cov6_f64(cov):
-    """Voxel covariances as C-contiguous float64 (N, 6) = xx xy xz yy yz zz; (N, 3, 3) input contributes its upper triangle."""
-    cov = np.asarray(cov)
-    if cov.ndim == 3 and cov.shape[1:] == (3, 3):
-        cov = cov[:, (0, 0, 0, 1, 1, 2), (0, 1, 2, 1, 2, 2)]
-    return np.ascontiguousarray(cov, dtype=np.float64)
+    return _align(lib().pcr_gicp_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
 
 
 def vgicp_linearize(target, scan, T, max_dist, flags=0):
-    """pcr_vgicp_linearize -> the 29 sums of one VGICP pass (see include/pcr.h)."""
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-    out = np.empty(29)
-    check(lib().pcr_vgicp_linearize(target.handle, scan.handle, T, float(max_dist), int(flags), out))
-    return out
+    """pcr_vgicp_linearize -> the 29 sums of one VGICP pass."""
+    return _linearize29(lib().pcr_vgicp_linearize, target, scan, T, max_dist, flags)
 
 
 def vgicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
     """pcr_vgicp_align: the host-driven Gauss-Newton loop over pcr_vgicp_linearize, behind the boundary."""
-    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
-    T = np.zeros(16)
-    iters = C.c_int(0)
-    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
-    check(lib().pcr_vgicp_align(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), int(flags), T,
-                                C.byref(iters), _ptr(trace)))
-    T = T.reshape(4, 4)
-    if want_trace:
-        return T, iters.value, trace[:iters.value]
-    return T, iters.value
+    return _align(lib().pcr_vgicp_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
 
 
 _linearize_fast = None
@@ -999,22 +993,13 @@ def linearize(target, scan, kind, T, max_dist, flags=FLAG_ICP_RR_QUIRK):
 
 def align(target, scan, kind, T_init, max_iter, tol, max_dist, flags=FLAG_ICP_RR_QUIRK, want_trace=False):
     """pcr_align: the whole Gauss-Newton loop behind the boundary."""
-    T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
-    T = np.zeros(16)
-    iters = C.c_int(0)
-    trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
     if getattr(target, "ghandle", None) is not None:
         if getattr(scan, "ghandle", None) is None:
             raise ValueError("a group target needs a scan created on the same group")
-        check(lib().pcr_group_align(target.ghandle, scan.ghandle, int(kind), T0, int(max_iter), float(tol), float(max_dist),
-                                    int(flags), T, C.byref(iters), _ptr(trace)))
+        entry, head = lib().pcr_group_align, (target.ghandle, scan.ghandle, int(kind))
     else:
-        check(lib().pcr_align(target.handle, scan.handle, int(kind), T0, int(max_iter), float(tol), float(max_dist),
-                              int(flags), T, C.byref(iters), _ptr(trace)))
-    T = T.reshape(4, 4)
-    if want_trace:
-        return T, iters.value, trace[:iters.value]
-    return T, iters.value
+        entry, head = lib().pcr_align, (target.handle, scan.handle, int(kind))
+    return _align(entry, head, T_init, max_iter, tol, max_dist, flags, want_trace)
 
 
 class ScanBatch:

@@ -8,28 +8,20 @@
 //                     usual "eigenvalues -> (eps, 1, 1)", which depends on the normal only -- or PCR_COV_RAW: cov itself.
 //                     Six floats (xx xy xz yy yz zz) per point, written through pt_orig: the INPUT order of the indexed cloud.
 //   k_gicp_reduce     sits where k_rows sits: behind a full search (pass.hip: pcr_rows_search) into a match buffer of the call.
-//                     Streams nn_j, the scan SoA and the scan covariances in the scan's device order (lane = consecutive
-//                     point), GICP_W points per lane in flight: indices, coordinates and scan covariances of all of them, then
-//                     all gathers, then the arithmetic.  The correspondence is ICP's (xform, the matched PtF,
+//   k_gicp_fold       The distribution pass of dist_pass.h (dist_reduce, dist_fold, dist_launch) with GicpArgs as its target
+//                     side, GICP_W points per lane in flight.  The correspondence is ICP's (xform, the matched PtF,
 //                     residual_f32<true>), the sums are acc_ndt's with M6 from icov_closed_form: nothing is restated here.
-//                     Fold: wave shuffles in a fixed order, LDS across the waves in wave order, ONE row of 32 doubles per
-//                     block with plain stores (block_store_partials).  No tickets, no atomics, no in-launch hand-off.
-//   k_gicp_fold       one block: thread e < 29 adds rows 0 .. nb-1 in order.  The kernel boundary is the only ordering
-//                     between the two launches; the grid depends on n and the device only, so two calls return the same bits.
 //
 // Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
-// correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line, through
-// a select on the index like reduce_stream's gather_slot: no branch between the gathers of a phase); its first 16 bytes are the
-// index's own PtF, so residual_f32<true> sees exactly what gather_point<PCR_ICP> would have handed it.
+// correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line); its
+// first 16 bytes are the index's own PtF, so residual_f32<true> sees exactly what gather_point<PCR_ICP> would have handed it.
 // det == 0 of Cq + R Cp R^T (e.g. two RAW covariances of single-point neighbourhoods): icov_closed_form's rule applies, the
 // adjugate is divided by 1e6 instead -- such a correspondence contributes (almost) nothing instead of Inf / NaN.
 #include <math.h>
 #include <string.h>
 
-#include "eigen3.h"
-#include "gicp_weight.h"
+#include "dist_pass.h"
 #include "knn_device.h"
-#include "pass_device.h"
 
 extern __shared__ __attribute__((aligned(16))) char gicp_smem[];
 
@@ -54,9 +46,7 @@ __device__ __forceinline__ void gicp_cov_finish(const PtF *pts, const PtF me, in
     if (mode == PCR_COV_PLANE) {
         double n[3];
         smallest_eigvec3(c, n);
-        const double s = 1.0 - eps;
-        c[0] = 1.0 - s * n[0] * n[0]; c[1] = -s * n[0] * n[1]; c[2] = -s * n[0] * n[2];
-        c[3] = 1.0 - s * n[1] * n[1]; c[4] = -s * n[1] * n[2]; c[5] = 1.0 - s * n[2] * n[2];
+        plane_cov6(n, eps, c);
     }
     float *dst = cov + 6 * (size_t)pt_orig(me);
 #pragma unroll
@@ -145,18 +135,9 @@ __global__ void __launch_bounds__(256) k_gicp_soa_to_aos(const float *__restrict
     xyz[3 * i] = x[i]; xyz[3 * i + 1] = y[i]; xyz[3 * i + 2] = z[i];
 }
 
-static dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 static pcr_status check_cov_args(int k, int mode, double eps) {
     if (k < 1 || k > KNN_MAX_K) { pcr_set_error("k must be in [1, %d]", KNN_MAX_K); return PCR_ERR_INVALID; }
-    PCR_REQUIRE(mode == PCR_COV_PLANE || mode == PCR_COV_RAW, "mode must be PCR_COV_PLANE or PCR_COV_RAW");
-    PCR_REQUIRE(mode == PCR_COV_RAW || (eps > 0.0 && eps <= 1.0), "eps must be in (0, 1]");
-    return PCR_OK;
-}
-static pcr_status check_finite(const float *v, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-        if (!isfinite(v[i])) { pcr_set_error("invalid argument: covariances must be finite"); return PCR_ERR_INVALID; }
-    return PCR_OK;
+    return check_cov_mode(mode, eps);
 }
 static bool scan_knows_order(const pcr_scan *s) { return !s->sorted || s->order != nullptr; }
 #define GICP_NEED_ORDER "the scan must know the caller's order: PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT"
@@ -192,7 +173,7 @@ extern "C" pcr_status pcr_target_estimate_covariances(pcr_target *t, int k, int 
 extern "C" pcr_status pcr_target_set_covariances(pcr_target *t, const float *cov6) {
     PCR_REQUIRE(t && (cov6 || t->n == 0), "NULL argument");
     PCR_REQUIRE(!t->is_voxel, "covariances belong to point targets");
-    PCR_TRY(check_finite(cov6, 6 * (size_t)t->n));
+    PCR_TRY(check_cov_finite(cov6, 6 * (size_t)t->n));
     pcr_context *ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
@@ -288,7 +269,7 @@ extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode
 extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
     PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
     PCR_REQUIRE(scan_knows_order(s), GICP_NEED_ORDER);
-    PCR_TRY(check_finite(cov6, 6 * (size_t)s->n));
+    PCR_TRY(check_cov_finite(cov6, 6 * (size_t)s->n));
     pcr_context *ctx = s->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
@@ -318,6 +299,21 @@ struct GicpArgs {
     const float *scov;       // scan covariances, device order, 6 floats per point
     const GicpRec *trec;     // target records, cell-sorted: point + covariance in one line
     double *rows;            // [gridDim.x][32]
+
+    // dist_pass.h's view of a match: the record, whole (one line, three 16-byte loads)
+    struct Match { float4 p, c0, c1; };
+    typedef float Res;
+    __device__ __forceinline__ void gather(const LinArgs &, uint32_t j, Match &m) const {
+        const GicpRec *r = trec + j;
+        m.p = r->p; m.c0 = r->c0; m.c1 = r->c1;
+    }
+    __device__ __forceinline__ bool residual(const LinArgs &a, const Match &m, float tx, float ty, float tz, float &dx, float &dy, float &dz) const {
+        return residual_f32<true>(a, m.p, tx, ty, tz, dx, dy, dz);
+    }
+    __device__ __forceinline__ void weight(const PoseK &P, const float cp[6], const Match &m, double m6[6]) const {
+        const float cq[6] = {m.c0.x, m.c0.y, m.c0.z, m.c0.w, m.c1.x, m.c1.y};
+        gicp_weight(P, cp, cq, m6);
+    }
 };
 
 // points per lane in flight.  3: the per-correspondence arithmetic (R Cp R^T, the closed-form inverse, acc_ndt) needs its
@@ -326,70 +322,11 @@ struct GicpArgs {
 #define GICP_W 3
 #endif
 
-// (the weight M6 = (Cq + R Cp R^T)^-1: gicp_weight.h, shared with vgicp.hip)
-__global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) {
-    const PoseK &P = a.hp;                           // host-driven: the pose came by value
-    constexpr int W = GICP_W;
-    double acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < a.n; t0 += W * stride) {
-        uint32_t j[W];
-        float x[W], y[W], z[W];
-        float2 cp[W][3];
-        float4 q[W], cq0[W], cq1[W];
-        bool use[W];
-        // phase A: index, coordinates and covariance of all W points (a point past the end reads the lane's first point)
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const int64_t t = t0 + u * stride;
-            use[u] = t < a.n;
-            const int64_t i = use[u] ? t : t0;
-            j[u] = a.nn_j[i];
-            x[u] = a.sx[i]; y[u] = a.sy[i]; z[u] = a.sz[i];
-            const float2 *c = reinterpret_cast<const float2 *>(ga.scov + 6 * i);
-            cp[u][0] = c[0]; cp[u][1] = c[1]; cp[u][2] = c[2];
-        }
-        reduce_phase();
-#pragma unroll
-        for (int u = 0; u < W; ++u) reduce_pin(j[u]);
-        // phase B: the matched records, one line each (no match: record 0 through a select on the index -- always there --
-        // and skipped in phase C; no branch between the gathers)
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            use[u] = use[u] && j[u] != PCR_NONE;
-            const GicpRec *r = ga.trec + (use[u] ? j[u] : 0u);
-            q[u] = r->p; cq0[u] = r->c0; cq1[u] = r->c1;
-        }
-        reduce_phase();
-        // phase C: residual, gate, weight, sums -- in index order
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (!use[u]) continue;
-            float tx, ty, tz, dx, dy, dz;
-            xform(P, x[u], y[u], z[u], tx, ty, tz);
-            if (!residual_f32<true>(a, q[u], tx, ty, tz, dx, dy, dz)) continue;
-            const float cpv[6] = {cp[u][0].x, cp[u][0].y, cp[u][1].x, cp[u][1].y, cp[u][2].x, cp[u][2].y};
-            const float cqv[6] = {cq0[u].x, cq0[u].y, cq0[u].z, cq0[u].w, cq1[u].x, cq1[u].y};
-            double m6[6];
-            gicp_weight(P, cpv, cqv, m6);
-            acc_ndt(acc, P, (double)x[u], (double)y[u], (double)z[u], m6, (double)dx, (double)dy, (double)dz);
-        }
-    }
-    block_store_partials<false>(acc, ga.rows);
-}
+__global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) { dist_reduce<GICP_W>(a, ga); }
+__global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) { dist_fold(rows, nb, out); }
 
-__global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) {
-    const int e = threadIdx.x;
-    if (e >= 29) return;
-    double s = 0.0;
-    for (int b = 0; b < nb; ++b) s += rows[(size_t)b * 32 + e];
-    out[e] = s;
-}
-
-// search + reduce + fold + 29 doubles back: one stream synchronisation, device blocks from the context's block cache
-pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
+// search + the distribution pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's
+static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
     if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
     LinArgs a;
@@ -397,36 +334,20 @@ pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double m
     PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_ICP, T, max_dist, flags, false));
     for (int i = 0; i < 29; ++i) out[i] = 0.0;
     if (s->n == 0) return PCR_OK;
-    pcr_context *ctx = t->ctx;
-    const int nb = choose_blocks(ctx, s->n);         // n and the device only
-    DevBuf<double> rows, sums;
-    HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
-    GicpArgs ga;
-    ga.scov = s->cov; ga.trec = (const GicpRec *)t->gcov; ga.rows = rows.p;
-    {
-        RoctxRange range("pcr:gicp_reduce");
-        hipLaunchKernelGGL(k_gicp_reduce, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, ga);
-        hipLaunchKernelGGL(k_gicp_fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, sums.p, 29 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    const GicpArgs ga{s->cov, (const GicpRec *)t->gcov, nullptr};
+    return dist_launch(t->ctx, "pcr:gicp_reduce", k_gicp_reduce, k_gicp_fold, a, ga, s->n, out);
 }
 
 extern "C" pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_run_gicp(t, s, T, max_dist, flags, out);
+    return pcr_run_gicp(t, s, PCR_ICP, T, max_dist, flags, out);
 }
 
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over pcr_run_gicp: same gn_step, same trace rows
-static pcr_status gicp_pass(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
-    return pcr_run_gicp(t, s, T, max_dist, flags, out);
-}
+// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                      unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_align_host_loop(gicp_pass, t, s, PCR_ICP, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return pcr_align_host_loop(pcr_run_gicp, t, s, PCR_ICP, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }

@@ -1,9 +1,17 @@
 // The weight of one distribution-to-distribution correspondence, shared by gicp.hip (float32 target covariances) and
-// vgicp.hip (float64 voxel covariances): ONE definition of the order in which R Cp R^T is evaluated.
+// vgicp.hip (float64 voxel covariances): ONE definition of the order in which R Cp R^T is evaluated -- and of the plane
+// regulariser both put on a covariance.
 #pragma once
 
 #include "eigen3.h"
 #include "pass_device.h"
+
+// the plane regulariser C = I - (1 - eps) n n^T as xx xy xz yy yz zz: eigenvalues (eps, 1, 1); the sign of n cancels
+__device__ __forceinline__ void plane_cov6(const double n[3], double eps, double c[6]) {
+    const double s = 1.0 - eps;
+    c[0] = 1.0 - s * n[0] * n[0]; c[1] = -s * n[0] * n[1]; c[2] = -s * n[0] * n[2];
+    c[3] = 1.0 - s * n[1] * n[1]; c[4] = -s * n[1] * n[2]; c[5] = 1.0 - s * n[2] * n[2];
+}
 
 // M6 = (Cq + R Cp R^T)^-1 as xx xy xz yy yz zz, float64.  CQ: the type the target side's covariance is stored in (widened
 // entry by entry before the sum)

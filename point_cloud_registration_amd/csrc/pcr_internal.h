@@ -427,10 +427,6 @@ pcr_status pcr_rows_search(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_
 typedef pcr_status (*pcr_pass_fn)(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double out[29]);
 pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
                                double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
-// ---- gicp.hip: search + k_gicp_reduce + k_gicp_fold (both sides must hold covariances)
-pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]);
-// ---- vgicp.hip: centroid search + k_vgicp_reduce + k_vgicp_fold (a voxel target with covariances, a scan with covariances)
-pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 
 // ---- roctx ranges around the hot-path launches (PCR_ROCTX=1; libroctx64 bound with dlopen, so the

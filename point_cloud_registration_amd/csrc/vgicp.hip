@@ -2,20 +2,16 @@
 // every correspondence -- found and gated exactly as NDT / VPlaneICP find and gate it -- is weighed with
 // M = (Cv + R Cp R^T)^-1, Cv the float64 covariance of the matched voxel, Cp the float32 covariance of the scan point (GICP's:
 // gicp.hip puts them on a scan).  Built BESIDE the hot path like gicp.hip: its own kernels and entry points, no new kind in the
-// templated pass kernels (pass_device.h / gicp_weight.h are included; kernels.hip, rows.hip, gicp.hip, seam64.hip do not change).
+// templated pass kernels (pass_device.h / dist_pass.h are included; kernels.hip, rows.hip, gicp.hip, seam64.hip do not change).
 //
 //   k_vgicp_plane_cov  one thread per kept voxel, key order: C = I - (1 - eps) n n^T from the voxel's normal (st_norm), float64,
 //                      six values xx xy xz yy yz zz.  Eigenvalues (eps, 1, 1); the sign of n cancels.
 //   k_vgicp_cov_out    cell-sorted rows back into key order (the inverse of pcr_permute_rows_f64), for the read-back.
 //   k_vgicp_reduce     sits where k_gicp_reduce sits: behind a full float64 centroid search (pass.hip: pcr_rows_search with
-//                      PCR_VPLANE, which needs the voxel normals only) into a match buffer of the call.  VGICP_W points per lane
-//                      in flight: index, coordinates and scan covariance of all of them (phase A), then the matched centroids
-//                      (32 bytes of `means`) and voxel covariances (48 bytes of `vcov`) with no branch between the gathers
-//                      (phase B), then residual_f64<true> on the loaded centroid, gicp_weight, acc_ndt in index order
-//                      (phase C): nothing is restated here.  One row of 32 doubles per block with plain stores
-//                      (block_store_partials<false>).  No tickets, no atomics.
-//   k_vgicp_fold       one block: thread e < 29 adds rows 0 .. nb-1 in order.  The grid depends on n and the device only, so
-//                      two calls return the same bits.
+//   k_vgicp_fold       PCR_VPLANE, which needs the voxel normals only) into a match buffer of the call.  The distribution pass
+//                      of dist_pass.h (dist_reduce, dist_fold, dist_launch) with VgicpArgs as its target side, VGICP_W points
+//                      per lane in flight: residual_f64<true> on the gathered centroid, gicp_weight, acc_ndt -- nothing is
+//                      restated here.
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -23,17 +19,14 @@
 #include <math.h>
 #include <string.h>
 
-#include "gicp_weight.h"
+#include "dist_pass.h"
 
 // ---- voxel covariances --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_vgicp_plane_cov(const double *__restrict__ norm, int64_t n, double eps, double *out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double n0 = norm[3 * i], n1 = norm[3 * i + 1], n2 = norm[3 * i + 2];
-    const double s = 1.0 - eps;
-    double *c = out + 6 * (size_t)i;
-    c[0] = 1.0 - s * n0 * n0; c[1] = -(s * n0 * n1); c[2] = -(s * n0 * n2);
-    c[3] = 1.0 - s * n1 * n1; c[4] = -(s * n1 * n2); c[5] = 1.0 - s * n2 * n2;
+    const double nv[3] = {norm[3 * i], norm[3 * i + 1], norm[3 * i + 2]};
+    plane_cov6(nv, eps, out + 6 * (size_t)i);
 }
 
 __global__ void __launch_bounds__(256) k_vgicp_cov_out(const double *__restrict__ vcov, int64_t n, const PtD *__restrict__ means, double *out) {
@@ -44,21 +37,17 @@ __global__ void __launch_bounds__(256) k_vgicp_cov_out(const double *__restrict_
     for (int k = 0; k < 6; ++k) out[6 * i + k] = vcov[6 * (size_t)j + k];
 }
 
-static dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 extern "C" pcr_status pcr_target_voxels_set_covariances(pcr_target *t, int mode, double eps, const double *cov6_or_null) {
     PCR_REQUIRE(t, "NULL argument");
     if (!t->is_voxel) { pcr_set_error("voxel covariances belong to voxel targets"); return PCR_ERR_NO_TARGET; }
     const int cols6[6] = {0, 1, 2, 3, 4, 5}, cols9[6] = {0, 1, 2, 4, 5, 8};
     if (!cov6_or_null) {
-        PCR_REQUIRE(mode == PCR_COV_PLANE || mode == PCR_COV_RAW, "mode must be PCR_COV_PLANE or PCR_COV_RAW");
-        PCR_REQUIRE(mode == PCR_COV_RAW || (eps > 0.0 && eps <= 1.0), "eps must be in (0, 1]");
+        PCR_TRY(check_cov_mode(mode, eps));
         if (mode == PCR_COV_PLANE && !t->st_norm) { pcr_set_error("voxel target does not hold 'norm'"); return PCR_ERR_NO_TARGET; }
         if (mode == PCR_COV_RAW && !t->st_cov) { pcr_set_error("voxel target does not hold 'cov'"); return PCR_ERR_NO_TARGET; }
     } else {
         // (checked before anything of the target changes: a refused set leaves the old covariances)
-        for (size_t i = 0; i < 6 * (size_t)t->n; ++i)
-            if (!isfinite(cov6_or_null[i])) { pcr_set_error("invalid argument: covariances must be finite"); return PCR_ERR_INVALID; }
+        PCR_TRY(check_cov_finite(cov6_or_null, 6 * (size_t)t->n));
     }
     pcr_context *ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -112,6 +101,23 @@ struct VgicpArgs {
     const float *scov;       // scan covariances, device order, 6 floats per point
     const double *vcov;      // voxel covariances, cell-sorted, 6 doubles per voxel (16-byte aligned rows)
     double *rows;            // [gridDim.x][32]
+
+    // dist_pass.h's view of a match: the centroid (32 bytes of `means`, as halves) and the voxel covariance (48 bytes of vcov)
+    struct Match { double2 m0, m1, cv[3]; };
+    typedef double Res;
+    __device__ __forceinline__ void gather(const LinArgs &a, uint32_t j, Match &m) const {
+        const double2 *mp = reinterpret_cast<const double2 *>(a.means + j);
+        const double2 *cq = reinterpret_cast<const double2 *>(vcov + 6 * (size_t)j);
+        m.m0 = mp[0]; m.m1 = mp[1];
+        m.cv[0] = cq[0]; m.cv[1] = cq[1]; m.cv[2] = cq[2];
+    }
+    __device__ __forceinline__ bool residual(const LinArgs &a, const Match &m, float tx, float ty, float tz, double &dx, double &dy, double &dz) const {
+        return residual_f64<true>(a, make_double4(m.m0.x, m.m0.y, m.m1.x, m.m1.y), tx, ty, tz, dx, dy, dz);
+    }
+    __device__ __forceinline__ void weight(const PoseK &P, const float cp[6], const Match &m, double m6[6]) const {
+        const double cq[6] = {m.cv[0].x, m.cv[0].y, m.cv[1].x, m.cv[1].y, m.cv[2].x, m.cv[2].y};
+        gicp_weight(P, cp, cq, m6);
+    }
 };
 
 // points per lane in flight.  2: a point carries a float64 centroid (8 registers) and a float64 Cv (12) through phase B where
@@ -120,74 +126,11 @@ struct VgicpArgs {
 #define VGICP_W 2
 #endif
 
-__global__ void __launch_bounds__(256) k_vgicp_reduce(const LinArgs a, const VgicpArgs va) {
-    const PoseK &P = a.hp;                           // host-driven: the pose came by value
-    constexpr int W = VGICP_W;
-    double acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < a.n; t0 += W * stride) {
-        uint32_t j[W];
-        float x[W], y[W], z[W];
-        float2 cp[W][3];
-        double2 m0[W], m1[W], cv[W][3];
-        bool use[W];
-        // phase A: index, coordinates and covariance of all W points (a point past the end reads the lane's first point)
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const int64_t t = t0 + u * stride;
-            use[u] = t < a.n;
-            const int64_t i = use[u] ? t : t0;
-            j[u] = a.nn_j[i];
-            x[u] = a.sx[i]; y[u] = a.sy[i]; z[u] = a.sz[i];
-            const float2 *c = reinterpret_cast<const float2 *>(va.scov + 6 * i);
-            cp[u][0] = c[0]; cp[u][1] = c[1]; cp[u][2] = c[2];
-        }
-        reduce_phase();
-#pragma unroll
-        for (int u = 0; u < W; ++u) reduce_pin(j[u]);
-        // phase B: the matched centroids and voxel covariances (no match: voxel 0 through a select on the index -- always
-        // there -- and skipped in phase C; no branch between the gathers)
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            use[u] = use[u] && j[u] != PCR_NONE;
-            const size_t jj = use[u] ? j[u] : 0u;
-            const double2 *mp = reinterpret_cast<const double2 *>(a.means + jj);
-            const double2 *cq = reinterpret_cast<const double2 *>(va.vcov + 6 * jj);
-            m0[u] = mp[0]; m1[u] = mp[1];
-            cv[u][0] = cq[0]; cv[u][1] = cq[1]; cv[u][2] = cq[2];
-        }
-        reduce_phase();
-        // phase C: residual, gate, weight, sums -- in index order
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (!use[u]) continue;
-            float tx, ty, tz;
-            double dx, dy, dz;
-            xform(P, x[u], y[u], z[u], tx, ty, tz);
-            const PtD m = make_double4(m0[u].x, m0[u].y, m1[u].x, m1[u].y);
-            if (!residual_f64<true>(a, m, tx, ty, tz, dx, dy, dz)) continue;
-            const float cpv[6] = {cp[u][0].x, cp[u][0].y, cp[u][1].x, cp[u][1].y, cp[u][2].x, cp[u][2].y};
-            const double cvv[6] = {cv[u][0].x, cv[u][0].y, cv[u][1].x, cv[u][1].y, cv[u][2].x, cv[u][2].y};
-            double m6[6];
-            gicp_weight(P, cpv, cvv, m6);
-            acc_ndt(acc, P, (double)x[u], (double)y[u], (double)z[u], m6, dx, dy, dz);
-        }
-    }
-    block_store_partials<false>(acc, va.rows);
-}
+__global__ void __launch_bounds__(256) k_vgicp_reduce(const LinArgs a, const VgicpArgs va) { dist_reduce<VGICP_W>(a, va); }
+__global__ void __launch_bounds__(64) k_vgicp_fold(const double *__restrict__ rows, int nb, double *out) { dist_fold(rows, nb, out); }
 
-__global__ void __launch_bounds__(64) k_vgicp_fold(const double *__restrict__ rows, int nb, double *out) {
-    const int e = threadIdx.x;
-    if (e >= 29) return;
-    double s = 0.0;
-    for (int b = 0; b < nb; ++b) s += rows[(size_t)b * 32 + e];
-    out[e] = s;
-}
-
-// search + reduce + fold + 29 doubles back: one stream synchronisation, device blocks from the context's block cache
-pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
+// centroid search + the distribution pass.  A pcr_pass_fn: `kind` is not read, the search is VPlaneICP's
+static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
     if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
     if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
@@ -203,35 +146,20 @@ pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, const double T[16], double 
     DevBuf<uint32_t> nn;
     PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_VPLANE, T, max_dist, flags, false));
     if (s->n == 0) return PCR_OK;
-    const int nb = choose_blocks(ctx, s->n);         // n and the device only
-    DevBuf<double> rows, sums;
-    HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
-    VgicpArgs va;
-    va.scov = s->cov; va.vcov = t->vcov; va.rows = rows.p;
-    {
-        RoctxRange range("pcr:vgicp_reduce");
-        hipLaunchKernelGGL(k_vgicp_reduce, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, va);
-        hipLaunchKernelGGL(k_vgicp_fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, sums.p, 29 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    const VgicpArgs va{s->cov, t->vcov, nullptr};
+    return dist_launch(ctx, "pcr:vgicp_reduce", k_vgicp_reduce, k_vgicp_fold, a, va, s->n, out);
 }
 
 extern "C" pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_run_vgicp(t, s, T, max_dist, flags, out);
+    return pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, out);
 }
 
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over pcr_run_vgicp: same gn_step, same trace rows
-static pcr_status vgicp_pass(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
-    return pcr_run_vgicp(t, s, T, max_dist, flags, out);
-}
+// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                       unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_align_host_loop(vgicp_pass, t, s, PCR_VPLANE, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return pcr_align_host_loop(pcr_run_vgicp, t, s, PCR_VPLANE, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }

@@ -8,6 +8,8 @@ point and of the scan point: float32 ``(N, 6)`` = xx xy xz yy yz zz, given by th
 nearest neighbours (``regularization="plane"``: ``I - (1 - eps) n n^T``, eigenvalues ``(eps, 1, 1)``; ``"raw"``: the k-NN
 covariance itself).  A singular ``Cq + R Cp R^T`` (determinant exactly 0) is divided by 1e6 instead of its determinant, the
 rule of the voxel targets' ``calc_icov``: such a pair contributes next to nothing instead of Inf / NaN.
+
+``DistributionPass`` is what ``GICP`` and ``VGICP`` (``vgicp.py``) share: everything but the target side.
 """
 
 import numpy as np
@@ -51,12 +53,15 @@ class ScanCovariances:
         return scan
 
 
-class GICP(ScanCovariances, Registration):
-    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_gicp_*)
+class DistributionPass(ScanCovariances, Registration):
+    """The distribution-to-distribution pass behind ``GICP`` and ``VGICP``.  A subclass supplies the target side:
+    ``set_target``, ``covariance``, its pair of ``_capi`` entry points and ``_match`` for the per-point loop."""
+    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_gicp_* / pcr_vgicp_*)
+    _capi_linearize = _capi_align = None
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
         if kw.get("devices") is not None or kw.get("comm") is not None:
-            raise ValueError("GICP runs on one GPU of one process: not with comm= or devices=")
+            raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
         if regularization not in _MODES:
             raise ValueError(f"regularization must be one of {sorted(_MODES)}, not {regularization!r}")
         if not 1 <= int(k) <= 64:
@@ -67,6 +72,89 @@ class GICP(ScanCovariances, Registration):
         self.eps = float(eps)
         self.regularization = regularization
         self._covariance = None
+
+    # -- passes ----------------------------------------------------------------------------------
+    def calc_H_g_e2(self, cur_T, source, source_cov=None, weights=None):
+        """Hessian (6x6), gradient (6) and squared (Mahalanobis) error at ``cur_T``.  ``source_cov``: (N, 6) or (N, 3, 3) in
+        the order of ``source``; default: estimated once per uploaded scan with this object's ``k`` / ``regularization``."""
+        if weights is not None:
+            self._unsupported("weights=")
+        scan = self._gicp_scan(source, source_cov)
+        return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
+
+    def align(self, source, init_T=np.eye(4), verbose=False, source_cov=None):
+        if self.is_target_set() is False:
+            raise ValueError("Target is not set.")
+        scan = self._gicp_scan(source, source_cov, fresh=True)
+        cur_T = np.array(init_T, dtype=np.float64)
+        if self._native_loop and not verbose:
+            T, iters, trace = self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
+                                               self._flags, want_trace=True)
+            self.last_iterations = iters
+            if iters:
+                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
+            return T
+        it = 0
+        for it in range(self.max_iter):
+            H, g, e2 = self._linearize(cur_T, scan)
+            if verbose:
+                print(f"iter {it}, error {e2}")
+            dx = -np.linalg.solve(H, g)
+            if np.linalg.norm(dx) < self.tol:
+                break
+            cur_T = plus(cur_T, dx)
+        self.last_iterations = it + 1 if self.max_iter > 0 else 0
+        return cur_T
+
+    def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_cov=None):
+        """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
+        (``_match``) and covariances, the inverse by ``numpy.linalg.inv``."""
+        cur_T = np.asarray(cur_T, dtype=np.float64)
+        R = cur_T[:3, :3]
+        source = np.asarray(source)
+        Cp = self.source_covariance(source) if source_cov is None else _capi.cov6(source_cov)
+        Cq = self.covariance
+        keep, idx, res = self._match(_xform32(cur_T, source.astype(np.float32)))
+        H, g, e2 = np.zeros((6, 6)), np.zeros(6), 0.0
+        for i, j, d in zip(keep, idx, res):
+            M = np.linalg.inv(_full(Cq[j]) + R @ _full(Cp[i]) @ R.T)
+            J = np.hstack([np.eye(3), -R @ skew(np.asarray(source[i], dtype=np.float64))])
+            H += J.T @ M @ J
+            g += J.T @ M @ d
+            e2 += d @ M @ d
+        return H, g, e2
+
+    def _match(self, src_trans):
+        """(scan points that pass the gate, the target element each is matched to, its float64 residual) for the
+        transformed float32 scan."""
+        raise NotImplementedError
+
+    # -- out of scope ----------------------------------------------------------------------------
+    def linearize(self, *a, **kw):
+        self._unsupported("linearize()")
+
+    def coreset(self, *a, **kw):
+        self._unsupported("coreset()")
+
+    def align_batch(self, *a, **kw):
+        self._unsupported("align_batch()")
+
+    def calc_H_g_e2_batch(self, *a, **kw):
+        self._unsupported("calc_H_g_e2_batch()")
+
+    # -- internals -------------------------------------------------------------------------------
+    def _unsupported(self, what):
+        raise NotImplementedError(f"{type(self).__name__} does not support {what}")
+
+    def _linearize(self, cur_T, scan):
+        out = self._capi_linearize(self._target, scan, cur_T, self._max_dist(), self._flags)
+        H, g, e2, cnt = _capi.unpack29(out)
+        self.last_correspondences = cnt
+        return H, g, e2
+
+
+class GICP(DistributionPass):
+    _capi_linearize, _capi_align = staticmethod(_capi.gicp_linearize), staticmethod(_capi.gicp_align)
 
     # -- target ----------------------------------------------------------------------------------
     def set_target(self, target, kdree=None, cov=None):
@@ -96,78 +184,11 @@ class GICP(ScanCovariances, Registration):
             self._covariance = self._target.get_covariances()
         return self._covariance
 
-    # -- passes ----------------------------------------------------------------------------------
-    def calc_H_g_e2(self, cur_T, source, source_cov=None, weights=None):
-        """Hessian (6x6), gradient (6) and squared (Mahalanobis) error at ``cur_T``.  ``source_cov``: (N, 6) or (N, 3, 3) in
-        the order of ``source``; default: estimated once per uploaded scan with this object's ``k`` / ``regularization``."""
-        if weights is not None:
-            raise NotImplementedError("GICP does not support weights=")
-        scan = self._gicp_scan(source, source_cov)
-        return self._gicp_linearize(np.asarray(cur_T, dtype=np.float64), scan)
-
-    def align(self, source, init_T=np.eye(4), verbose=False, source_cov=None):
-        if self.is_target_set() is False:
-            raise ValueError("Target is not set.")
-        scan = self._gicp_scan(source, source_cov, fresh=True)
-        cur_T = np.array(init_T, dtype=np.float64)
-        if self._native_loop and not verbose:
-            T, iters, trace = _capi.gicp_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
-                                               self._flags, want_trace=True)
-            self.last_iterations = iters
-            if iters:
-                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
-            return T
-        it = 0
-        for it in range(self.max_iter):
-            H, g, e2 = self._gicp_linearize(cur_T, scan)
-            if verbose:
-                print(f"iter {it}, error {e2}")
-            dx = -np.linalg.solve(H, g)
-            if np.linalg.norm(dx) < self.tol:
-                break
-            cur_T = plus(cur_T, dx)
-        self.last_iterations = it + 1 if self.max_iter > 0 else 0
-        return cur_T
-
-    def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_cov=None):
-        """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
-        (``self.kdtree.query``) and covariances, the inverse by ``numpy.linalg.inv``."""
-        cur_T = np.asarray(cur_T, dtype=np.float64)
-        R = cur_T[:3, :3]
-        source = np.asarray(source)
-        Cp = self.source_covariance(source) if source_cov is None else _capi.cov6(source_cov)
-        Cq = self.covariance
-        src_trans = _xform32(cur_T, source.astype(np.float32))
+    def _match(self, src_trans):
+        # ICP's: float32 residual against the matched point, float32 gate (``self.kdtree.query``)
         dist, idx = self.kdtree.query(src_trans)
-        H, g, e2 = np.zeros((6, 6)), np.zeros(6), 0.0
-        for i in np.nonzero(dist < np.float32(self.max_dist))[0]:
-            M = np.linalg.inv(_full(Cq[idx[i]]) + R @ _full(Cp[i]) @ R.T)
-            J = np.hstack([np.eye(3), -R @ skew(np.asarray(source[i], dtype=np.float64))])
-            d = (src_trans[i] - self.target[idx[i]]).astype(np.float64)
-            H += J.T @ M @ J
-            g += J.T @ M @ d
-            e2 += d @ M @ d
-        return H, g, e2
-
-    # -- out of scope ----------------------------------------------------------------------------
-    def linearize(self, *a, **kw):
-        raise NotImplementedError("GICP does not support linearize()")
-
-    def coreset(self, *a, **kw):
-        raise NotImplementedError("GICP does not support coreset()")
-
-    def align_batch(self, *a, **kw):
-        raise NotImplementedError("GICP does not support align_batch()")
-
-    def calc_H_g_e2_batch(self, *a, **kw):
-        raise NotImplementedError("GICP does not support calc_H_g_e2_batch()")
-
-    # -- internals -------------------------------------------------------------------------------
-    def _gicp_linearize(self, cur_T, scan):
-        out = _capi.gicp_linearize(self._target, scan, cur_T, self._max_dist(), self._flags)
-        H, g, e2, cnt = _capi.unpack29(out)
-        self.last_correspondences = cnt
-        return H, g, e2
+        keep = np.nonzero(dist < np.float32(self.max_dist))[0]
+        return keep, idx[keep], (src_trans[keep] - self.target[idx[keep]]).astype(np.float64)
 
 
 def _xform32(T, p):

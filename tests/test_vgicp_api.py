@@ -18,6 +18,11 @@ def test_exported():
     assert (v.voxel_size, v.max_dist, v.k, v.regularization) == (0.5, 2.0, 20, "raw")
     # the scan side is GICP's, not a copy of it
     assert pcr.VGICP._gicp_scan is pcr.GICP._gicp_scan and pcr.VGICP.source_covariance is pcr.GICP.source_covariance
+    # ... and the pass is the base class's: no per-class copies of align, calc_H_g_e2 or the stubs
+    from point_cloud_registration_amd.gicp import DistributionPass
+    for name in ("align", "calc_H_g_e2", "linearize", "coreset", "align_batch", "calc_H_g_e2_batch"):
+        assert getattr(pcr.VGICP, name) is getattr(DistributionPass, name) is getattr(pcr.GICP, name), name
+        assert name not in vars(pcr.VGICP) and name not in vars(pcr.GICP), name
 
 
 def test_refusals_without_a_device():
