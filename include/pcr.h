@@ -438,6 +438,30 @@ PCR_API pcr_status pcr_knn_query(pcr_target *t, const float *q, int64_t m, int k
 PCR_API pcr_status pcr_nn_query_dd(pcr_target *t, const double *q, int64_t m, double r_max, double *dist, int64_t *idx);
 PCR_API pcr_status pcr_knn_query_f64(pcr_target *t, const double *q, int64_t m, int k, double *dist, int64_t *idx);
 
+/* ---- fixed-radius search over a point target (no reference counterpart) -----------------
+ * Everything within r of a query, exactly: a point is a neighbour iff the distance pcr_knn_query (pcr_knn_query_f64 for the
+ * _dd pair) would report for the pair is <= r -- sqrtf of the float32 squared distance against r in float32, sqrt of
+ * (dx*dx + dy*dy) + dz*dz against r in float64 -- so r = 0 finds coincident points.  A query with a NaN or infinite
+ * coordinate has no neighbours.  Two calls, CSR layout: pcr_radius_count writes count[m]; the caller forms
+ * offsets[m + 1] = 0 and the running sums of count; pcr_radius_query fills dist / idx [offsets[i], offsets[i + 1]) with the
+ * neighbours of query i ordered by (squared distance, index) ascending, the k-NN's order; idx indexes the array given to
+ * pcr_target_points_create.  The same call twice returns the same bits.
+ * PCR_ERR_INVALID: r negative, NaN or infinite; a voxel target; the _dd pair on a point target without float64 coordinates
+ * (pcr_target_points_set_f64); offsets that do not start at 0, decrease, or give a segment a length other than what the
+ * search finds -- dist and idx are then left untouched.  m = 0 returns PCR_OK; an empty target counts zero everywhere.
+ * A call holds at most PCR_RADIUS_CHUNK entries (environment, default 2^26) on the device at a time: queries are taken in
+ * chunks of consecutive queries whose segments fit, a larger query alone; the results do not depend on the chunking.     */
+PCR_API pcr_status pcr_radius_count(pcr_target *t, const float *q, int64_t m, float r, int64_t *count);
+PCR_API pcr_status pcr_radius_query(pcr_target *t, const float *q, int64_t m, float r, const int64_t *offsets, float *dist, int64_t *idx);
+PCR_API pcr_status pcr_radius_count_dd(pcr_target *t, const double *q, int64_t m, double r, int64_t *count);
+PCR_API pcr_status pcr_radius_query_dd(pcr_target *t, const double *q, int64_t m, double r, const int64_t *offsets, double *dist,
+                                       int64_t *idx);
+/* The mean distance from every point of a point target to its k nearest neighbours within the target (1 <= k <= 64; the
+ * point itself included, as for normals and covariances): the float32 distances pcr_knn_query reports, summed in float64
+ * nearest first and divided by the number found.  mean_out: n doubles in the order of the array the target was created
+ * from.  Always searches the float32 copy of the points.                                                              */
+PCR_API pcr_status pcr_knn_mean_distance(pcr_target *t, int k, double *mean_out);
+
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the
  * context's stream; pcr_profile_read drains them (synchronises) and reports per-kernel

@@ -82,6 +82,12 @@ PROTOTYPES = {
     "pcr_knn_query": (C.c_int, [_vp, _f32p, C.c_int64, C.c_int, _f32p, _i64p]),
     "pcr_nn_query_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _f64p, _i64p]),
     "pcr_knn_query_f64": (C.c_int, [_vp, _f64p, C.c_int64, C.c_int, _f64p, _i64p]),
+    # fixed-radius search and the mean k-NN distance (include/pcr.h, outliers.py)
+    "pcr_radius_count": (C.c_int, [_vp, _f32p, C.c_int64, C.c_float, _i64p]),
+    "pcr_radius_query": (C.c_int, [_vp, _f32p, C.c_int64, C.c_float, _i64p, _f32p, _i64p]),
+    "pcr_radius_count_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _i64p]),
+    "pcr_radius_query_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _i64p, _f64p, _i64p]),
+    "pcr_knn_mean_distance": (C.c_int, [_vp, C.c_int, _f64p]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -254,6 +260,21 @@ def check(status):
     if status == PCR_ERR_NO_TARGET:
         raise ValueError(msg)
     raise PcrError(f"libpcr_hip status {status}: {msg}")
+
+
+def check_radius(r):
+    """A search radius as a float: finite and >= 0, else ValueError (checked before the GPU is touched)."""
+    r = float(r)
+    if not (np.isfinite(r) and r >= 0):
+        raise ValueError(f"radius must be finite and >= 0, got {r}")
+    return r
+
+
+def check_k(k):
+    """1 <= k <= 64, the library's own bound and message (csrc/knn_normals.hip: check_k)."""
+    if not 1 <= int(k) <= 64:
+        raise ValueError("k must be in [1, 64]")
+    return int(k)
 
 
 def has_dev_kernels():
@@ -653,6 +674,49 @@ class Target:
         idx = np.empty((m, k), np.int64)
         check(lib().pcr_knn_query(self.handle, q, m, int(k), dist, idx))
         return dist, idx
+
+    # -- fixed-radius search (include/pcr.h): CSR results, float64 on a point target that holds float64 coordinates
+    def _radius_args(self, q, r):
+        r = check_radius(r)
+        f64 = self.searches_f64()
+        q = np.ascontiguousarray(q, dtype=np.float64 if f64 else np.float32)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("points must have shape (M, 3)")
+        return q, r, f64
+
+    def radius_count(self, q, r):
+        """Neighbours within ``r`` of every query: (M,) int64.  A target that answers in float64 takes every query array to
+        float64 (exact for float32) and searches the float64 coordinates; any other rounds the queries to float32."""
+        q, r, f64 = self._radius_args(q, r)
+        count = np.empty(q.shape[0], np.int64)
+        check((lib().pcr_radius_count_dd if f64 else lib().pcr_radius_count)(self.handle, q, q.shape[0], r, count))
+        return count
+
+    def radius_query(self, q, r, offsets=None, out=None):
+        """-> (dist, idx, offsets): the neighbours of query i at [offsets[i], offsets[i + 1]), ordered by (squared distance,
+        index).  ``offsets`` (M + 1 int64, the running sums of ``radius_count``) is computed when not given; ``out`` =
+        (dist, idx) arrays to fill.  Offsets that do not match what the search finds raise ValueError and leave ``out`` as
+        it was."""
+        q, r, f64 = self._radius_args(q, r)
+        if offsets is None:
+            offsets = np.zeros(q.shape[0] + 1, np.int64)
+            np.cumsum(self.radius_count(q, r), out=offsets[1:])
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.shape != (q.shape[0] + 1,):
+            raise ValueError("offsets must have M + 1 entries")
+        total = max(int(offsets[-1]), 0)
+        dist, idx = out if out is not None else (np.empty(total, np.float64 if f64 else np.float32), np.empty(total, np.int64))
+        if dist.dtype != (np.float64 if f64 else np.float32) or idx.dtype != np.int64 or len(dist) < total or len(idx) < total:
+            raise ValueError("out arrays do not fit the offsets")
+        check((lib().pcr_radius_query_dd if f64 else lib().pcr_radius_query)(self.handle, q, q.shape[0], r, offsets, dist, idx))
+        return dist, idx, offsets
+
+    def knn_mean_distance(self, k):
+        """Mean distance of every point to its k nearest neighbours within the target (itself included): (N,) float64 in
+        the caller's order, over the float32 copy of the points."""
+        out = np.empty(self.size(), np.float64)
+        check(lib().pcr_knn_mean_distance(self.handle, int(k), out))
+        return out
 
     def close(self):
         if getattr(self, "handle", None) and not _shutdown and not getattr(self, "_borrowed", False):

@@ -1,0 +1,486 @@
+// Exact fixed-radius search over a point target's cell grid, and the mean k-NN distance of a cloud's own points.
+//
+//   pcr_radius_count / _query        float32 queries against the float32 records (gf / pts)
+//   pcr_radius_count_dd / _query_dd  float64 queries against the float64 coordinates (gq / pts64)
+//   pcr_knn_mean_distance            k_knn_mean_dist<REG>, sibling of k_gicp_cov / k_knn_normals
+//
+// One lane = one query, no atomics, the grid depends on the query count only.  k_radius<Real, MODE> walks the cell box of the
+// query's ball: MODE 0 counts the members, MODE 1 writes them into the lane's own segment [off[i], off[i + 1]) of the
+// caller's CSR layout, every store guarded by the segment's length; a lane that finds more or fewer members than its segment
+// holds raises one flag word (a plain store, every lane the same value), which the host reads before it copies anything out.
+//
+// Membership is decided by the distance pcr_knn_query / pcr_knn_query_f64 would report for the pair:
+//   float32   d2 = dist2_f32(q - p) (nn_device.h), member iff __builtin_sqrtf(d2) <= r
+//   float64   d2 = (dx*dx + dy*dy) + dz*dz, no contraction, member iff sqrt(d2) <= r
+// so r == 0 finds coincident points and a query with a non-finite coordinate finds nothing.
+//
+// Each segment is then ordered by (d2, original index) ascending -- the k-NN's order, by d2 and not by the rounded distance:
+//   float32   one key (bits(d2) << 32) | orig per entry, rocprim::segmented_radix_sort_keys, k_radius_unpack
+//   float64   two stable segmented passes: by original index, then by the bits of d2
+// Keys are unique within a segment (float32) or tied only between passes that are stable (float64): two calls return the
+// same bits.
+//
+// The float64 walk is s64_ball_walk (seam64_device.h) with a counting / emitting sink.  The float32 walk below has its form:
+// slabs, rows skipped by their (y, z) gap, each row's x range clipped by sqrt(B - dyz2) + slack, cells clamped into the grid,
+// records fetched KNN_BATCH at a time and none past the end of a range offered (knn_scan_range's rule).  A ball that misses
+// the grid box returns before the first row look-up: nothing here counts rings from a far query's own cell (seam64.hip).
+//
+// Device memory: a call holds at most PCR_RADIUS_CHUNK entries (default 2^26) at a time; queries are taken in chunks of
+// consecutive queries whose segments fit, a single larger query as a chunk of its own.  Entries never move between
+// segments, so the results do not depend on the chunking.
+#include <float.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <rocprim/rocprim.hpp>
+
+#include "seam64_device.h"
+
+#define RAD_BLOCK 64
+#define RAD_ROWS 4           // rows whose cell_start entries are requested together
+
+extern __shared__ __attribute__((aligned(16))) char rad_smem[];
+
+// ---- membership and the sinks ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rad_member(float d2, float r) { return __builtin_sqrtf(d2) <= r; }
+__device__ __forceinline__ bool rad_member(double d2, double r) { return __builtin_sqrt(d2) <= r; }
+// an upper bound on the d2 of every member (pruning and the pre-test only; rad_member decides).  The smallest normal number
+// covers radii whose square is subnormal.
+__device__ __forceinline__ float rad_bound2(float r) { return r * r * 1.00001f + FLT_MIN; }
+__device__ __forceinline__ double rad_bound2(double r) { const double rr = r * 1.0000001; return rr * rr + DBL_MIN; }
+
+__device__ __forceinline__ uint64_t rad_key(float d2, uint32_t o) { return ((uint64_t)__float_as_uint(d2) << 32) | o; }
+__device__ __forceinline__ uint64_t rad_key(double d2, uint32_t) { return (uint64_t)__double_as_longlong(d2); }
+
+template <typename Real, int MODE>
+struct RadSink {
+    Real r, b2;
+    uint32_t cnt, len;
+    uint64_t *keys;      // the lane's segment: float32 (bits(d2) << 32) | orig; float64 bits(d2) ...
+    uint32_t *vals;      // ... and orig (float64 only)
+    __device__ __forceinline__ Real bound() const { return b2; }
+    __device__ __forceinline__ void offer(Real d2, uint32_t, uint32_t o) {
+        if (d2 <= b2 && rad_member(d2, r)) {                               // (NaN fails the pre-test)
+            if (MODE == 1 && cnt < len) {
+                keys[cnt] = rad_key(d2, o);
+                if (sizeof(Real) == 8) vals[cnt] = o;
+            }
+            ++cnt;
+        }
+    }
+};
+
+// ---- the float32 ball walk ------------------------------------------------------------------------------------------------
+template <typename SINK>
+__device__ __forceinline__ void rad_scan_f32(SINK &S, const PtF *__restrict__ pts, uint32_t s, uint32_t e, float qx, float qy, float qz) {
+    for (uint32_t j = s; j < e; j += KNN_BATCH) {
+        PtF p[KNN_BATCH];
+#pragma unroll
+        for (int u = 0; u < KNN_BATCH; ++u) p[u] = pts[j + u];
+#pragma unroll
+        for (int u = 0; u < KNN_BATCH; ++u) {
+            if (j + u < e) {
+                const float dx = qx - p[u].x, dy = qy - p[u].y, dz = qz - p[u].z;
+                S.offer(dist2_f32(dx, dy, dz), j + u, pt_orig(p[u]));
+            }
+        }
+    }
+}
+
+// |q - p| >= this for every record of cell c of one axis (a record lies within `slack` of its cell)
+__device__ __forceinline__ float rad_cell_gap(const Geom<float> &g, float q, float o, int c) {
+    const float lo = (o + (float)c * g.h) - g.slack, hi = (o + (float)(c + 1) * g.h) + g.slack;
+    return fmaxf(fmaxf(lo - q, q - hi), 0.f);
+}
+// the cell of a coordinate, NOT clamped into the grid (NaN: far below)
+__device__ __forceinline__ int rad_cell(const Geom<float> &g, float v, float o) {
+    return (int)floorf(fminf(fmaxf((v - o) * g.inv_h, -1.0e9f), 1.0e9f));
+}
+
+template <typename SINK>
+__device__ __forceinline__ void rad_ball_walk(const Geom<float> &g, const PtF *__restrict__ pts, const uint32_t *__restrict__ cs,
+                                              float qx, float qy, float qz, float r, SINK &S) {
+    const float lim = 1.0e9f;
+    // g.slack covers roundings at the magnitude of the grid's own coordinates; a query far from the grid rounds at its own
+    const float pad = g.slack + 1.0e-6f * (fmaxf(fmaxf(fabsf(qx), fabsf(qy)), fabsf(qz)) + r);
+    const float R = r + pad;
+    int xl = rad_cell(g, qx - R, g.ox), xh = rad_cell(g, qx + R, g.ox);
+    int yl = rad_cell(g, qy - R, g.oy), yh = rad_cell(g, qy + R, g.oy);
+    int zl = rad_cell(g, qz - R, g.oz), zh = rad_cell(g, qz + R, g.oz);
+    if (xl > g.nx - 1 || xh < 0 || yl > g.ny - 1 || yh < 0 || zl > g.nz - 1 || zh < 0) return;       // the ball misses the grid box
+    xl = max(xl, 0); xh = min(xh, g.nx - 1);
+    yl = max(yl, 0); yh = min(yh, g.ny - 1);
+    zl = max(zl, 0); zh = min(zh, g.nz - 1);
+    const float B = S.bound();
+    for (int z = zl; z <= zh; ++z) {
+        const float dzm = rad_cell_gap(g, qz, g.oz, z);
+        const float dz2 = dzm * dzm;
+        if (dz2 > B) continue;
+        for (int y0 = yl; y0 <= yh; y0 += RAD_ROWS) {
+            uint32_t s_[RAD_ROWS], e_[RAD_ROWS];
+#pragma unroll
+            for (int u = 0; u < RAD_ROWS; ++u) {
+                const int y = min(y0 + u, yh);
+                const float dym = rad_cell_gap(g, qy, g.oy, y);
+                const float dyz2 = dz2 + dym * dym;
+                int x0 = xl, x1 = xh;
+                const float xr = __builtin_sqrtf(fmaxf(B - dyz2, 0.f)) + pad;
+                const float a = (qx - xr - g.ox) * g.inv_h, b = (qx + xr - g.ox) * g.inv_h;
+                if (a > (float)x0) x0 = (int)floorf(fminf(a, lim));
+                if (b < (float)x1) x1 = (int)floorf(fmaxf(b, -lim));
+                const bool live = y0 + u <= yh && dyz2 <= B && x0 <= x1;
+                x0 = min(max(x0, 0), g.nx - 1); x1 = min(max(x1, 0), g.nx - 1);      // (a dead row is still addressed)
+                const size_t row = ((size_t)z * (size_t)g.ny + (size_t)y) * (size_t)g.nx;
+                const uint32_t s0 = cs[row + x0] & g.cs_mask, e0 = cs[row + x1 + 1] & g.cs_mask;
+                s_[u] = s0; e_[u] = live ? e0 : s0;
+            }
+#pragma unroll
+            for (int u = 0; u < RAD_ROWS; ++u) rad_scan_f32(S, pts, s_[u], e_[u], qx, qy, qz);
+        }
+    }
+}
+template <typename SINK>
+__device__ __forceinline__ void rad_ball_walk(const Geom<double> &g, const PtD *__restrict__ pts, const uint32_t *__restrict__ cs,
+                                              double qx, double qy, double qz, double r, SINK &S) {
+    s64_ball_walk(g, pts, cs, qx, qy, qz, r * 1.0000001 + g.slack, S);
+}
+
+template <typename Real> struct RadPt;
+template <> struct RadPt<float> { typedef PtF type; };
+template <> struct RadPt<double> { typedef PtD type; };
+
+// MODE 0: count[i] = members of query i.  MODE 1: the members into keys / vals at [off[i], off[i + 1]) in walk order; *flag = 1
+// when a lane's count is not its segment's length.
+template <typename Real, int MODE>
+__global__ void __launch_bounds__(RAD_BLOCK) k_radius(Geom<Real> g, const typename RadPt<Real>::type *pts, const uint32_t *cs, const Real *q,
+                                                      int64_t m, Real r, int64_t *count, const uint32_t *off, uint64_t *keys, uint32_t *vals,
+                                                      uint32_t *flag) {
+    const int64_t i = (int64_t)blockIdx.x * RAD_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    const Real qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
+    RadSink<Real, MODE> S;
+    S.r = r; S.b2 = rad_bound2(r); S.cnt = 0; S.len = 0; S.keys = nullptr; S.vals = nullptr;
+    if (MODE == 1) {
+        const uint32_t o = off[i];
+        S.len = off[i + 1] - o;
+        S.keys = keys + o;
+        S.vals = vals ? vals + o : nullptr;
+    }
+    const Real big = RealTraits<Real>::inf();
+    const bool finite = qx > -big && qx < big && qy > -big && qy < big && qz > -big && qz < big;      // (false for NaN)
+    if (finite) rad_ball_walk(g, pts, cs, qx, qy, qz, r, S);
+    if (MODE == 0) count[i] = (int64_t)S.cnt;
+    else if (S.cnt != S.len) *flag = 1u;
+}
+
+// sorted keys -> (distance, original index)
+__global__ void __launch_bounds__(256) k_radius_unpack(const uint64_t *__restrict__ keys, int64_t n, float *dist, int64_t *idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = keys[i];
+    dist[i] = __builtin_sqrtf(__uint_as_float((uint32_t)(k >> 32)));
+    idx[i] = (int64_t)(uint32_t)k;
+}
+__global__ void __launch_bounds__(256) k_radius_unpack_dd(const uint64_t *__restrict__ d2, const uint32_t *__restrict__ orig, int64_t n,
+                                                          double *dist, int64_t *idx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dist[i] = __builtin_sqrt(__longlong_as_double((long long)d2[i]));
+    idx[i] = (int64_t)orig[i];
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------
+// entries a call holds on the device at a time (PCR_RADIUS_CHUNK, read once)
+static int64_t radius_budget() {
+    static const int64_t b = [] {
+        const char *e = getenv("PCR_RADIUS_CHUNK");
+        const long long v = e ? atoll(e) : 0;
+        return (int64_t)(v >= 1 ? v : (1ll << 26));
+    }();
+    return b;
+}
+// PCR_RADIUS_TIMES=1 (developer, tools/radius_time.py): a query call brackets fill / sort / unpack with events and reports
+// their milliseconds on stderr
+static bool radius_times() {
+    static const bool on = getenv("PCR_RADIUS_TIMES") && atoi(getenv("PCR_RADIUS_TIMES")) != 0;
+    return on;
+}
+
+struct RadEvents {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    ~RadEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t init() {
+        on = true;
+        for (hipEvent_t &e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) return s; }
+        return hipSuccess;
+    }
+    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
+};
+
+template <typename Real> struct RadTarget;
+template <> struct RadTarget<float> {
+    static const Geom<float> &geom(const pcr_target *t) { return t->gf; }
+    static const PtF *pts(const pcr_target *t) { return t->pts; }
+};
+template <> struct RadTarget<double> {
+    static const Geom<double> &geom(const pcr_target *t) { return t->gq; }
+    static const PtD *pts(const pcr_target *t) { return t->pts64; }
+};
+
+template <typename Real>
+static pcr_status radius_check(const pcr_target *t, Real r, const char *who) {
+    if (t->is_voxel) { pcr_set_error("invalid argument: %s needs a point target", who); return PCR_ERR_INVALID; }
+    if (sizeof(Real) == 8 && t->n > 0 && t->pts64 == nullptr) {
+        pcr_set_error("invalid argument: %s needs a point target with float64 coordinates (pcr_target_points_set_f64)", who);
+        return PCR_ERR_INVALID;
+    }
+    if (!(r >= 0 && r <= (Real)(sizeof(Real) == 8 ? DBL_MAX : FLT_MAX))) {
+        pcr_set_error("invalid argument: %s needs a finite radius >= 0", who);
+        return PCR_ERR_INVALID;
+    }
+    return PCR_OK;
+}
+
+static dim3 rad_grid(int64_t m) { return dim3((unsigned)((m + RAD_BLOCK - 1) / RAD_BLOCK)); }
+
+template <typename Real>
+static void radius_launch_count(pcr_target *t, const Real *d_q, int64_t m, Real r, int64_t *d_count) {
+    hipLaunchKernelGGL((k_radius<Real, 0>), rad_grid(m), dim3(RAD_BLOCK), 0, t->ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
+                       (const uint32_t *)t->cell_start, d_q, m, r, d_count, (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                       (uint32_t *)nullptr);
+}
+
+template <typename Real>
+static pcr_status radius_count(pcr_target *t, const Real *q, int64_t m, Real r, int64_t *count, const char *who) {
+    PCR_REQUIRE(t && (q || m == 0) && (count || m == 0), "NULL argument");
+    PCR_REQUIRE(m >= 0, "negative query count");
+    PCR_TRY(radius_check<Real>(t, r, who));
+    if (m == 0) return PCR_OK;
+    if (t->n == 0) { for (int64_t i = 0; i < m; ++i) count[i] = 0; return PCR_OK; }
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    DevBuf<Real> d_q;
+    DevBuf<int64_t> d_count;
+    HIP_TRY(d_q.alloc(3 * (size_t)m));
+    HIP_TRY(d_count.alloc((size_t)m));
+    HIP_TRY(hipMemcpyAsync(d_q.p, q, sizeof(Real) * 3 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    RadEvents ev;
+    if (radius_times()) HIP_TRY(ev.init());
+    ev.mark(0, ctx->stream);
+    radius_launch_count<Real>(t, d_q.p, m, r, d_count.p);
+    HIP_TRY(hipGetLastError());
+    ev.mark(1, ctx->stream);
+    HIP_TRY(hipMemcpyAsync(count, d_count.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ev.on) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
+        fprintf(stderr, "pcr_radius_times %s queries %lld count_ms %.4f\n", who, (long long)m, ms);
+    }
+    return PCR_OK;
+}
+
+// order the E entries of a chunk's segments by (d2, original index); *keys_out / *vals_out: where the result lies
+static pcr_status radius_sort(pcr_context *ctx, bool f64, uint64_t *k0, uint64_t *k1, uint32_t *v0, uint32_t *v1, unsigned E, unsigned segs,
+                              const uint32_t *d_off, uint64_t **keys_out, uint32_t **vals_out) {
+    DevBuf<char> tmp;
+    size_t bytes = 0;
+    if (!f64) {
+        rocprim::double_buffer<uint64_t> keys(k0, k1);
+        HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, bytes, keys, E, segs, d_off, d_off + 1, 0, 64, ctx->stream));
+        HIP_TRY(tmp.alloc_bytes(bytes));
+        HIP_TRY(rocprim::segmented_radix_sort_keys(tmp.p, bytes, keys, E, segs, d_off, d_off + 1, 0, 64, ctx->stream));
+        *keys_out = keys.current(); *vals_out = nullptr;
+        return PCR_OK;
+    }
+    // by original index, then (stable) by the bits of d2
+    rocprim::double_buffer<uint32_t> o(v0, v1);
+    rocprim::double_buffer<uint64_t> d(k0, k1);
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, bytes, o, d, E, segs, d_off, d_off + 1, 0, 32, ctx->stream));
+    HIP_TRY(tmp.alloc_bytes(bytes));
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(tmp.p, bytes, o, d, E, segs, d_off, d_off + 1, 0, 32, ctx->stream));
+    size_t bytes2 = 0;
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, bytes2, d, o, E, segs, d_off, d_off + 1, 0, 64, ctx->stream));
+    if (bytes2 > bytes) { HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(tmp.alloc_bytes(bytes2)); }
+    HIP_TRY(rocprim::segmented_radix_sort_pairs(tmp.p, bytes2, d, o, E, segs, d_off, d_off + 1, 0, 64, ctx->stream));
+    *keys_out = d.current(); *vals_out = o.current();
+    return PCR_OK;
+}
+
+template <typename Real>
+static pcr_status radius_query(pcr_target *t, const Real *q, int64_t m, Real r, const int64_t *offsets, Real *dist, int64_t *idx, const char *who) {
+    PCR_REQUIRE(t && (q || m == 0) && offsets, "NULL argument");
+    PCR_REQUIRE(m >= 0, "negative query count");
+    PCR_TRY(radius_check<Real>(t, r, who));
+    // the CSR layout: starts at 0, never decreases
+    PCR_REQUIRE(offsets[0] == 0, "offsets must start at 0");
+    for (int64_t i = 0; i < m; ++i) PCR_REQUIRE(offsets[i + 1] >= offsets[i], "offsets must not decrease");
+    PCR_REQUIRE(offsets[m] == 0 || (dist && idx), "NULL argument");
+    if (m == 0) return PCR_OK;
+    if (t->n == 0) { PCR_REQUIRE(offsets[m] == 0, "offsets are not the prefix sum of the counts"); return PCR_OK; }
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    const bool f64 = sizeof(Real) == 8;
+    const int64_t budget = radius_budget();
+    DevBuf<Real> d_q;
+    HIP_TRY(d_q.alloc(3 * (size_t)m));
+    HIP_TRY(hipMemcpyAsync(d_q.p, q, sizeof(Real) * 3 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+
+    // chunks of consecutive queries [cut[c], cut[c + 1]) whose segments fit the budget; a larger query alone
+    std::vector<int64_t> cut{0};
+    int64_t e_max = 0;
+    for (int64_t a = 0; a < m;) {
+        int64_t b = a + 1;
+        while (b < m && offsets[b + 1] - offsets[a] <= budget) ++b;
+        cut.push_back(b);
+        if (offsets[b] - offsets[a] > e_max) e_max = offsets[b] - offsets[a];
+        a = b;
+    }
+    PCR_REQUIRE(e_max < ((int64_t)1 << 32), "a chunk of segments holds 2^32 entries or more");
+    const size_t n_chunks = cut.size() - 1;
+    int64_t m_max = 0;
+    for (size_t c = 0; c < n_chunks; ++c) m_max = cut[c + 1] - cut[c] > m_max ? cut[c + 1] - cut[c] : m_max;
+
+    if (n_chunks > 1) {
+        // results of an earlier chunk reach the caller before a later chunk's flag is known: check every length first
+        DevBuf<int64_t> d_count;
+        HIP_TRY(d_count.alloc((size_t)m));
+        radius_launch_count<Real>(t, d_q.p, m, r, d_count.p);
+        HIP_TRY(hipGetLastError());
+        std::vector<int64_t> cnt((size_t)m);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), d_count.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (int64_t i = 0; i < m; ++i) PCR_REQUIRE(cnt[i] == offsets[i + 1] - offsets[i], "offsets are not the prefix sum of the counts");
+    }
+
+    const size_t cap = (size_t)(e_max > 0 ? e_max : 1);
+    DevBuf<uint64_t> k0, k1;
+    DevBuf<uint32_t> v0, v1, d_off, d_flag;
+    DevBuf<Real> d_dist;
+    DevBuf<int64_t> d_idx;
+    HIP_TRY(k0.alloc(cap)); HIP_TRY(k1.alloc(cap));
+    if (f64) { HIP_TRY(v0.alloc(cap)); HIP_TRY(v1.alloc(cap)); }
+    HIP_TRY(d_off.alloc((size_t)m_max + 1)); HIP_TRY(d_flag.alloc(1));
+    HIP_TRY(d_dist.alloc(cap)); HIP_TRY(d_idx.alloc(cap));
+    std::vector<uint32_t> rel((size_t)m_max + 1);
+    RadEvents ev;
+    if (radius_times()) HIP_TRY(ev.init());
+
+    for (size_t c = 0; c < n_chunks; ++c) {
+        const int64_t a = cut[c], b = cut[c + 1], mc = b - a, E = offsets[b] - offsets[a];
+        for (int64_t i = 0; i <= mc; ++i) rel[(size_t)i] = (uint32_t)(offsets[a + i] - offsets[a]);
+        HIP_TRY(hipMemcpyAsync(d_off.p, rel.data(), 4 * (size_t)(mc + 1), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemsetAsync(d_flag.p, 0, 4, ctx->stream));
+        ev.mark(0, ctx->stream);
+        hipLaunchKernelGGL((k_radius<Real, 1>), rad_grid(mc), dim3(RAD_BLOCK), 0, ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
+                           (const uint32_t *)t->cell_start, (const Real *)(d_q.p + 3 * a), mc, r, (int64_t *)nullptr, (const uint32_t *)d_off.p,
+                           k0.p, v0.p, d_flag.p);
+        HIP_TRY(hipGetLastError());
+        ev.mark(1, ctx->stream);
+        if (E > 0) {
+            uint64_t *ks = nullptr;
+            uint32_t *vs = nullptr;
+            PCR_TRY(radius_sort(ctx, f64, k0.p, k1.p, v0.p, v1.p, (unsigned)E, (unsigned)mc, d_off.p, &ks, &vs));
+            ev.mark(2, ctx->stream);
+            if (f64)
+                hipLaunchKernelGGL(k_radius_unpack_dd, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)ks,
+                                   (const uint32_t *)vs, E, (double *)d_dist.p, d_idx.p);
+            else
+                hipLaunchKernelGGL(k_radius_unpack, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)ks, E,
+                                   (float *)d_dist.p, d_idx.p);
+            HIP_TRY(hipGetLastError());
+        } else {
+            ev.mark(2, ctx->stream);
+        }
+        ev.mark(3, ctx->stream);
+        // the host copies happen only after the flag reads clean
+        uint32_t flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        PCR_REQUIRE(flag == 0, "offsets are not the prefix sum of the counts");
+        if (ev.on) {
+            float ms[3] = {0, 0, 0};
+            for (int p = 0; p < 3; ++p) (void)hipEventElapsedTime(&ms[p], ev.ev[p], ev.ev[p + 1]);
+            fprintf(stderr, "pcr_radius_times %s queries %lld entries %lld fill_ms %.4f sort_ms %.4f unpack_ms %.4f\n", who, (long long)mc,
+                    (long long)E, ms[0], ms[1], ms[2]);
+        }
+        if (E > 0) {
+            HIP_TRY(hipMemcpyAsync(dist + offsets[a], d_dist.p, sizeof(Real) * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(idx + offsets[a], d_idx.p, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_radius_count(pcr_target *t, const float *q, int64_t m, float r, int64_t *count) {
+    return radius_count<float>(t, q, m, r, count, "pcr_radius_count");
+}
+extern "C" pcr_status pcr_radius_query(pcr_target *t, const float *q, int64_t m, float r, const int64_t *offsets, float *dist, int64_t *idx) {
+    return radius_query<float>(t, q, m, r, offsets, dist, idx, "pcr_radius_query");
+}
+extern "C" pcr_status pcr_radius_count_dd(pcr_target *t, const double *q, int64_t m, double r, int64_t *count) {
+    return radius_count<double>(t, q, m, r, count, "pcr_radius_count_dd");
+}
+extern "C" pcr_status pcr_radius_query_dd(pcr_target *t, const double *q, int64_t m, double r, const int64_t *offsets, double *dist,
+                                          int64_t *idx) {
+    return radius_query<double>(t, q, m, r, offsets, dist, idx, "pcr_radius_query_dd");
+}
+
+// ---- mean k-NN distance ---------------------------------------------------------------------------------------------------
+template <typename LIST>
+__device__ __forceinline__ void knn_mean_finish(const PtF me, double *mean, LIST &L) {
+    // the distances pcr_knn_query reports, summed in float64 nearest first, over the neighbours found
+    double s = 0;
+    L.for_each([&](int, float d2, uint32_t) { s += (double)__builtin_sqrtf(d2); });
+    mean[pt_orig(me)] = s / (double)(L.cnt > 0 ? L.cnt : 1);
+}
+
+// REG = 1: the collect path (k <= 16); 0: the LDS list -- launch shape and LDS sizing of k_knn_normals / k_gicp_cov
+template <int REG>
+__global__ void __launch_bounds__(KNN_BLOCK) k_knn_mean_dist(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, int k, double *mean) {
+    const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const PtF me = pts[i];
+    if (REG) {
+        KnnOut L;
+        L.init(rad_smem);
+        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
+        knn_mean_finish(me, mean, L);
+    } else {
+        KnnList L;
+        L.k = k; L.cnt = 0; L.lane = threadIdx.x;
+        L.d = (float *)rad_smem;
+        L.j = (uint32_t *)(rad_smem + sizeof(float) * k * KNN_BLOCK);
+        L.pts = pts;
+        knn_search(g, pts, cs, me.x, me.y, me.z, L);
+        knn_mean_finish(me, mean, L);
+    }
+}
+
+extern "C" pcr_status pcr_knn_mean_distance(pcr_target *t, int k, double *mean_out) {
+    PCR_REQUIRE(t, "NULL argument");
+    PCR_REQUIRE(!t->is_voxel, "the mean k-NN distance belongs to point targets");
+    if (k < 1 || k > KNN_MAX_K) { pcr_set_error("k must be in [1, %d]", KNN_MAX_K); return PCR_ERR_INVALID; }
+    PCR_REQUIRE(mean_out || t->n == 0, "NULL argument");
+    if (t->n == 0) return PCR_OK;
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    DevBuf<double> d_mean;
+    HIP_TRY(d_mean.alloc((size_t)t->n));
+    const dim3 grid((unsigned)((t->n + KNN_BLOCK - 1) / KNN_BLOCK));
+    if (k <= KNN_REG_K)
+        hipLaunchKernelGGL(k_knn_mean_dist<1>, grid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream, t->gf, (const PtF *)t->pts,
+                           (const uint32_t *)t->cell_start, t->n, k, d_mean.p);
+    else
+        hipLaunchKernelGGL(k_knn_mean_dist<0>, grid, dim3(KNN_BLOCK), 2 * sizeof(float) * (size_t)k * KNN_BLOCK, ctx->stream, t->gf,
+                           (const PtF *)t->pts, (const uint32_t *)t->cell_start, t->n, k, d_mean.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mean_out, d_mean.p, 8 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
+}

@@ -35,10 +35,30 @@ class KDTree:
             self._target.set_points_f64(data)
 
     def query(self, points, k=1, distance_upper_bound=np.inf):
-        """Exact k nearest neighbours: ``(dist, idx)``, shape (M,) for k=1 and (M, k) otherwise."""
+        """Exact k nearest neighbours: ``(dist, idx)``, shape (M,) for k=1 and (M, k) otherwise.  With a finite
+        ``distance_upper_bound`` r, entries with ``not (d < r)`` read ``(inf, n)`` for k > 1 -- the strict comparison of the
+        k = 1 search with the padding of a tree smaller than k; rows are nearest first, so those entries are a suffix."""
         points = np.asarray(points)
         if k == 1:
             dist, idx = self._target.nn_query(points, distance_upper_bound)
         else:
             dist, idx = self._target.knn_query(points, k)
+            if not distance_upper_bound == np.inf:
+                out = ~(dist < distance_upper_bound)
+                dist[out] = np.inf
+                idx[out] = self.n
         return dist.astype(self._dtype, copy=False), idx
+
+    def query_radius(self, points, r, count_only=False):
+        """Everything within ``r`` of every query point, exactly: ``(dist, idx, offsets)`` in CSR form -- the neighbours of
+        query i are ``idx[offsets[i]:offsets[i + 1]]`` at distances ``dist[...]`` (the tree's dtype), ordered by (squared
+        distance, index) as ``query`` orders them; ``idx`` and ``offsets`` are int64.  A neighbour is a point whose distance,
+        as ``query`` would report it, is ``<= r``.  ``count_only=True``: the (M,) int64 counts alone.  A float64 tree takes the
+        queries in the dtype they come in (float32 is widened exactly); a float32 tree rounds float64 queries, as ``query``
+        does.  ``r`` must be finite and >= 0 (ValueError)."""
+        r = _capi.check_radius(r)
+        points = np.asarray(points)
+        if count_only:
+            return self._target.radius_count(points, r)
+        dist, idx, offsets = self._target.radius_query(points, r)
+        return dist.astype(self._dtype, copy=False), idx, offsets
