@@ -462,6 +462,44 @@ PCR_API pcr_status pcr_radius_query_dd(pcr_target *t, const double *q, int64_t m
  * from.  Always searches the float32 copy of the points.                                                              */
 PCR_API pcr_status pcr_knn_mean_distance(pcr_target *t, int k, double *mean_out);
 
+/* ---- FPFH descriptors and exact feature matching (no reference counterpart) ---------------
+ * Fast Point Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009) in the Open3D form, of a point target that has normals
+ * (pcr_target_points_create(..., normals), pcr_target_set_normals or pcr_target_estimate_normals), at a radius r (float32,
+ * finite, >= 0).
+ * Neighbourhood of point i: every point j of the target that pcr_radius_query returns for the query p_i at r -- the float32
+ *   rule sqrtf(dist2_f32) <= r -- except the pairs with d2 == 0, d2 = (dx*dx + dy*dy) + dz*dz in float64 over the widened
+ *   float32 coordinates: the point itself and its exact duplicates are dropped, on both passes.  k_i = neighbours left.
+ * Pair feature of (p = point i, q = neighbour j), normals np, nq, all in float64 from the widened float32 inputs, no
+ *   contraction, every dot product (ax*bx + ay*by) + az*bz:
+ *     d = q - p, L = sqrt(d2), a1 = np . d, a2 = nq . d
+ *     |a1| < |a2| (strict): n1 = nq, n2 = np, d = -d; otherwise n1 = np, n2 = nq
+ *     phi = (n1 . d) / L, v = d x n1
+ *     v . v == 0 (d parallel to n1, or a zero normal): alpha = theta = 0; otherwise v = v / sqrt(v . v), w = n1 x v,
+ *     alpha = v . n2, theta = atan2(w . n2, n1 . n2)
+ *     bin coordinates 11 (alpha + 1) / 2, 11 (phi + 1) / 2, 11 (theta + pi) / (2 pi); bin = clamp(floor(coordinate), 0, 10);
+ *     the three features fill three blocks of 11 bins: 33 bins, alpha first.
+ * SPFH: unsigned counts per bin over the neighbourhood, and k_i; S_i[b] = 100 count[b] / k_i in float64, 0 when k_i == 0.
+ * FPFH: A_i[b] = sum over the neighbourhood of S_j[b] / d2_ij in float64; per 11-bin block F_i[b] = S_i[b] + 100 A_i[b] /
+ *   sum_block(A_i) (the second term 0 when the block sum is not > 0), rounded to float32: every block of a point that has
+ *   neighbours sums to 200.  The counts are exact; the float64 sums are taken in the order the index is walked, ~1e-14
+ *   relative.  No atomics: the same call twice returns the same bits.
+ * pcr_target_spfh: counts (n x 33) and k (n); pcr_target_fpfh: fpfh (n x 33) and, when not NULL, k (n); rows in the order of
+ *   the array the target was created from.  Always over the float32 copy of the points.
+ * PCR_ERR_NO_TARGET: a point target without normals.  PCR_ERR_INVALID: a voxel target; r negative, NaN or infinite.  An
+ *   empty target returns PCR_OK without a launch.
+ *
+ * pcr_feature_match: for every row i of A (na x dim) its nearest row of B (nb x dim), float32, 1 <= dim <= 64 (else
+ *   PCR_ERR_INVALID), host arrays.  d2(i, j) = the float32 sum over c = 0 .. dim - 1, in that order, of (A[i,c] - B[j,c])^2,
+ *   every step a separate subtract, multiply and add.  idx[i] = the j that minimises the key (d2, j), d2_first[i] that
+ *   distance, d2_second[i] the distance of the second smallest key over all j (equal to d2_first for duplicate rows of B, inf
+ *   when nb == 1).  A NaN distance never wins; a row with no other distance gets idx = -1, d2_first = inf.  The result
+ *   does not depend on how the work is tiled or split.  na == 0 returns PCR_OK; nb == 0 fills idx = -1 and both distances
+ *   with inf; neither launches anything.                                                                                */
+PCR_API pcr_status pcr_target_spfh(pcr_target *t, float r, uint32_t *counts, int64_t *k);
+PCR_API pcr_status pcr_target_fpfh(pcr_target *t, float r, float *fpfh, int64_t *k_or_null);
+PCR_API pcr_status pcr_feature_match(pcr_context *ctx, const float *A, int64_t na, const float *B, int64_t nb, int dim,
+                                     int64_t *idx, float *d2_first, float *d2_second);
+
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the
  * context's stream; pcr_profile_read drains them (synchronises) and reports per-kernel

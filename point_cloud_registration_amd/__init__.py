@@ -20,11 +20,12 @@ from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
 from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
 from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
+from .features import compute_fpfh, match_features, select_matches
 
 __all__ = [
     "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "KDTree", "VoxelGrid", "voxel_filter",
     "color_by_voxel", "get_keys", "estimate_normals", "get_norm_lines", "estimate_norm_with_tree",
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
-    "remove_radius_outliers", "remove_statistical_outliers",
+    "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
 ]

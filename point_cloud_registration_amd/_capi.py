@@ -42,6 +42,7 @@ _shutdown = False
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
+_u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 
 # name -> (restype, argtypes); also the list of symbols the library must export
@@ -88,6 +89,10 @@ PROTOTYPES = {
     "pcr_radius_count_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _i64p]),
     "pcr_radius_query_dd": (C.c_int, [_vp, _f64p, C.c_int64, C.c_double, _i64p, _f64p, _i64p]),
     "pcr_knn_mean_distance": (C.c_int, [_vp, C.c_int, _f64p]),
+    # FPFH descriptors and exact feature matching (include/pcr.h, features.py)
+    "pcr_target_spfh": (C.c_int, [_vp, C.c_float, _u32p, _i64p]),
+    "pcr_target_fpfh": (C.c_int, [_vp, C.c_float, _f32p, _vp]),
+    "pcr_feature_match": (C.c_int, [_vp, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _i64p, _f32p, _f32p]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -718,6 +723,25 @@ class Target:
         check(lib().pcr_knn_mean_distance(self.handle, int(k), out))
         return out
 
+    # -- FPFH descriptors (include/pcr.h): a point target that has normals
+    def spfh(self, r):
+        """-> (counts (N, 33) uint32, k (N,) int64): the simplified point feature histograms as integer counts and the
+        number of neighbours, in the caller's order."""
+        r = check_radius(r)
+        n = self.size()
+        counts, k = np.zeros((n, 33), np.uint32), np.zeros(n, np.int64)
+        check(lib().pcr_target_spfh(self.handle, r, counts, k))
+        return counts, k
+
+    def fpfh(self, r, want_k=False):
+        """-> (N, 33) float32 FPFH descriptors in the caller's order (and k (N,) int64 with ``want_k``)."""
+        r = check_radius(r)
+        n = self.size()
+        out = np.zeros((n, 33), np.float32)
+        k = np.zeros(n, np.int64) if want_k else None
+        check(lib().pcr_target_fpfh(self.handle, r, out, _ptr(k)))
+        return (out, k) if want_k else out
+
     def close(self):
         if getattr(self, "handle", None) and not _shutdown and not getattr(self, "_borrowed", False):
             lib().pcr_target_destroy(self.handle)
@@ -915,6 +939,19 @@ def lzf_compress(data):
     w = C.c_uint64(0)
     check(lib().pcr_lzf_compress(src.ctypes.data_as(_vp), src.size, out.ctypes.data_as(_vp), out.size, C.byref(w)))
     return out[:w.value].tobytes()
+
+
+def feature_match(ctx, A, B):
+    """pcr_feature_match: A (na, D), B (nb, D) float32 -> (idx (na,) int64, d2_first (na,) float32, d2_second (na,) float32)."""
+    A, B = np.ascontiguousarray(A, dtype=np.float32), np.ascontiguousarray(B, dtype=np.float32)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+        raise ValueError("features must have shapes (NA, D) and (NB, D)")
+    if not 1 <= A.shape[1] <= 64:
+        raise ValueError("features must have 1 to 64 columns")
+    na = A.shape[0]
+    idx, d1, d2 = np.empty(na, np.int64), np.empty(na, np.float32), np.empty(na, np.float32)
+    check(lib().pcr_feature_match(ctx.handle, A, na, B, B.shape[0], A.shape[1], idx, d1, d2))
+    return idx, d1, d2
 
 
 def gn_set(ctx, J, r):
