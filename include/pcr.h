@@ -523,6 +523,13 @@ PCR_API pcr_status pcr_target_index_info(pcr_target *t, double *cell, int64_t di
  * ~5 points per occupied cell, the points of a cell are Morton-sorted, and every range of more than 24 records is searched
  * through boxes over 64 and 8 consecutive records (csrc/nn_device.h: nn_scan_range_lb).  Any pointer may be NULL.         */
 PCR_API pcr_status pcr_target_index_population(pcr_target *t, int64_t *pop_max, int64_t *pop_p99, int *heavy);
+/* point targets: *xq = the x quantum (metres, cell / 65536) when the records of every cell and of every extended list are
+ * stored in ascending x, so that the plain search scans a row of cells from the query's x outward; 0 when they are not
+ * (heavy targets, voxel targets, PCR_XORDER=0 in the environment when the target was built).
+ * pcr_x_order_rule: the host-side rule behind it (needs no device): 1 when a target of `n` points whose cell ids take
+ * `cell_bits` bits gets the x order -- float32 point targets without heavy cells, unless PCR_XORDER=0                       */
+PCR_API pcr_status pcr_target_index_x_order(pcr_target *t, double *xq);
+PCR_API int pcr_x_order_rule(int f32_point_target, int heavy, int64_t n, int cell_bits);
 /* point targets: margin (metres) and total records of the extended per-cell lists ring 0 searches (a cell's
  * own points plus the neighbours' points within the margin of the shared face; PCR_HALO sets the margin as a
  * fraction of the cell edge, default 0.1, 0 = none).  Voxel targets: the same of the float32 filter index over
@@ -540,8 +547,14 @@ PCR_API pcr_status pcr_target_filter_band(pcr_target *t, double *band);
 /* work counters of the NN search for one pose (point targets): out[0..3] = rings entered, row
  * segments loaded, rows pruned by arithmetic, candidates tested, summed over queries; out[4..7] = the
  * same with each wave's maximum charged to all 64 lanes (the cost under divergence); out[8..10] =
- * wave wall-clock cycles summed over waves: prologue (load, transform, cell), ring 0, outer rings   */
+ * wave wall-clock cycles summed over waves: prologue (load, transform, cell), ring 0, outer rings.
+ * pcr_nn_counters_x: the same traversal on a target in the OLD order inside a cell (built under
+ * PCR_XORDER=0, no heavy cells; zeros otherwise): out[0] = candidates tested, out[1..2] = those of them
+ * whose bound (p.x - q.x)^2 + (slab distance of the row)^2 was within the best distance at the time of
+ * the test / within the final best -- what a scan that knew the order of x inside a row could not have
+ * skipped, summed over queries                                                                      */
 PCR_API pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[11]);
+PCR_API pcr_status pcr_nn_counters_x(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[3]);
 /* select the hot-path variant: 2 (default) = chosen per launch by the size of the scan: 1 = NN kernel
  * writing correspondences to HBM followed by a reduce kernel (faster for large scans: twice the
  * occupancy), 0 = one fused transform+NN+reduce kernel (faster for small, latency-bound scans: 100 k

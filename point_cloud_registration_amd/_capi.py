@@ -99,12 +99,15 @@ PROTOTYPES = {
     "pcr_target_index_info": (C.c_int, [_vp, C.POINTER(C.c_double), _i64p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcr_target_index_halo": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pcr_target_index_population": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "pcr_target_index_x_order": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "pcr_x_order_rule": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int]),
     "pcr_set_variant": (C.c_int, [_vp, C.c_int]),
     "pcr_get_variant": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "pcr_set_nn_mode": (C.c_int, [_vp, C.c_int]),
     "pcr_set_fuse_finalize": (C.c_int, [_vp, C.c_int]),
     "pcr_get_pipeline": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pcr_nn_counters": (C.c_int, [_vp, _vp, _f64p, C.c_double, _f64p]),
+    "pcr_nn_counters_x": (C.c_int, [_vp, _vp, _f64p, C.c_double, _f64p]),
     "pcr_set_reuse": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "pcr_get_reuse": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pcr_scan_reuse_stats": (C.c_int, [_vp, _f64p]),
@@ -633,10 +636,13 @@ class Target:
         check(lib().pcr_target_index_halo2(self.handle, C.byref(halo2), C.byref(nh2)))
         pmax, p99, heavy = C.c_int64(0), C.c_int64(0), C.c_int(0)
         check(lib().pcr_target_index_population(self.handle, C.byref(pmax), C.byref(p99), C.byref(heavy)))
+        xq = C.c_double(0)
+        check(lib().pcr_target_index_x_order(self.handle, C.byref(xq)))
         return {"cell": cell.value, "dims": tuple(int(d) for d in dims), "occupied": occ.value, "n": n.value,
                 "halo": halo.value, "halo_records": nh.value, "filter_band": band.value,
                 "halo2": halo2.value, "halo2_records": nh2.value,
-                "pop_max": pmax.value, "pop_p99": p99.value, "heavy": bool(heavy.value)}
+                "pop_max": pmax.value, "pop_p99": p99.value, "heavy": bool(heavy.value),
+                "x_ordered": xq.value > 0.0, "xq": xq.value}
 
     def searches_f64(self):
         """True when the target answers in float64: a voxel target, or a point target that holds the float64 coordinates
@@ -1192,6 +1198,16 @@ def nn_counters(target, scan, T, max_dist):
     return {**{k: out[i] / n for i, k in enumerate(names)},
             **{"wave_" + k: out[4 + i] / n for i, k in enumerate(names)},
             "cyc_prologue": out[8] / waves, "cyc_ring0": out[9] / waves, "cyc_rings": out[10] / waves}
+
+
+def nn_counters_x(target, scan, T, max_dist):
+    """Per query, on a target in the old order inside a cell: candidates tested and how many of them an x-ordered scan could
+    not have skipped, against the best at the time / the final best (see include/pcr.h: pcr_nn_counters_x)."""
+    out = np.zeros(3)
+    check(lib().pcr_nn_counters_x(target.handle, scan.handle, np.ascontiguousarray(T, np.float64).reshape(16),
+                                  float(max_dist), out))
+    n = max(scan.n, 1)
+    return {"candidates": out[0] / n, "x_now": out[1] / n, "x_final": out[2] / n}
 
 
 def unpack29(out):

@@ -281,6 +281,10 @@ extern "C" int pcr_has_dev_kernels(void) {
 #endif
 }
 #ifndef PCR_DEV
+extern "C" pcr_status pcr_nn_counters_x(pcr_target *, pcr_scan *, const double *, double, double *) {
+    pcr_set_error("pcr_nn_counters_x needs the developer build of the library (make DEV=1: libpcr_hip_dev.so)");
+    return PCR_ERR_INVALID;
+}
 extern "C" pcr_status pcr_nn_counters(pcr_target *, pcr_scan *, const double *, double, double *) {
     pcr_set_error("pcr_nn_counters needs the developer build of the library (make DEV=1: libpcr_hip_dev.so)");
     return PCR_ERR_INVALID;
@@ -631,6 +635,12 @@ extern "C" pcr_status pcr_target_index_info(pcr_target *t, double *cell, int64_t
     }
     if (occupied) *occupied = t->occupied;
     if (n) *n = t->n;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_index_x_order(pcr_target *t, double *xq) {
+    PCR_REQUIRE(t && xq, "NULL argument");
+    *xq = t->is_voxel ? 0.0 : (double)t->gf.xq;
     return PCR_OK;
 }
 

@@ -183,6 +183,24 @@ __device__ __forceinline__ uint32_t sub_morton(const Geom<Real> &g, Real x, Real
     return code;
 }
 
+// Position of a point inside its cell along x, in quanta of cell / 65536: the minor sort key of an x-ordered target (Geom::xq).
+// Non-decreasing in x over the points of a cell: (x - ox) * inv_h is monotone, the cell's own index is subtracted exactly, the
+// scale is a power of two and the clamp keeps the order.  cx0 / span: the cells the key counts from and over -- the point's own
+// cell (cell_of's x index) and 1 for the cell-sorted array; the extended list of cell cx holds points of the cells
+// cx - 1 .. cx + 1 and is keyed from the lower face of cell cx - 1 over 3 cells.  Two records with equal keys differ in x by
+// less than cell / 65536 plus the rounding of (x - ox) * inv_h, which Geom::slack covers.
+#define PCR_XQ_BITS 16
+template <typename Real>
+__device__ __forceinline__ uint32_t sub_xq(const Geom<Real> &g, Real x, int cx0, int span) {
+    const Real ux = (x - g.ox) * g.inv_h;
+    const int q = (int)floor((ux - (Real)cx0) * (Real)(1 << PCR_XQ_BITS));
+    return (uint32_t)min(max(q, 0), (span << PCR_XQ_BITS) - 1);
+}
+template <typename Real>
+__device__ __forceinline__ uint32_t sub_xq_own(const Geom<Real> &g, Real x) {
+    return sub_xq<Real>(g, x, min(max((int)floor((x - g.ox) * g.inv_h), 0), g.nx - 1), 1);
+}
+
 // (occ: += the number of cells this launch touched first, i.e. the occupied cells of a histogram that started at zero -- one
 // atomic per block; a separate counting pass over the cells cost as much as this kernel, round 5)
 // sub_bits > 0: cell_id = (cell << sub_bits) | Morton code of the position inside the cell.
@@ -193,7 +211,7 @@ __device__ __forceinline__ uint32_t sub_morton(const Geom<Real> &g, Real x, Real
 template <typename Real, typename T, typename K = uint32_t>
 __global__ void __launch_bounds__(256) k_cell_ids(const T *__restrict__ xyz, int64_t n, Geom<Real> g,
                                                   K *cell_id, uint32_t *idx, uint32_t *counts, unsigned long long *occ,
-                                                  int sub_bits) {
+                                                  int sub_bits, bool xsub = false) {
     __shared__ unsigned firsts, popmax;
     if (threadIdx.x == 0) { firsts = 0; popmax = 0; }
     __syncthreads();
@@ -205,7 +223,8 @@ __global__ void __launch_bounds__(256) k_cell_ids(const T *__restrict__ xyz, int
         const Real x = (Real)xyz[3 * i], y = (Real)xyz[3 * i + 1], z = (Real)xyz[3 * i + 2];
         c = cell_of<Real>(g, x, y, z);
         if (cell_id) {
-            cell_id[i] = sub_bits > 0 ? ((K)c << sub_bits) | (K)sub_morton<Real>(g, x, y, z, sub_bits / 3) : (K)c;
+            // (xsub: the minor key is the x offset inside the cell, PCR_XQ_BITS wide, instead of the Morton code)
+            cell_id[i] = sub_bits > 0 ? ((K)c << sub_bits) | (K)(xsub ? sub_xq_own<Real>(g, x) : sub_morton<Real>(g, x, y, z, sub_bits / 3)) : (K)c;
             idx[i] = (uint32_t)i;
         }
     }
@@ -355,6 +374,28 @@ __global__ void __launch_bounds__(256) k_halo_fill(const PtF *__restrict__ pts, 
     });
 }
 
+// x-ordered targets (Geom::xq): a list must be ascending in x as a whole, its own points and the copies from its neighbours
+// merged.  The fill writes (list cell, x offset from the lower face of the cell before it) keys and the cell-sorted indices into
+// the same slots as k_halo_fill; one radix sort of the pairs then orders every list in place (the cell is the major key and every
+// list keeps its number of entries), and the records are gathered behind it.
+__global__ void __launch_bounds__(256) k_halo_fill_x(const PtF *__restrict__ pts, int64_t n, Geom<float> g, const uint32_t *__restrict__ cs,
+                                                     const uint32_t *__restrict__ cs_h, uint32_t *cursor, unsigned long long *key_out,
+                                                     uint32_t *j_out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const PtF p = pts[j];
+    halo_cells(g, p.x, p.y, p.z, [&](uint32_t c, bool own) {
+        const uint32_t e = own ? cs_h[c] + ((uint32_t)j - (cs[c] & g.cs_mask)) : atomicAdd(&cursor[c], 1u);
+        const int lx = (int)(c % (uint32_t)g.nx);
+        key_out[e] = ((unsigned long long)c << (PCR_XQ_BITS + 2)) | (unsigned long long)sub_xq<float>(g, p.x, lx - 1, 3);
+        j_out[e] = (uint32_t)j;
+    });
+}
+__global__ void __launch_bounds__(256) k_halo_gather(const PtF *__restrict__ pts, const uint32_t *__restrict__ j_h, int64_t n_h, PtF *out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n_h) out[e] = pts[j_h[e]];
+}
+
 // cs_h gets the gap bits of the finished cell_start (same cells are empty in both)
 __global__ void __launch_bounds__(256) k_gap_copy(const uint32_t *__restrict__ cs, uint32_t *cs_h, int64_t n1, uint32_t mask) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -480,6 +521,7 @@ static bool make_geom(const float lo[3], const float hi[3], double h, Geom<Real>
     g->cs_mask = 0xffffffffu;
     g->seed = nullptr;
     g->halo = (Real)0; g->cs_h = nullptr; g->pts_h = nullptr; g->j_h = nullptr; g->rowocc = nullptr; g->nyw = 0; g->nxb = 0; g->lbox = nullptr; g->gbox = nullptr; g->lbox_h = nullptr; g->gbox_h = nullptr;
+    g->xq = (Real)0;
     return true;
 }
 
@@ -506,6 +548,16 @@ static pcr_status sort_pairs(pcr_context *ctx, K *keys_in, K *keys_out, uint32_t
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit,
                                                ctx->stream));
     return PCR_OK;
+}
+
+// The host-side rule: which targets store the records of a cell in ascending x.  float32 point targets (the centroid filter
+// index of a voxel target is searched by tracking searches only and stays as it was) without heavy cells -- those keep the
+// Morton order their leaf / group boxes need -- whose (cell, x offset) key fits 64 bits; PCR_XORDER=0 builds the old order
+// (the A/B switch: read when a target is built, never on the pass path).
+extern "C" int pcr_x_order_rule(int f32_point_target, int heavy, int64_t n, int cell_bits) {
+    const char *e = getenv("PCR_XORDER");
+    if (e && *e && atoi(e) == 0) return 0;
+    return f32_point_target && !heavy && n > 0 && cell_bits + PCR_XQ_BITS <= 64 ? 1 : 0;
 }
 
 static int bits_for(double ncells) {
@@ -554,7 +606,15 @@ static pcr_status build_halo_lists(pcr_context *ctx, Geom<float> gh, const PtF *
     HIP_TRY(pts_h->alloc_exact((size_t)n_h + PCR_PTS_PAD));
     HIP_TRY(j_h->alloc_exact((size_t)n_h + PCR_PTS_PAD));
     hipLaunchKernelGGL(k_pad_sentinels<PtF>, dim3(1), dim3(64), 0, ctx->stream, pts_h->p + (size_t)n_h);
-    hipLaunchKernelGGL(k_halo_fill, dim3(nb), dim3(256), 0, ctx->stream, pts, n, gh, cs, (const uint32_t *)cs_h->p, cursor.p, pts_h->p, j_h->p);
+    if (gh.xq > 0.f && n_h > 0) {
+        DevBuf<unsigned long long> key, key2;
+        DevBuf<uint32_t> j_tmp;
+        HIP_TRY(key.alloc((size_t)n_h)); HIP_TRY(key2.alloc((size_t)n_h)); HIP_TRY(j_tmp.alloc((size_t)n_h));
+        hipLaunchKernelGGL(k_halo_fill_x, dim3(nb), dim3(256), 0, ctx->stream, pts, n, gh, cs, (const uint32_t *)cs_h->p, cursor.p, key.p, j_tmp.p);
+        PCR_TRY(sort_pairs<unsigned long long>(ctx, key, key2, j_tmp, j_h->p, n_h, bits_for((double)ncells) + PCR_XQ_BITS + 2));
+        hipLaunchKernelGGL(k_halo_gather, dim3((unsigned)((n_h + 255) / 256)), dim3(256), 0, ctx->stream, pts, (const uint32_t *)j_h->p, n_h, pts_h->p);
+    } else
+        hipLaunchKernelGGL(k_halo_fill, dim3(nb), dim3(256), 0, ctx->stream, pts, n, gh, cs, (const uint32_t *)cs_h->p, cursor.p, pts_h->p, j_h->p);
     hipLaunchKernelGGL(k_gap_copy, dim3((unsigned)((nc1 + 255) / 256)), dim3(256), 0, ctx->stream, cs, cs_h->p, (int64_t)nc1, gh.cs_mask);
     HIP_TRY(hipGetLastError());
     *n_h_out = n_h;                 // (not synchronised: every caller synchronises the stream before it hands the lists out)
@@ -681,6 +741,9 @@ static pcr_status build_grid(pcr_context *ctx, const T *d_xyz, int64_t n, double
     // there): 8 consecutive records are 8 neighbours along the line.  <= 9 keeps the 32-bit key.
     int sub_bits = 0;
     bool wide = false;
+    // Targets WITHOUT heavy cells: minor sort key = the x offset inside the cell (Geom::xq), through the same 64-bit sort.
+    const bool xorder = pcr_x_order_rule(heavy_out != nullptr && sizeof(Real) == 4, heavy, n, bits_for(ncells)) != 0;
+    if (xorder) { sub_bits = PCR_XQ_BITS; wide = true; }
     if (heavy) {
         static const int want = getenv("PCR_HEAVY_SUB_BITS") ? atoi(getenv("PCR_HEAVY_SUB_BITS")) : 18;
         const int w = (want < 0 ? 0 : (want > 21 ? 21 : want)) / 3 * 3;
@@ -695,7 +758,7 @@ static pcr_status build_grid(pcr_context *ctx, const T *d_xyz, int64_t n, double
         DevBuf<unsigned long long> d_key, d_key2;
         HIP_TRY(d_key.alloc(nn)); HIP_TRY(d_key2.alloc(nn));
         hipLaunchKernelGGL((k_cell_ids<Real, T, unsigned long long>), dim3(nb), dim3(256), 0, ctx->stream, d_xyz, n, g, d_key.p, d_idx.p,
-                           (uint32_t *)nullptr, (unsigned long long *)nullptr, sub_bits);
+                           (uint32_t *)nullptr, (unsigned long long *)nullptr, sub_bits, xorder);
         PCR_TRY(sort_pairs<unsigned long long>(ctx, d_key, d_key2, d_idx, d_idx2, n, bits_for(ncells) + sub_bits));
         hipLaunchKernelGGL(k_cell_heads<unsigned long long>, dim3(nb), dim3(256), 0, ctx->stream, (const unsigned long long *)d_key2.p, n,
                            (int64_t)ncells, d_counts.p, d_nz.p, sub_bits);
@@ -724,6 +787,7 @@ static pcr_status build_grid(pcr_context *ctx, const T *d_xyz, int64_t n, double
     // ---- halo lists (point targets with a gap field: both share the 28-bit offsets)
     g.halo = (Real)0; g.cs_h = nullptr; g.pts_h = nullptr; g.j_h = nullptr; g.rowocc = nullptr; g.nyw = 0; g.nxb = 0;
     g.lbox = nullptr; g.gbox = nullptr; g.lbox_h = nullptr; g.gbox_h = nullptr;
+    g.xq = xorder ? (Real)((double)g.h / (double)(1 << PCR_XQ_BITS)) : (Real)0;
     DevBuf<uint32_t> d_cs_h, d_j_h;
     DevBuf<PtF> d_pts_h;
     int64_t n_h = 0;
@@ -1090,6 +1154,7 @@ pcr_status pcr_attach_points_f64(pcr_context *ctx, pcr_target *t, const double *
     g.cs_mask = gf.cs_mask;
     g.seed = nullptr; g.halo = 0; g.cs_h = nullptr; g.pts_h = nullptr; g.j_h = nullptr; g.rowocc = nullptr; g.nyw = 0; g.nxb = 0;
     g.lbox = nullptr; g.gbox = nullptr; g.lbox_h = nullptr; g.gbox_h = nullptr;
+    g.xq = 0;                      // (the float64 side is searched by nn_scan_range: correct on any order inside a cell)
     return PCR_OK;
 }
 

@@ -174,8 +174,8 @@ __device__ __forceinline__ void nn_chunk_loop(const LinArgs &a, Body &&body) {
 #ifndef PCR_VOX_WAVES
 #define PCR_VOX_WAVES 4
 #endif
-template <int VOXEL, int HALO, int LOCAL, int MODE, bool LB = false>
-__global__ void __launch_bounds__(256, VOXEL == 2 ? PCR_VOX_WAVES : (LB ? 4 : 5)) k_nn_scan(const LinArgs a) {       // LB: see nn_point
+template <int VOXEL, int HALO, int LOCAL, int MODE, int LB = PCR_RANGE_PLAIN>
+__global__ void __launch_bounds__(256, VOXEL == 2 ? PCR_VOX_WAVES : (LB == PCR_RANGE_BOXES ? 4 : 5)) k_nn_scan(const LinArgs a) {       // LB: see nn_point
     PoseK P;
     PoseQ Q;
     if (!load_pose<false>(a, P)) return;
@@ -531,7 +531,7 @@ __global__ void __launch_bounds__(64) k_publish(const double *__restrict__ out, 
 }
 
 // ---- fine seam: plain NN queries (no transform), original indices out -------------------------
-template <typename Real, typename PT, bool HALO, bool LB = false>
+template <typename Real, typename PT, bool HALO, int LB = PCR_RANGE_PLAIN>
 __global__ void __launch_bounds__(256) k_nn_query(Geom<Real> g, const PT *pts, const uint32_t *cs,
                                                   const float *q, int64_t m, Real bound2, Real rmax,
                                                   Real *dist, int64_t *idx) {
@@ -569,6 +569,8 @@ __global__ void __launch_bounds__(256) k_nn_query_q6(Geom<float> gf, const PtF *
 // launch functions: run-time arguments -> kernel instantiation (declared in pass_device.h, called from pass.hip)
 // =============================================================================================
 static const dim3 kBlock(256);
+// how the plain float32 search scans the ranges of this point target (nn_device.h)
+static int range_mode(const Geom<float> &g) { return g.lbox != nullptr ? PCR_RANGE_BOXES : (g.xq > 0.f ? PCR_RANGE_XORDER : PCR_RANGE_PLAIN); }
 
 void launch_certify(bool voxel, dim3 grid, hipStream_t st, const LinArgs &a) {
     with_const<2>(voxel, [&](auto V) { hipLaunchKernelGGL(k_certify<V()>, grid, kBlock, 0, st, a); });
@@ -578,18 +580,18 @@ void launch_certify(bool voxel, dim3 grid, hipStream_t st, const LinArgs &a) {
 // searches of the device-resident loop only (a tracking search takes 2 as 1, a LIST pass deals chunks and ignores it)
 void launch_nn_scan(int voxel, int mode, bool halo, int local, dim3 grid, hipStream_t st, const LinArgs &a) {
     const int l = mode == PCR_NN_LIST ? 0 : (mode == PCR_NN_FULL && local == 2) ? 2 : local != 0;
-    // (LB: plain full searches of a point target with heavy cells, Geom::lbox)
-    const bool lb = voxel == 0 && mode == PCR_NN_FULL && a.gf.lbox != nullptr;
+    // (LB: plain full searches of a point target with heavy cells, Geom::lbox, or with the x order, Geom::xq)
+    const int lb = voxel == 0 && mode == PCR_NN_FULL ? range_mode(a.gf) : PCR_RANGE_PLAIN;
     with_const<3>(voxel, [&](auto V) {
         with_const<3>(mode, [&](auto M) {
             with_const<2>(halo && voxel == 0, [&](auto H) {
                 with_const<3>(l, [&](auto L) {
-                    with_const<2>(lb, [&](auto B) {
+                    with_const<3>(lb, [&](auto B) {
                         // lists and leaf boxes: point targets only; LB: full searches only.  (LOCAL == 2 exists for tracking and
                         // LIST searches too, as it always has, although `l` above never selects it: the set of kernels is
                         // held fixed here)
                         if constexpr (!(V() != 0 && (H() || B())) && !(M() != PCR_NN_FULL && B()))
-                            hipLaunchKernelGGL((k_nn_scan<V(), H(), L(), M(), B() != 0>), grid, kBlock, 0, st, a);
+                            hipLaunchKernelGGL((k_nn_scan<V(), H(), L(), M(), B()>), grid, kBlock, 0, st, a);
                     });
                 });
             });
@@ -644,7 +646,7 @@ static void with_fused_variant(int kind, const FusedVariant &v, F &&go) {
         with_const<2>(v.halo, [&](auto H) {
             with_const<2>(v.gn, [&](auto G) {
                 with_const<2>(v.filt, [&](auto FL) {
-                    with_const<2>(v.lb, [&](auto LB) {
+                    with_const<3>(v.lb, [&](auto LB) {
                         constexpr bool point = K() == PCR_ICP || K() == PCR_PLANE;
                         if constexpr (point ? !FL() : (!LB() && (FL() || !H()))) go(K, H, G, FL, LB);
                     });
@@ -660,8 +662,13 @@ void launch_fused(int kind, const FusedVariant &v, dim3 grid, hipStream_t st, co
 }
 void launch_fused_batch(int kind, const FusedVariant &v, dim3 grid, hipStream_t st, const LinArgs &a, const FinArgs &f,
                         const BatchItem *items) {
-    with_fused_variant(kind, v, [&](auto K, auto H, auto G, auto FL, auto LB) {
-        hipLaunchKernelGGL((k_linearize_batch<K(), H(), G(), FL(), LB()>), grid, kBlock, 0, st, a, f, items);
+    // (the batched kernel has no x-ordered instantiation: it scans the ranges of an x-ordered target plainly, which is exact on
+    // any order inside a cell and gives the single launch's matches and sums)
+    FusedVariant vb = v;
+    if (vb.lb == PCR_RANGE_XORDER) vb.lb = PCR_RANGE_PLAIN;
+    with_fused_variant(kind, vb, [&](auto K, auto H, auto G, auto FL, auto LB) {
+        if constexpr (LB() != PCR_RANGE_XORDER)
+            hipLaunchKernelGGL((k_linearize_batch<K(), H(), G(), FL(), LB()>), grid, kBlock, 0, st, a, f, items);
     });
 }
 
@@ -685,8 +692,8 @@ void launch_nn_query(const pcr_target *t, int form, hipStream_t st, const float 
     const dim3 grid((unsigned)((m + 255) / 256));
     if (form == 0) {
         with_const<2>(t->cs_h != nullptr, [&](auto H) {
-            with_const<2>(t->gf.lbox != nullptr, [&](auto B) {
-                hipLaunchKernelGGL((k_nn_query<float, PtF, H() != 0, B() != 0>), grid, kBlock, 0, st, t->gf, t->pts, t->cell_start, q, m,
+            with_const<3>(range_mode(t->gf), [&](auto B) {
+                hipLaunchKernelGGL((k_nn_query<float, PtF, H() != 0, B()>), grid, kBlock, 0, st, t->gf, t->pts, t->cell_start, q, m,
                                    (float)bound2, (float)rmax, (float *)dist, idx);
             });
         });
@@ -709,7 +716,7 @@ int nn_blocks_per_cu(int which) {
     case PCR_OCC_POINT: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_scan<0, 1, 0, 0>, 256, 0); break;
     case PCR_OCC_VOXEL: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_scan<1, 0, 0, 0>, 256, 0); break;
     case PCR_OCC_FILTER: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_filter<1, 0>, 256, 0); break;
-    case PCR_OCC_POINT_LB: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_scan<0, 1, 0, 0, true>, 256, 0); break;
+    case PCR_OCC_POINT_LB: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_scan<0, 1, 0, 0, PCR_RANGE_BOXES>, 256, 0); break;
 #ifdef PCR_DEV
     case PCR_OCC_MFMA: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_nn_mfma<1, 0>, 256, 0); break;
 #endif

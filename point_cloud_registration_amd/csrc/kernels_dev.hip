@@ -194,15 +194,17 @@ __global__ void __launch_bounds__(256) k_nn_coop(const LinArgs a) {
 
 // work counters of the search (instrumentation; same traversal as k_nn_scan<0>): out[0..3] = per-lane
 // sums of rings, rows loaded, rows pruned by arithmetic, candidates tested; out[4..7] = the same with
-// the per-WAVE maximum charged to all 64 lanes (what the SIMD actually executes under divergence)
-template <int HALO, bool LB = false>
+// the per-WAVE maximum charged to all 64 lanes (what the SIMD actually executes under divergence); out[11..12] = of the
+// candidates tested, those an x-ordered scan could not skip against `best` at the time / against the final best (NNStats)
+template <int HALO, int LB = PCR_RANGE_PLAIN>
 __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned long long *out) {
     const TileIter it(a);
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long cyc[3] = {0, 0, 0};                  // wave wall-clock: prologue, ring 0, outer rings
+    unsigned long long xs[2] = {0, 0};
     for (int64_t i0 = it.base - threadIdx.x; i0 < it.end; i0 += it.stride) {
         const int64_t i = i0 + threadIdx.x;
-        NNStats st = {0, 0, 0, 0};
+        NNStats st = {0, 0, 0, 0, 0, 0, 0.f};
         const unsigned long long t0 = __builtin_readcyclecounter();
         float tx = 0, ty = 0, tz = 0;
         const bool live = i < it.end;
@@ -211,6 +213,12 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
             xform(a.hp, x, y, z, tx, ty, tz);
         }
         uint32_t bj = PCR_NONE, bo = PCR_NONE; float best = a.bound2_f;
+        if (live && LB == PCR_RANGE_PLAIN) {                                  // the final best first: what cand_fin is measured against
+            if (HALO) nn_search<float, PtF, false, false, true>(a.gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo);
+            else nn_search<float, PtF, false, false, false>(a.gf, a.pts, a.cell_start, tx, ty, tz, a.bound2_f, best, bj, bo);
+            st.fin = best;
+            bj = PCR_NONE; bo = PCR_NONE; best = a.bound2_f;
+        }
         NNCell<float> c = nn_cell<float>(a.gf, tx, ty, tz, a.bound2_f);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long t1 = __builtin_readcyclecounter();
@@ -223,6 +231,7 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
         const unsigned long long t3 = __builtin_readcyclecounter();
         cyc[0] += t1 - t0; cyc[1] += t2 - t1; cyc[2] += t3 - t2;
         uint32_t v[4] = {st.rings, st.rows_loaded, st.rows_pruned, st.cand};
+        xs[0] += st.cand_now; xs[1] += st.cand_fin;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
             uint32_t m = v[c4];
@@ -232,6 +241,7 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
         }
     }
     for (int c = 0; c < 8; ++c) atomicAdd(&out[c], acc[c]);
+    atomicAdd(&out[11], xs[0]); atomicAdd(&out[12], xs[1]);
     if ((threadIdx.x & 63) == 0) for (int c = 0; c < 3; ++c) atomicAdd(&out[8 + c], cyc[c]);
 }
 
@@ -333,7 +343,7 @@ int pcr_dev_coop_blocks_per_cu() {
 }
 
 // ---- instrumentation: search work counters for one pose (point targets) ------------------------
-extern "C" pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[11]) {
+static pcr_status nn_counters_run(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[13]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     PCR_REQUIRE(!t->is_voxel, "counters are implemented for point targets");
     pcr_context *ctx = t->ctx;
@@ -350,19 +360,34 @@ extern "C" pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T
     const double bound = max_dist * (1.0 + 1e-6);
     a.bound2_f = (float)(bound * bound);
     a.nblocks = choose_blocks(ctx, s->n);
-    unsigned long long h[11];
+    unsigned long long h[13];
     CtxScope scope(ctx);
     DevBuf<unsigned long long> d;
-    HIP_TRY(d.alloc(11));
+    HIP_TRY(d.alloc(13));
     HIP_TRY(hipMemsetAsync(d.p, 0, sizeof h, ctx->stream));
-    if (t->gf.lbox && t->cs_h) hipLaunchKernelGGL((k_nn_counters<1, true>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
-    else if (t->gf.lbox) hipLaunchKernelGGL((k_nn_counters<0, true>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
+    if (t->gf.lbox && t->cs_h) hipLaunchKernelGGL((k_nn_counters<1, PCR_RANGE_BOXES>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
+    else if (t->gf.lbox) hipLaunchKernelGGL((k_nn_counters<0, PCR_RANGE_BOXES>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
+    else if (t->gf.xq > 0.f && t->cs_h) hipLaunchKernelGGL((k_nn_counters<1, PCR_RANGE_XORDER>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
+    else if (t->gf.xq > 0.f) hipLaunchKernelGGL((k_nn_counters<0, PCR_RANGE_XORDER>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
     else if (t->cs_h) hipLaunchKernelGGL(k_nn_counters<1>, dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
     else hipLaunchKernelGGL(k_nn_counters<0>, dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 11; ++i) out[i] = (double)h[i];
+    for (int i = 0; i < 13; ++i) out[i] = (double)h[i];
+    return PCR_OK;
+}
+extern "C" pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[11]) {
+    double all[13];
+    PCR_TRY(nn_counters_run(t, s, T, max_dist, all));
+    for (int i = 0; i < 11; ++i) out[i] = all[i];
+    return PCR_OK;
+}
+extern "C" pcr_status pcr_nn_counters_x(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[3]) {
+    PCR_REQUIRE(out, "NULL argument");
+    double all[13];
+    PCR_TRY(nn_counters_run(t, s, T, max_dist, all));
+    out[0] = all[3]; out[1] = all[11]; out[2] = all[12];
     return PCR_OK;
 }
 

@@ -192,7 +192,88 @@ __device__ __forceinline__ void nn_scan_range(const PT *__restrict__ pts, uint32
 }
 
 // Per-lane work counters, compiled in only for pcr_nn_counters (STATS = true).
-struct NNStats { uint32_t rings, rows_loaded, rows_pruned, cand; };
+struct NNStats {
+    uint32_t rings, rows_loaded, rows_pruned, cand;
+    // what a scan that knew the order of x inside a range could skip (plain float32 search only): of the candidates tested,
+    // those whose bound (p.x - q.x)^2 + dyz^2 (dyz: the row's slab distance, 0 for ring 0) was within `best` at the moment of
+    // the test / within the final best `fin`, which the caller found with a search of its own beforehand
+    uint32_t cand_now, cand_fin;
+    float fin;
+};
+
+// nn_scan_range<float, PtF, 0, B> with the two counts above
+template <int B>
+__device__ __forceinline__ void nn_scan_range_xstat(const float4 *__restrict__ pts, uint32_t s, uint32_t e, float qx, float qy, float qz,
+                                                    float dyz2, float &best, uint32_t &bj, uint32_t &borig, NNStats *st) {
+    for (uint32_t j = s; j < e; j += B) {
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            const float4 p = pts[j + u];
+            const float dx = p.x - qx, lb = __builtin_fmaf(dx, dx, dyz2);
+            st->cand_now += lb <= best ? 1u : 0u;
+            st->cand_fin += lb <= st->fin ? 1u : 0u;
+            nn_test_f32<0>(p, j + u, qx, qy, qz, best, bj, borig, nullptr);
+        }
+    }
+}
+
+// ---- ranges in ascending x (Geom::xq) ------------------------------------------------------------------------------------
+// How a range is scanned: the template axis LB of the functions below (a target has heavy cells or the x order, never both)
+#define PCR_RANGE_PLAIN 0        // nn_scan_range: every record, left to right
+#define PCR_RANGE_BOXES 1        // nn_scan_range_lb: behind leaf / group boxes (heavy targets)
+#define PCR_RANGE_XORDER 2       // nn_scan_range_x: from the query's x outward (x-ordered targets)
+// Records [s, e) of an x-ordered array: a row of cells at fixed (y, z), one cell, or one extended list -- for positions i < j
+// inside the range x[i] <= x[j] + xq + slack.  Every record of the range is at least dyz2 (the row's slab distance, 0 for a list)
+// + (p.x - qx)^2 away, so beyond |p.x - qx| > xr = sqrt(best - dyz2) nothing can win or tie.  The scan starts at the batch
+// that holds position s + t (e - s) -- t in [0, 1]: where the query's x lies in the x extent of the range's cells; a poor guess
+// costs candidates, never exactness -- and walks UP while the last record of the batch just tested, which every later record
+// of the range follows, is within xr + xm on the right of the query, then DOWN from the start while the first record of the
+// lowest batch is within it on the left.  xr comes from the current best at each test: the first batches hold the row's
+// nearest records and the bound collapses at once.  The exit is strict and loosened by 1.000002 for the native square root,
+// as the cell-level clip of nn_rings is, and by xm = 2 (xq + slack): one for the order of the records, one because dlo below
+// is a maximum over batches whose first records are themselves only ordered up to xq + slack.  So a record AT the best
+// distance (which may win on the smaller index) is never skipped.  Batches start at s + multiples of B: a downward batch
+// never reads below s, an upward batch over-reads into the tail pad like nn_scan_range.  best - dyz2 < 0 (an over-read record
+// of ANOTHER row won: nothing of this row can beat it) makes xr a NaN, and both tests are written so that a NaN ends the scan.
+// Two loops, not one with a direction flag: the flag cost a dozen VALU operations per batch in selects and masks.  The square
+// root is the bare v_sqrt_f32 (1 ulp; __fsqrt_rn wraps it in five more operations that rescale denormal arguments): an
+// argument below 1e-38 gives 0 where the root is below 1e-19, far inside the margin.
+template <int B, bool STATS = false>
+__device__ __forceinline__ void nn_scan_range_x(const float4 *__restrict__ pts, uint32_t s, uint32_t e, float t, float xm, float dyz2,
+                                                float qx, float qy, float qz, float &best, uint32_t &bj, uint32_t &borig,
+                                                NNStats *st = nullptr) {
+    if (e <= s) return;
+    const uint32_t n = e - s;
+    const uint32_t j0 = s + min((uint32_t)(fminf(fmaxf(t, 0.f), 1.f) * (float)n), n - 1u) / B * B;
+    float dlo = -RealTraits<float>::inf();        // qx - x of the first record of the lowest batch tested so far (the start batch's)
+    for (uint32_t j = j0;;) {
+        const float4 *__restrict__ b = pts + j;
+        float4 p[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) p[u] = b[u];
+#pragma unroll
+        for (int u = 0; u < B; ++u) nn_test_f32<0>(p[u], j + u, qx, qy, qz, best, bj, borig, nullptr);
+        if (STATS) st->cand += B;
+        dlo = fmaxf(dlo, qx - p[0].x);
+        j += B;
+        if (j >= e) break;
+        const float xr = __builtin_fmaf(__builtin_amdgcn_sqrtf(best - dyz2), 1.000002f, xm);
+        if (!(p[B - 1].x - qx <= xr)) break;
+    }
+    for (uint32_t j = j0; j > s;) {
+        const float xr = __builtin_fmaf(__builtin_amdgcn_sqrtf(best - dyz2), 1.000002f, xm);
+        if (!(dlo <= xr)) break;
+        j -= B;
+        const float4 *__restrict__ b = pts + j;
+        float4 p[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) p[u] = b[u];
+#pragma unroll
+        for (int u = 0; u < B; ++u) nn_test_f32<0>(p[u], j + u, qx, qy, qz, best, bj, borig, nullptr);
+        if (STATS) st->cand += B;
+        dlo = qx - p[0].x;
+    }
+}
 
 // ---- ranges with leaf / group boxes (Geom::lbox; round 6) ---------------------------------------------------------------
 // Squared distance from the query to a box of records, by the candidates' own formula: for every record p inside the box
@@ -353,7 +434,7 @@ __device__ __forceinline__ NNCell<Real> nn_cell(const Geom<Real> &g, Real qx, Re
 // nearly converged query (residual << halo) is certified by ring 0 alone and never enters the ring
 // loop: without the halo the ~8 % of lanes that sit closer to a face than to their match drag their
 // whole wave through ring 1 (measured: 75 % of the wave time at the converged pose).
-template <typename Real, typename PT, bool STATS = false, bool HALO = false, int TRACK = 0, int B = PCR_NN_BATCH, bool LB = false>
+template <typename Real, typename PT, bool STATS = false, bool HALO = false, int TRACK = 0, int B = PCR_NN_BATCH, int LB = PCR_RANGE_PLAIN>
 __device__ __forceinline__ int nn_ring0(const Geom<Real> &g, const PT *__restrict__ pts, const uint32_t *__restrict__ cs,
                                         NNCell<Real> &c, Real qx, Real qy, Real qz,
                                         Real &best, uint32_t &bj, uint32_t &borig, NNStats *st = nullptr,
@@ -371,9 +452,12 @@ __device__ __forceinline__ int nn_ring0(const Geom<Real> &g, const PT *__restric
         // landed one cell off the surface is served like one inside an occupied cell.
         const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
         if (e_ > s_) {
-            if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+            if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
             uint32_t ej = PCR_NONE;
-            if constexpr (LB) nn_scan_range_lb<B, STATS>((const PtF *)g.pts_h, g.lbox_h, g.gbox_h, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, ej, borig, st);
+            if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>((const PtF *)g.pts_h, g.lbox_h, g.gbox_h, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, ej, borig, st);
+            // (x order: the list's points lie within the halo of the cell: the query's place in [-halo, h + halo])
+            else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>((const PtF *)g.pts_h, s_, e_, (c.fx + g.halo) * __frcp_rn(g.h + 2.f * g.halo), 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, ej, borig, st);
+            else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>((const PtF *)g.pts_h, s_, e_, qx, qy, qz, 0.f, best, ej, borig, st);
             else nn_scan_range<Real, PT, TRACK, B>((const PT *)g.pts_h, s_, e_, qx, qy, qz, best, ej, borig, tk);
             if (ej != PCR_NONE) bj = g.j_h[ej];
             c.reach0 = g.halo;
@@ -383,8 +467,10 @@ __device__ __forceinline__ int nn_ring0(const Geom<Real> &g, const PT *__restric
         }
     } else if (gap == 0) {
         const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
-        if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-        if constexpr (LB) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st);
+        if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+        if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st);
+        else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, c.fx * g.inv_h, 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, bj, borig, st);
+        else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, 0.f, best, bj, borig, st);
         else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
         return 1;
     }
@@ -412,7 +498,7 @@ __device__ __forceinline__ bool nn_certified(const Geom<Real> &g, const NNCell<R
 
 // Rings kstart (>= 1) .. kmax.
 // (a tracking search prunes with tk->prune wherever the plain one prunes with best: PB below)
-template <typename Real, typename PT, bool STATS = false, int TRACK = 0, int B = PCR_NN_BATCH, bool LB = false>
+template <typename Real, typename PT, bool STATS = false, int TRACK = 0, int B = PCR_NN_BATCH, int LB = PCR_RANGE_PLAIN>
 __device__ __forceinline__ void nn_rings(const Geom<Real> &g, const PT *__restrict__ pts, const uint32_t *__restrict__ cs,
                                          const NNCell<Real> &c, int kstart, Real qx, Real qy, Real qz,
                                          Real &best, uint32_t &bj, uint32_t &borig, NNStats *st = nullptr,
@@ -423,6 +509,7 @@ __device__ __forceinline__ void nn_rings(const Geom<Real> &g, const PT *__restri
     const int cx = c.cx, cy = c.cy, cz = c.cz;
     const Real fx = c.fx, fy = c.fy, fz = c.fz;
     const uint32_t unx = (uint32_t)g.nx, plane = (uint32_t)g.ny * (uint32_t)g.nx;   // ncells < 2^32
+    [[maybe_unused]] const Real rx = (Real)cx + fx * g.inv_h;                       // x order: the query's x in cells
     for (int k = kstart; k <= c.kmax; ++k) {
         if (nn_certified<Real>(g, c, k, PB)) break;
         if (STATS) st->rings++;
@@ -458,19 +545,19 @@ __device__ __forceinline__ void nn_rings(const Geom<Real> &g, const PT *__restri
                     }
                     if (xl <= xh) {
                         const uint32_t s_ = cs[row + (uint32_t)xl] & g.cs_mask, e_ = cs[row + (uint32_t)xh + 1u] & g.cs_mask;
-                        if (STATS) { st->rows_loaded++; st->cand += LB ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-                        if constexpr (LB) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
+                        if (STATS) { st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+                        if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, (rx - (Real)xl) * __frcp_rn((Real)(xh - xl + 1)), 2.f * (g.xq + g.slack), dyz2, qx, qy, qz, best, bj, borig, st); else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, dyz2, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
                     }
                 } else {                                    // interior row of the ring: its two end cells
                     if (xa_in && dyz2 + dxa <= PB) {
                         const uint32_t s_ = cs[row + (uint32_t)xa] & g.cs_mask, e_ = cs[row + (uint32_t)xa + 1u] & g.cs_mask;
-                        if (STATS) { st->rows_loaded++; st->cand += LB ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-                        if constexpr (LB) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
+                        if (STATS) { st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+                        if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, (Real)1, 2.f * (g.xq + g.slack), dyz2, qx, qy, qz, best, bj, borig, st); else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, dyz2, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
                     }
                     if (xb_in && dyz2 + dxb <= PB) {
                         const uint32_t s_ = cs[row + (uint32_t)xb] & g.cs_mask, e_ = cs[row + (uint32_t)xb + 1u] & g.cs_mask;
-                        if (STATS) { st->rows_loaded++; st->cand += LB ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-                        if constexpr (LB) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
+                        if (STATS) { st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+                        if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st); else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, (Real)0, 2.f * (g.xq + g.slack), dyz2, qx, qy, qz, best, bj, borig, st); else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, dyz2, best, bj, borig, st); else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
                     }
                 }
             }
@@ -583,7 +670,7 @@ __device__ __forceinline__ void nn_rings_occ(const Geom<Real> &g, const PT *__re
 // TRACK: `tk` was initialised with nn_track_init(tk, bound2, mu); on return min(tk->second, tk->pmin) is a lower
 // bound on the squared distance to every target point other than the winner (to every point if there is none).
 template <typename Real, typename PT, bool STATS = false, bool SEEDED = false, bool HALO = false, int TRACK = 0, bool OCC = false,
-          int B = PCR_NN_BATCH, bool LB = false>
+          int B = PCR_NN_BATCH, int LB = PCR_RANGE_PLAIN>
 __device__ __forceinline__ void nn_search(const Geom<Real> &g, const PT *__restrict__ pts,
                                           const uint32_t *__restrict__ cs,
                                           Real qx, Real qy, Real qz, Real bound2,
@@ -591,10 +678,10 @@ __device__ __forceinline__ void nn_search(const Geom<Real> &g, const PT *__restr
                                           NNTrack<Real> *tk = nullptr) {
     if (!SEEDED) { best = bound2; bj = PCR_NONE; borig = PCR_NONE; }
     NNCell<Real> c = nn_cell<Real>(g, qx, qy, qz, bound2);
-    static_assert(!LB || (sizeof(Real) == 4 && TRACK == 0 && !OCC), "leaf / group boxes: plain float32 point search only");
+    static_assert(LB == PCR_RANGE_PLAIN || (sizeof(Real) == 4 && TRACK == 0 && !OCC), "leaf / group boxes, x order: plain float32 point search only");
     const int kstart = nn_ring0<Real, PT, STATS, HALO, TRACK, B, LB>(g, pts, cs, c, qx, qy, qz, best, bj, borig, st, tk);
-    if constexpr (LB) {
-        nn_rings<Real, PT, STATS, TRACK, B, true>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
+    if constexpr (LB != PCR_RANGE_PLAIN) {
+        nn_rings<Real, PT, STATS, TRACK, B, LB>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
     } else if (OCC) nn_rings_occ<Real, PT, STATS, TRACK>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
     else nn_rings<Real, PT, STATS, TRACK, B>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
 }

@@ -319,7 +319,7 @@ static FusedVariant fused_variant(const Pass *ps) {
     FusedVariant v;
     v.filt = t->is_voxel && ps->a.band_f > 0.f && ps->fused_fin;
     v.halo = t->is_voxel ? (v.filt && t->filter->cs_h != nullptr) : t->cs_h != nullptr;
-    v.lb = !t->is_voxel && ps->a.gf.lbox != nullptr;
+    v.lb = t->is_voxel ? PCR_RANGE_PLAIN : (ps->a.gf.lbox != nullptr ? PCR_RANGE_BOXES : (ps->a.gf.xq > 0.f ? PCR_RANGE_XORDER : PCR_RANGE_PLAIN));
     v.gn = ps->gn_inline;
     return v;
 }

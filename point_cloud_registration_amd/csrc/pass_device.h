@@ -512,7 +512,7 @@ __device__ __forceinline__ void linearize_body(const LinArgs &a, const PoseK &P,
         bool ok;
         if (KIND == PCR_ICP || KIND == PCR_PLANE) {
             float best;
-            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH_SMALL, LB != 0>(a.gf, a.pts, a.cell_start, tx, ty, tz,
+            nn_search<float, PtF, false, false, HALO != 0, false, false, PCR_NN_BATCH_SMALL, LB>(a.gf, a.pts, a.cell_start, tx, ty, tz,
                                                                                                    a.bound2_f, best, bj, bo);
             ok = bj != PCR_NONE && __builtin_sqrtf(best) < a.md_f;                 // icp.py:34 strict gate
         } else if (FILT) {
@@ -718,7 +718,7 @@ __device__ __forceinline__ void nnj_store(uint32_t *p, uint32_t v) {
 // one that moved more searches exactly like the plain kernel (its bound then carries no margin).
 // LB: a target with heavy cells: every range longer than PCR_LB_MIN records is scanned through its leaf / group boxes
 // (nn_scan_range_lb)
-template <int VOXEL, int HALO, int TRACK, bool LB = false>
+template <int VOXEL, int HALO, int TRACK, int LB = PCR_RANGE_PLAIN>
 __device__ __forceinline__ void nn_point(const LinArgs &a, const Geom<float> &gf, const PoseK &P, const PoseQ &Q, int64_t i) {
     const float x = a.sx[i], y = a.sy[i], z = a.sz[i];
     float tx, ty, tz;
@@ -1119,7 +1119,8 @@ static void with_const(int v, F &&f) {
 // halo = the target has the extended lists, lb = heavy target (ranges through their leaf / group boxes); voxel targets: filt =
 // float32 filter search over the rounded centroids (halo then refers to the FILTER index); gn = the Gauss-Newton step inline.
 struct FusedVariant {
-    bool halo, filt, lb, gn;
+    bool halo, filt, gn;
+    int lb;              // PCR_RANGE_PLAIN / _BOXES (heavy target) / _XORDER (x-ordered target): nn_device.h
 };
 void launch_certify(bool voxel, dim3 grid, hipStream_t st, const LinArgs &a);
 void launch_nn_scan(int voxel, int mode, bool halo, int local, dim3 grid, hipStream_t st, const LinArgs &a);

@@ -69,6 +69,11 @@ struct Geom {
     // box (nn_scan_range_lb): a cell of a LiDAR sweep's inner rings holds hundreds of points where the average cell holds five.
     // lbox_h / gbox_h: the same over the extended lists (pts_h).
     const float4 *lbox, *gbox, *lbox_h, *gbox_h;
+    // x order (float32 point targets WITHOUT heavy cells; 0 = none): the records of a cell, and of every extended list, are
+    // stored in ascending x up to this quantum (cell / 65536: the minor sort key), so a row of cells is one range ascending in x:
+    // for positions i < j of a row range or of a list, x[i] <= x[j] + xq + slack.  nn_scan_range_x scans such a range from the
+    // query's x outward and stops on either side at the first record beyond the remaining budget.
+    Real xq;
 };
 #define PCR_LB_MIN 24            // ranges up to this many records are scanned plainly
 #ifndef PCR_HALO2_FRAC
