@@ -500,6 +500,54 @@ PCR_API pcr_status pcr_target_fpfh(pcr_target *t, float r, float *fpfh, int64_t 
 PCR_API pcr_status pcr_feature_match(pcr_context *ctx, const float *A, int64_t na, const float *B, int64_t nb, int dim,
                                      int64_t *idx, float *d2_first, float *d2_second);
 
+/* ---- pose hypotheses from correspondences: RANSAC (no reference counterpart) ---------------
+ * The last third of a global registration: from matches (pcr_feature_match) to a pose that an aligner can start from.
+ * src, dst: m x 3 float32 host arrays, finite; row j is one correspondence, scan point -> map point.  A pose is 12 float32:
+ *   R row-major (9), then t (3); it maps src into the frame of dst (the init_T convention of pcr_align).
+ * Inlier rule, float32, no fma, exactly this order:
+ *     x = ((R00*px + R01*py) + R02*pz) + tx, likewise y and z;  d = x - q;  d2 = (dx*dx + dy*dy) + dz*dz
+ *   row j is an inlier iff d2 <= thr, thr = max_dist * max_dist in float32; a NaN anywhere is not an inlier.  count = the
+ *   number of inliers, an integer: independent of tiling, splitting and order.
+ * Sampling, counter-based: hypothesis h depends on (seed, h, m) only.  mix = SplitMix64's step,
+ *     z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31
+ *   (mix(0) = 0xE220A8397B1DCDAF, mix(1) = 0x910A2DEC89025CC1).  s = mix(seed), u_k = mix(s ^ (4h + k)) for k = 0, 1, 2,
+ *     c0 = mulhi64(u_0, m), c1 = mulhi64(u_1, m - 1), c2 = mulhi64(u_2, m - 2)
+ *     c1 += (c1 >= c0);  a = min(c0, c1), b = max(c0, c1):  c2 += (c2 >= a), then c2 += (c2 >= b)
+ *   -- uniform over the ordered triples of distinct rows.  m < 3 gives no hypotheses.
+ * Validity, float64 over the widened float32 points, no contraction, every dot product (ax*bx + ay*by) + az*bz: for the
+ *   edges (i, j) = (0,1), (1,2), (2,0): a2 = |p_i - p_j|^2, b2 = |q_i - q_j|^2; valid iff every edge has a2 >= s^2 b2,
+ *   b2 >= s^2 a2, a2 >= e^2 and b2 >= e^2 (s = edge_similarity, e = min_edge, widened to float64: Open3D's edge-length checker
+ *   plus a minimum edge length), and both triangles are non-degenerate: |e1|^2 > 0 and |e1 x e2|^2 > 0 on each side.
+ * Fit, the triad construction in float64 with +, -, x, / and sqrt only: on the source side e1 = p1 - p0, e2 = p2 - p0,
+ *   w = e1 x e2, u1 = e1 / sqrt(e1 . e1), u3 = w / sqrt(w . w), u2 = u3 x u1; the same on the destination side gives v1, v2,
+ *   v3 (a x b = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx));
+ *     R[r][c] = (v1[r]*u1[c] + v2[r]*u2[c]) + v3[r]*u3[c];  cp = ((p0 + p1) + p2) / 3, cq likewise;
+ *     t[r] = cq[r] - ((R[r][0]*cp[0] + R[r][1]*cp[1]) + R[r][2]*cp[2]);  R and t rounded to float32.
+ *   An invalid hypothesis has an all-NaN pose and count = -1.  (The 3-point least-squares fit is deliberately not used: it
+ *   needs an eigen or singular value solver that no restatement matches bit for bit; least squares belongs to the refinement
+ *   over all inliers, on the host.)
+ * Selection: the largest count, ties to the smallest h -- a maximum over a key, so it does not depend on the grid or on the
+ *   chunks (PCR_RANSAC_CHUNK hypotheses at a time, default 2^20, read once per process: device memory is bounded by about
+ *   48 bytes x chunk).  Residual sums take no part; there is no early termination: two calls return the same bits.  No valid
+ *   hypothesis: best = -1, the identity pose, count = 0, PCR_OK.
+ * pcr_pose_score: count[i] (and, when not NULL, mask[i * m + j] = 0 / 1 bytes) of poses[i] over all m rows.  With few poses the
+ *   rows are split over blocks and the integer partial counts added; pcr_pose_score_splits(m, b) is the host-side rule (needs
+ *   no device): the number of row splits a call with these sizes uses.  Rows pass through tiles of PCR_RANSAC_TILE.
+ * pcr_ransac_poses: n_hyp hypotheses of `seed`; *best, best_pose, *best_count, *n_valid (the number of valid hypotheses) and,
+ *   when not NULL, per hypothesis the three sampled rows, the pose and the count.  With m < 3 (and n_hyp > 0) those arrays
+ *   read as invalid hypotheses: rows -1, NaN poses, counts -1.
+ * PCR_ERR_INVALID: max_dist or min_edge negative or non-finite; edge_similarity outside [0, 1]; m > 2^24; n_hyp (or b) < 0 or
+ *   > 2^26; src or dst non-finite.  m == 0, b == 0, n_hyp == 0 and m < 3 return PCR_OK without a launch: counts 0, best -1.
+ *   One GPU of one process.  A refused call leaves the context usable.                                                    */
+#define PCR_RANSAC_TILE 256
+PCR_API pcr_status pcr_pose_score(pcr_context *ctx, const float *src, const float *dst, int64_t m, const float *poses /* b x 12 */,
+                                  int64_t b, float max_dist, int32_t *count /* b */, uint8_t *mask_or_null /* b x m */);
+PCR_API pcr_status pcr_ransac_poses(pcr_context *ctx, const float *src, const float *dst, int64_t m, int64_t n_hyp, uint64_t seed,
+                                    float max_dist, float edge_similarity, float min_edge, int64_t *best, float best_pose[12],
+                                    int32_t *best_count, int64_t *n_valid, int32_t *samples_or_null /* n_hyp x 3 */,
+                                    float *poses_or_null /* n_hyp x 12 */, int32_t *counts_or_null /* n_hyp */);
+PCR_API int pcr_pose_score_splits(int64_t m, int64_t b);
+
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the
  * context's stream; pcr_profile_read drains them (synchronises) and reports per-kernel

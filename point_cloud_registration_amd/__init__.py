@@ -21,6 +21,7 @@ from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_wi
 from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
 from .features import compute_fpfh, match_features, select_matches
+from .global_registration import score_poses, fit_rigid, ransac_pose, register_global
 
 __all__ = [
     "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "KDTree", "VoxelGrid", "voxel_filter",
@@ -28,4 +29,5 @@ __all__ = [
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
+    "score_poses", "fit_rigid", "ransac_pose", "register_global",
 ]

@@ -43,6 +43,7 @@ _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
+_i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 
 # name -> (restype, argtypes); also the list of symbols the library must export
@@ -93,6 +94,11 @@ PROTOTYPES = {
     "pcr_target_spfh": (C.c_int, [_vp, C.c_float, _u32p, _i64p]),
     "pcr_target_fpfh": (C.c_int, [_vp, C.c_float, _f32p, _vp]),
     "pcr_feature_match": (C.c_int, [_vp, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _i64p, _f32p, _f32p]),
+    # pose hypotheses from correspondences and pose scoring (include/pcr.h, global_registration.py)
+    "pcr_pose_score": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, _f32p, C.c_int64, C.c_float, _i32p, _vp]),
+    "pcr_ransac_poses": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float,
+                                   C.POINTER(C.c_int64), _f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _vp, _vp, _vp]),
+    "pcr_pose_score_splits": (C.c_int, [C.c_int64, C.c_int64]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -958,6 +964,94 @@ def feature_match(ctx, A, B):
     idx, d1, d2 = np.empty(na, np.int64), np.empty(na, np.float32), np.empty(na, np.float32)
     check(lib().pcr_feature_match(ctx.handle, A, na, B, B.shape[0], A.shape[1], idx, d1, d2))
     return idx, d1, d2
+
+
+RANSAC_TILE = 256               # PCR_RANSAC_TILE of include/pcr.h: rows per tile of k_pose_score
+RANSAC_M_MAX = 1 << 24
+RANSAC_H_MAX = 1 << 26
+
+
+def check_pairs(src, dst):
+    """Paired correspondences as C-contiguous float32 (M, 3) arrays: finite, M <= 2^24, else ValueError (checked before the
+    GPU is touched)."""
+    src, dst = np.asarray(src), np.asarray(dst)
+    if src.ndim != 2 or src.shape[1] != 3 or src.shape != dst.shape:
+        raise ValueError("src and dst must have one shape (M, 3)")
+    if len(src) > RANSAC_M_MAX:
+        raise ValueError("more than 2^24 correspondences")
+    with np.errstate(over="ignore"):
+        src, dst = np.ascontiguousarray(src, dtype=np.float32), np.ascontiguousarray(dst, dtype=np.float32)
+    if not (np.all(np.isfinite(src)) and np.all(np.isfinite(dst))):
+        raise ValueError("src and dst must be finite as float32")
+    return src, dst
+
+
+def check_distance(d, name):
+    """A float32 distance: finite and >= 0, else ValueError."""
+    with np.errstate(over="ignore"):
+        d = float(np.float32(d))
+    if not (np.isfinite(d) and d >= 0):
+        raise ValueError(f"{name} must be finite and >= 0")
+    return d
+
+
+def pose_score(ctx, src, dst, poses, max_dist, want_mask=False):
+    """pcr_pose_score: src, dst (M, 3), poses (B, 12) float32 -> counts (B,) int32 (and masks (B, M) bool with ``want_mask``).
+    ``ctx`` may be a callable that returns the context: it is called after the arguments have passed."""
+    src, dst = check_pairs(src, dst)
+    poses = np.asarray(poses)
+    if poses.ndim != 2 or poses.shape[1] != 12:
+        raise ValueError("poses must have shape (B, 12)")
+    if len(poses) > RANSAC_H_MAX:
+        raise ValueError("more than 2^26 poses")
+    poses = np.ascontiguousarray(poses, dtype=np.float32)
+    max_dist = check_distance(max_dist, "max_dist")
+    b, m = len(poses), len(src)
+    count = np.zeros(b, np.int32)
+    mask = np.zeros((b, m), np.uint8) if want_mask else None
+    if b and m:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_pose_score(ctx.handle, src, dst, m, poses, b, max_dist, count, _ptr(mask)))
+    return (count, mask.view(np.bool_)) if want_mask else count
+
+
+def ransac_poses(ctx, src, dst, n_hyp, seed, max_dist, edge_similarity, min_edge, want_all=False):
+    """pcr_ransac_poses -> dict(best, pose (12,) float32, count, n_valid) and, with ``want_all``, samples (H, 3) int32, poses
+    (H, 12) float32 and counts (H,) int32 of every hypothesis.  ``ctx`` may be a callable, as for ``pose_score``."""
+    src, dst = check_pairs(src, dst)
+    n_hyp, seed = int(n_hyp), int(seed)
+    if not 0 <= n_hyp <= RANSAC_H_MAX:
+        raise ValueError("n_hypotheses must be in [0, 2^26]")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    max_dist, min_edge = check_distance(max_dist, "max_dist"), check_distance(min_edge, "min_edge")
+    edge_similarity = float(np.float32(edge_similarity))
+    if not 0 <= edge_similarity <= 1:
+        raise ValueError("edge_similarity must be in [0, 1]")
+    m = len(src)
+    pose = np.zeros(12, np.float32)
+    pose[[0, 4, 8]] = 1
+    out = {"best": -1, "pose": pose, "count": 0, "n_valid": 0}
+    if want_all:
+        out["samples"] = np.full((n_hyp, 3), -1, np.int32)
+        out["poses"] = np.full((n_hyp, 12), np.nan, np.float32)
+        out["counts"] = np.full(n_hyp, -1, np.int32)
+    if n_hyp == 0 or m < 3:
+        return out
+    if callable(ctx):
+        ctx = ctx()
+    best, count, n_valid = C.c_int64(-1), C.c_int32(0), C.c_int64(0)
+    check(lib().pcr_ransac_poses(ctx.handle, src, dst, m, n_hyp, seed, max_dist, edge_similarity, min_edge, C.byref(best), pose,
+                                 C.byref(count), C.byref(n_valid), _ptr(out.get("samples")), _ptr(out.get("poses")),
+                                 _ptr(out.get("counts"))))
+    out.update(best=best.value, count=count.value, n_valid=n_valid.value)
+    return out
+
+
+def pose_score_splits(m, b):
+    """pcr_pose_score_splits: how many row splits a pcr_pose_score call of b poses over m rows uses (a host-side rule)."""
+    return int(lib().pcr_pose_score_splits(int(m), int(b)))
 
 
 def gn_set(ctx, J, r):

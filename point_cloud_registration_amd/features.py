@@ -1,6 +1,7 @@
 """FPFH descriptors and exact descriptor matching on the MI355X: the first two thirds of a global registration (what Open3D's
 ``compute_fpfh_feature`` and a nearest-neighbour search over the features do), kernels in ``csrc/fpfh.hip``, definitions in
-``include/pcr.h``.  The reference has no counterpart.  Pose hypotheses from the matches are not part of this module.
+``include/pcr.h``.  The reference has no counterpart.  Pose hypotheses from the matches: ``global_registration.py``
+(``ransac_pose``, ``register_global``).
 
 Descriptors are computed over the **float32 copy** of the points, whatever dtype the array has.
 """

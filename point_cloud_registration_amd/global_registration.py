@@ -1,0 +1,174 @@
+"""Global registration on the MI355X: from feature matches to a pose (what Open3D's
+``registration_ransac_based_on_feature_matching`` does after the matching), kernels in ``csrc/ransac.hip``, definitions in
+``include/pcr.h``.  The reference has no counterpart.
+
+``ransac_pose`` draws pose hypotheses from triples of matches, scores every one of them against every match on the GPU and
+refines the winner over its inliers; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose``.  The
+result is an ``init_T`` for ``align`` of any of the local aligners.  Everything is computed over the **float32 copy** of the
+points, and the same call twice returns the same bits.
+"""
+
+import numpy as np
+
+from . import _capi
+from .features import compute_fpfh, match_features
+
+
+def _pairs(source, target, ia, ib):
+    """The paired float32 rows source[ia], target[ib]."""
+    source, target = np.asarray(source), np.asarray(target)
+    for a, name in ((source, "source"), (target, "target")):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must have shape (N, 3)")
+    ia, ib = np.asarray(ia), np.asarray(ib)
+    if ia.ndim != 1 or ia.shape != ib.shape:
+        raise ValueError("ia and ib must be vectors of one length")
+    if len(ia) and not (np.issubdtype(ia.dtype, np.integer) and np.issubdtype(ib.dtype, np.integer)):
+        raise ValueError("ia and ib must be integer row indices")
+    ia, ib = ia.astype(np.int64), ib.astype(np.int64)
+    if len(ia) and (ia.min() < 0 or ia.max() >= len(source) or ib.min() < 0 or ib.max() >= len(target)):
+        raise ValueError("ia / ib point outside source / target")
+    return _capi.check_pairs(source[ia], target[ib])
+
+
+def _poses12(Ts):
+    """(B, 4, 4) or (4, 4) -> (B, 12) float32: R row-major, then t."""
+    Ts = np.asarray(Ts)
+    single = Ts.ndim == 2
+    if single:
+        Ts = Ts[None]
+    if Ts.ndim != 3 or Ts.shape[1:] != (4, 4):
+        raise ValueError("Ts must have shape (B, 4, 4) or (4, 4)")
+    with np.errstate(over="ignore", invalid="ignore"):
+        P = np.concatenate([Ts[:, :3, :3].reshape(len(Ts), 9), Ts[:, :3, 3]], axis=1).astype(np.float32)
+    return np.ascontiguousarray(P), single
+
+
+def _T_of(pose12):
+    T = np.eye(4)
+    T[:3, :3] = np.asarray(pose12[:9], np.float64).reshape(3, 3)
+    T[:3, 3] = pose12[9:]
+    return T
+
+
+def score_poses(source, target, ia, ib, Ts, max_dist, return_mask=False, device=None):
+    """How many of the correspondences ``source[ia] -> target[ib]`` each pose of ``Ts`` ((B, 4, 4) or (4, 4), rounded to
+    float32) brings within ``max_dist``: the float32 inlier rule of ``include/pcr.h``, a NaN pose scores 0.
+
+    -> counts (B,) int32, or an int for a single pose; with ``return_mask`` also the masks (B, M) bool (or (M,))."""
+    src, dst = _pairs(source, target, ia, ib)
+    P, single = _poses12(Ts)
+    res = _capi.pose_score(lambda: _capi.get_context(device), src, dst, P, max_dist, want_mask=return_mask)
+    if not return_mask:
+        return int(res[0]) if single else res
+    return (int(res[0][0]), res[1][0]) if single else res
+
+
+def fit_rigid(src, dst):
+    """The least-squares rigid motion of paired points (Kabsch), float64 on the host: centroids, the 3 x 3 sum of
+    (q - c_q)(p - c_p)^T, ``np.linalg.svd`` and the determinant correction -> a (4, 4) pose that maps ``src`` onto ``dst``."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    if src.ndim != 2 or src.shape[1] != 3 or src.shape != dst.shape or len(src) < 3:
+        raise ValueError("src and dst must have one shape (N, 3), N >= 3")
+    cp, cq = src.mean(axis=0), dst.mean(axis=0)
+    H = (dst - cq).T @ (src - cp)
+    U, _, Vt = np.linalg.svd(H)
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U @ Vt) >= 0 else -1.0])
+    T = np.eye(4)
+    T[:3, :3] = U @ D @ Vt
+    T[:3, 3] = cq - T[:3, :3] @ cp
+    return T
+
+
+def _rmse(T, src, dst, mask):
+    """Root mean square residual of the masked rows under T, float64."""
+    if not mask.any():
+        return np.inf
+    p, q = src[mask].astype(np.float64), dst[mask].astype(np.float64)
+    r = p @ T[:3, :3].T + T[:3, 3] - q
+    return float(np.sqrt(np.mean(np.sum(r * r, axis=1))))
+
+
+def _round32(T):
+    with np.errstate(over="ignore"):
+        return T.astype(np.float32).astype(np.float64)
+
+
+def _proper(T):
+    """T with its rotation block replaced by the nearest rotation (float64, by SVD); the translation stays."""
+    U, _, Vt = np.linalg.svd(T[:3, :3])
+    D = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U @ Vt) >= 0 else -1.0])
+    out = T.copy()
+    out[:3, :3] = U @ D @ Vt
+    return out
+
+
+def refine_pose(score, src, dst, T, refine_rounds):
+    """The refinement of ``ransac_pose`` over a scoring function ``score(T) -> (count, mask)``: -> (T, count, mask, rmse)."""
+    T = _round32(T)
+    count, mask = score(T)
+    rmse = _rmse(T, src, dst, mask)
+    for _ in range(int(refine_rounds)):
+        if count < 3:
+            break
+        T2 = _round32(fit_rigid(src[mask], dst[mask]))
+        c2, m2 = score(T2)
+        r2 = _rmse(T2, src, dst, m2)
+        if not (c2 > count or (c2 == count and r2 < rmse)):
+            break
+        T, count, mask, rmse = T2, c2, m2, r2
+    return T, count, mask, rmse
+
+
+def ransac_pose(source, target, ia, ib, max_dist, n_hypotheses=100_000, seed=0, edge_similarity=0.9, min_edge=0.0,
+                refine_rounds=5, return_info=False, device=None):
+    """A pose from the correspondences ``source[ia] -> target[ib]`` by RANSAC.
+
+    ``n_hypotheses`` triples of correspondences are drawn by a counter-based generator (hypothesis h depends on ``seed``, h and
+    the number of correspondences only); a triple whose edge lengths differ by more than the factor ``edge_similarity``
+    between the two sides, or are shorter than ``min_edge``, is dropped; every other gets the rigid motion of its two
+    triangles and is scored against all the correspondences at ``max_dist``.  The best -- most inliers, then the smallest h --
+    is refined on the host up to ``refine_rounds`` times: Kabsch over the inliers, kept while it gains inliers or, at the same
+    count, lowers their RMSE.  There is no early termination.
+
+    -> ``T`` (4, 4) float64, identity when no hypothesis is valid; with ``return_info`` also a dict with ``inliers`` (M,)
+    bool, ``count``, ``fitness`` (count / M), ``rmse``, ``hypothesis`` (-1: none valid), ``n_valid`` and ``pose`` -- the 12
+    float32 values exactly as scored, to which the inliers, the count and the RMSE belong.  ``T`` is that pose with its rotation
+    made orthonormal in float64 (the nearest rotation; entries move by less than 1e-7): a rotation rounded to float32 is
+    orthonormal to 1e-8 only, and ``align`` composes its steps onto ``init_T`` without ever restoring that."""
+    src, dst = _pairs(source, target, ia, ib)
+    refine_rounds = int(refine_rounds)
+    if refine_rounds < 0:
+        raise ValueError("refine_rounds must be >= 0")
+    box = []
+
+    def ctx():
+        if not box:
+            box.append(_capi.get_context(device))
+        return box[0]
+    res = _capi.ransac_poses(ctx, src, dst, n_hypotheses, seed, max_dist, edge_similarity, min_edge)
+    m = len(src)
+    T, count, mask, rmse = np.eye(4), 0, np.zeros(m, bool), np.inf
+    pose = res["pose"]
+    if res["best"] >= 0:
+        def score(Tc):
+            c, k = _capi.pose_score(ctx, src, dst, _poses12(Tc)[0], max_dist, want_mask=True)
+            return int(c[0]), k[0]
+        T, count, mask, rmse = refine_pose(score, src, dst, _T_of(pose), refine_rounds)
+        pose = _poses12(T)[0][0]
+        T = _proper(T)
+    if not return_info:
+        return T
+    return T, {"pose": pose, "inliers": mask, "count": int(count), "fitness": count / m if m else 0.0, "rmse": rmse, "hypothesis": int(res["best"]),
+               "n_valid": int(res["n_valid"])}
+
+
+def register_global(source, target, feature_radius, max_dist, normals=None, mutual=True, ratio=None, device=None, **ransac):
+    """Global registration end to end: ``compute_fpfh`` on both clouds at ``feature_radius``, ``match_features`` (source
+    against target, ``mutual`` / ``ratio``), then ``ransac_pose`` with the remaining keywords.  ``normals``: ``None`` to
+    estimate them, or a pair ``(source_normals, target_normals)``."""
+    ns, nt = (None, None) if normals is None else normals
+    fs = compute_fpfh(source, ns, radius=feature_radius, device=device)
+    ft = compute_fpfh(target, nt, radius=feature_radius, device=device)
+    ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
+    return ransac_pose(source, target, ia, ib, max_dist, device=device, **ransac)
