@@ -499,6 +499,41 @@ PCR_API pcr_status pcr_target_spfh(pcr_target *t, float r, uint32_t *counts, int
 PCR_API pcr_status pcr_target_fpfh(pcr_target *t, float r, float *fpfh, int64_t *k_or_null);
 PCR_API pcr_status pcr_feature_match(pcr_context *ctx, const float *A, int64_t na, const float *B, int64_t nb, int dim,
                                      int64_t *idx, float *d2_first, float *d2_second);
+/* pcr_target_fpfh_rows: the descriptors of m chosen points only -- fpfh (m x 33) and, when not NULL, k (m); row s belongs to
+ *   point rows[s] (an index into the array the target was created from) and equals row rows[s] of pcr_target_fpfh bit for
+ *   bit: the SPFH pass still runs over the whole target (the neighbours' histograms are needed), the second pass and the
+ *   copy-back cover the m rows.  rows must be strictly ascending and inside [0, n), else PCR_ERR_INVALID with the outputs left
+ *   untouched; the other refusals are pcr_target_fpfh's.  m == 0 returns PCR_OK without a launch.                        */
+PCR_API pcr_status pcr_target_fpfh_rows(pcr_target *t, float r, const int64_t *rows, int64_t m, float *fpfh, int64_t *k_or_null);
+
+/* ---- ISS keypoints (no reference counterpart) ----------------------------------------------
+ * Intrinsic Shape Signatures (Zhong, ICCV workshops 2009) in the Open3D form, of a point target, over the float32 copy of the
+ * points; no normals are needed.
+ * Support set N_r(i): exactly what pcr_radius_query finds for the query p_i at r -- the float32 rule sqrtf(dist2_f32) <= r --
+ *   the point itself and its exact duplicates included.  k_i = |N_r(i)|.
+ * Scatter matrix of i at the salient radius, all in float64 from the widened float32 inputs, no contraction, every sum a plain
+ *   +: the members are taken in ascending order of the index's cell-sorted position (the order in which the radius search
+ *   walks them for ANY query); the anchor a is the first member; for every member d = q - a, s1 += d (3 sums),
+ *   s2 += d d^T (6 sums); m = s1 / k, C = s2 / k - m m^T, stored xx xy xz yy yz zz.  The anchor and the order are functions of
+ *   the member set, not of the query: two points with the same support set get bit-identical sums and eigenvalues.
+ * Eigenvalues l1 >= l2 >= l3 of C: cyclic Jacobi in float64 (the sweep rule of the normal estimation), the sorted diagonal.
+ * Saliency: i is salient iff k_i >= min_neighbors, l1 > 0, l2 < gamma21 * l1, l3 < gamma32 * l2 and l3 > 0 (products, no
+ *   division); s_i = l3 when salient, else 0.
+ * Keypoint at the non-maximum radius rn: s_i > 0, |N_rn(i)| >= min_neighbors (the point itself included), and for every other
+ *   j in N_rn(i): s_j < s_i, or s_j == s_i and orig_j > orig_i (orig = the index in the caller's array): a tie goes to the
+ *   smaller original index, a cluster of exact duplicates yields at most one keypoint.
+ * Defaults of the Python layer, as Open3D's: gamma21 = gamma32 = 0.975, min_neighbors = 5; radii of 6 x and 4 x the cloud's
+ *   resolution, resolution = 2 * mean(pcr_knn_mean_distance(t, 2)) in float64 (that call counts the point itself at distance
+ *   0), both rounded to float32.
+ * pcr_target_iss_saliency: eig (n x 3, l1 l2 l3), saliency (n) and k (n); pcr_target_iss_keypoints: is_keypoint (n bytes,
+ *   0 / 1) and, when not NULL, saliency (n); everything in the order of the array the target was created from.  No atomics:
+ *   the same call twice returns the same bits.
+ * PCR_ERR_INVALID: a voxel target; a radius negative, NaN or infinite; a gamma that is not finite and > 0;
+ *   min_neighbors < 1 -- the outputs are then left untouched.  An empty target returns PCR_OK without a launch.           */
+PCR_API pcr_status pcr_target_iss_saliency(pcr_target *t, float r, double gamma21, double gamma32, int min_neighbors,
+                                           double *eig /* n x 3 */, double *saliency, int64_t *k);
+PCR_API pcr_status pcr_target_iss_keypoints(pcr_target *t, float r_salient, float r_nonmax, double gamma21, double gamma32,
+                                            int min_neighbors, uint8_t *is_keypoint, double *saliency_or_null);
 
 /* ---- pose hypotheses from correspondences: RANSAC (no reference counterpart) ---------------
  * The last third of a global registration: from matches (pcr_feature_match) to a pose that an aligner can start from.

@@ -20,7 +20,8 @@ from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
 from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
 from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
-from .features import compute_fpfh, match_features, select_matches
+from .features import compute_fpfh, compute_fpfh_rows, match_features, select_matches
+from .keypoints import iss_keypoints
 from .global_registration import score_poses, fit_rigid, ransac_pose, register_global
 
 __all__ = [
@@ -29,5 +30,5 @@ __all__ = [
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
-    "score_poses", "fit_rigid", "ransac_pose", "register_global",
+    "score_poses", "fit_rigid", "ransac_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
 ]

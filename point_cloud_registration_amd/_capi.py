@@ -44,6 +44,7 @@ _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+_u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 _vp = C.c_void_p
 
 # name -> (restype, argtypes); also the list of symbols the library must export
@@ -94,6 +95,10 @@ PROTOTYPES = {
     "pcr_target_spfh": (C.c_int, [_vp, C.c_float, _u32p, _i64p]),
     "pcr_target_fpfh": (C.c_int, [_vp, C.c_float, _f32p, _vp]),
     "pcr_feature_match": (C.c_int, [_vp, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _i64p, _f32p, _f32p]),
+    "pcr_target_fpfh_rows": (C.c_int, [_vp, C.c_float, _i64p, C.c_int64, _f32p, _vp]),
+    # ISS keypoints (include/pcr.h, keypoints.py)
+    "pcr_target_iss_saliency": (C.c_int, [_vp, C.c_float, C.c_double, C.c_double, C.c_int, _f64p, _f64p, _i64p]),
+    "pcr_target_iss_keypoints": (C.c_int, [_vp, C.c_float, C.c_float, C.c_double, C.c_double, C.c_int, _u8p, _vp]),
     # pose hypotheses from correspondences and pose scoring (include/pcr.h, global_registration.py)
     "pcr_pose_score": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, _f32p, C.c_int64, C.c_float, _i32p, _vp]),
     "pcr_ransac_poses": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float,
@@ -282,6 +287,17 @@ def check_radius(r):
     if not (np.isfinite(r) and r >= 0):
         raise ValueError(f"radius must be finite and >= 0, got {r}")
     return r
+
+
+def check_iss(gamma_21, gamma_32, min_neighbors):
+    """The ISS parameters as (float, float, int): gammas finite and > 0, min_neighbors an integer >= 1 (the library's own
+    rule, csrc/keypoints.hip: iss_check), else ValueError before the GPU is touched."""
+    g21, g32 = float(gamma_21), float(gamma_32)
+    if not (np.isfinite(g21) and g21 > 0 and np.isfinite(g32) and g32 > 0):
+        raise ValueError("gamma_21 and gamma_32 must be finite and > 0")
+    if int(min_neighbors) != min_neighbors or not 1 <= int(min_neighbors) < 2 ** 31:
+        raise ValueError("min_neighbors must be an integer >= 1")
+    return g21, g32, int(min_neighbors)
 
 
 def check_k(k):
@@ -745,14 +761,45 @@ class Target:
         check(lib().pcr_target_spfh(self.handle, r, counts, k))
         return counts, k
 
-    def fpfh(self, r, want_k=False):
-        """-> (N, 33) float32 FPFH descriptors in the caller's order (and k (N,) int64 with ``want_k``)."""
+    def fpfh(self, r, want_k=False, rows=None):
+        """-> (N, 33) float32 FPFH descriptors in the caller's order (and k (N,) int64 with ``want_k``).  ``rows``: strictly
+        ascending int64 indices -> the (len(rows), 33) descriptors of those points only, equal to ``fpfh(r)[rows]``."""
         r = check_radius(r)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.ndim != 1:
+                raise ValueError("rows must be a vector")
+            out = np.zeros((len(rows), 33), np.float32)
+            k = np.zeros(len(rows), np.int64) if want_k else None
+            check(lib().pcr_target_fpfh_rows(self.handle, r, rows, len(rows), out, _ptr(k)))
+            return (out, k) if want_k else out
         n = self.size()
         out = np.zeros((n, 33), np.float32)
         k = np.zeros(n, np.int64) if want_k else None
         check(lib().pcr_target_fpfh(self.handle, r, out, _ptr(k)))
         return (out, k) if want_k else out
+
+    # -- ISS keypoints (include/pcr.h): a point target, no normals needed
+    def iss_saliency(self, r, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+        """-> (eig (N, 3) float64, l1 >= l2 >= l3; saliency (N,) float64; k (N,) int64) at the salient radius ``r``, in the
+        caller's order."""
+        r = check_radius(r)
+        g21, g32, mn = check_iss(gamma_21, gamma_32, min_neighbors)
+        n = self.size()
+        eig, sal, k = np.zeros((n, 3), np.float64), np.zeros(n, np.float64), np.zeros(n, np.int64)
+        check(lib().pcr_target_iss_saliency(self.handle, r, g21, g32, mn, eig, sal, k))
+        return eig, sal, k
+
+    def iss_keypoints(self, r_salient, r_nonmax, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, want_saliency=False):
+        """-> (N,) bool keypoint mask in the caller's order (and the saliency (N,) float64 with ``want_saliency``)."""
+        r_salient, r_nonmax = check_radius(r_salient), check_radius(r_nonmax)
+        g21, g32, mn = check_iss(gamma_21, gamma_32, min_neighbors)
+        n = self.size()
+        mask = np.zeros(n, np.uint8)
+        sal = np.zeros(n, np.float64) if want_saliency else None
+        check(lib().pcr_target_iss_keypoints(self.handle, r_salient, r_nonmax, g21, g32, mn, mask, _ptr(sal)))
+        mask = mask.astype(bool)
+        return (mask, sal) if want_saliency else mask
 
     def close(self):
         if getattr(self, "handle", None) and not _shutdown and not getattr(self, "_borrowed", False):

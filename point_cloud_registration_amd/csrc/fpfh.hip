@@ -3,6 +3,7 @@
 //
 //   pcr_target_spfh     k_spfh<1>                       counts and k in the caller's order (the seam of the exact test)
 //   pcr_target_fpfh     k_spfh<0>, k_fpfh               float32 (n, 33) in the caller's order
+//   pcr_target_fpfh_rows  k_spfh<0>, k_fpfh_row_index, k_fpfh_rows   float32 (m, 33): the descriptors of m chosen rows
 //   pcr_feature_match   k_feature_nn<D>, k_feature_merge
 //
 // k_spfh / k_fpfh: one lane = one point in CELL-SORTED order, so the lanes of a wave are spatial neighbours; both walk the
@@ -135,22 +136,9 @@ __global__ void __launch_bounds__(FPFH_BLOCK) k_spfh(Geom<float> g, const PtF *p
     kk[o] = S.k;
 }
 
-__global__ void __launch_bounds__(FPFH_BLOCK) k_fpfh(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, float r,
-                                                     const uint32_t *counts, const uint32_t *kk, float *out, int64_t *k_out) {
-    const int64_t i = (int64_t)blockIdx.x * FPFH_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const PtF me = pts[i];
-    FpfhSink S;
-    S.r = r; S.b2 = rad_bound2(r); S.mx = me.x; S.my = me.y; S.mz = me.z; S.pts = pts; S.counts = counts; S.kk = kk;
-#pragma unroll
-    for (int b = 0; b < FPFH_BINS; ++b) S.acc[b] = 0.0;
-    const float big = RealTraits<float>::inf();
-    const bool finite = me.x > -big && me.x < big && me.y > -big && me.y < big && me.z > -big && me.z < big;
-    if (finite) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
-    const uint32_t ki = kk[i];
+// the end of k_fpfh and k_fpfh_rows: the lane's own SPFH (counts c, k = ki) plus its normalised sums, one float32 row
+__device__ __forceinline__ void fpfh_finish(const FpfhSink &S, const uint32_t *c, uint32_t ki, float *row) {
     const double kd = (double)(ki ? ki : 1u);
-    const uint32_t *c = counts + (size_t)i * FPFH_BINS;
-    float *row = out + (size_t)pt_orig(me) * FPFH_BINS;
 #pragma unroll
     for (int blk = 0; blk < 3; ++blk) {
         double sum = 0.0;
@@ -163,7 +151,54 @@ __global__ void __launch_bounds__(FPFH_BLOCK) k_fpfh(Geom<float> g, const PtF *p
             row[11 * blk + b] = (float)(own + nb);
         }
     }
+}
+
+// the walk of k_fpfh and k_fpfh_rows for the point at cell-sorted index i
+__device__ __forceinline__ void fpfh_walk(const Geom<float> &g, const PtF *pts, const uint32_t *cs, float r, const uint32_t *counts,
+                                          const uint32_t *kk, const PtF &me, FpfhSink &S) {
+    S.r = r; S.b2 = rad_bound2(r); S.mx = me.x; S.my = me.y; S.mz = me.z; S.pts = pts; S.counts = counts; S.kk = kk;
+#pragma unroll
+    for (int b = 0; b < FPFH_BINS; ++b) S.acc[b] = 0.0;
+    const float big = RealTraits<float>::inf();
+    const bool finite = me.x > -big && me.x < big && me.y > -big && me.y < big && me.z > -big && me.z < big;
+    if (finite) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
+}
+
+__global__ void __launch_bounds__(FPFH_BLOCK) k_fpfh(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, float r,
+                                                     const uint32_t *counts, const uint32_t *kk, float *out, int64_t *k_out) {
+    const int64_t i = (int64_t)blockIdx.x * FPFH_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const PtF me = pts[i];
+    FpfhSink S;
+    fpfh_walk(g, pts, cs, r, counts, kk, me, S);
+    const uint32_t ki = kk[i];
+    fpfh_finish(S, counts + (size_t)i * FPFH_BINS, ki, out + (size_t)pt_orig(me) * FPFH_BINS);
     if (k_out) k_out[pt_orig(me)] = (int64_t)ki;
+}
+
+// descriptors at chosen rows.  slot_of[original index] = the row's place in the caller's list, or -1: every selected point
+// stores its cell-sorted index at its slot (the slots are unique: a plain store)
+__global__ void __launch_bounds__(256) k_fpfh_row_index(const PtF *pts, int64_t n, const int32_t *slot_of, uint32_t *sel) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t s = slot_of[pt_orig(pts[i])];
+    if (s >= 0) sel[s] = (uint32_t)i;
+}
+
+// one lane = one selected row, in the caller's (ascending) order; the walk, its order and the finish are k_fpfh's, so row
+// `slot` equals row rows[slot] of pcr_target_fpfh bit for bit
+__global__ void __launch_bounds__(FPFH_BLOCK) k_fpfh_rows(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t m, float r,
+                                                          const uint32_t *counts, const uint32_t *kk, const uint32_t *sel, float *out,
+                                                          int64_t *k_out) {
+    const int64_t slot = (int64_t)blockIdx.x * FPFH_BLOCK + threadIdx.x;
+    if (slot >= m) return;
+    const size_t i = sel[slot];
+    const PtF me = pts[i];
+    FpfhSink S;
+    fpfh_walk(g, pts, cs, r, counts, kk, me, S);
+    const uint32_t ki = kk[i];
+    fpfh_finish(S, counts + i * FPFH_BINS, ki, out + (size_t)slot * FPFH_BINS);
+    if (k_out) k_out[slot] = (int64_t)ki;
 }
 
 // ---- feature matching -----------------------------------------------------------------------------------------------------
@@ -336,6 +371,60 @@ extern "C" pcr_status pcr_target_fpfh(pcr_target *t, float r, float *fpfh, int64
     if (k_or_null) HIP_TRY(hipMemcpyAsync(k_or_null, d_kout.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ev.on) fprintf(stderr, "pcr_fpfh_times points %lld spfh_ms %.4f fpfh_ms %.4f\n", (long long)t->n, ev.ms(0), ev.ms(1));
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_fpfh_rows(pcr_target *t, float r, const int64_t *rows, int64_t m, float *fpfh, int64_t *k_or_null) {
+    PCR_REQUIRE(t, "NULL argument");
+    PCR_TRY(fpfh_check(t, r, "pcr_target_fpfh_rows"));
+    PCR_REQUIRE(m >= 0, "negative row count");
+    PCR_REQUIRE(rows || m == 0, "NULL argument");
+    for (int64_t s = 0; s < m; ++s) {
+        if (rows[s] < 0 || rows[s] >= t->n || (s > 0 && rows[s] <= rows[s - 1])) {
+            pcr_set_error("invalid argument: pcr_target_fpfh_rows needs strictly ascending rows inside [0, n)");
+            return PCR_ERR_INVALID;
+        }
+    }
+    if (m == 0) return PCR_OK;
+    PCR_REQUIRE(fpfh, "NULL argument");
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    const size_t n = (size_t)t->n;
+    std::vector<int32_t> slot_of(n, -1);
+    for (int64_t s = 0; s < m; ++s) slot_of[(size_t)rows[s]] = (int32_t)s;
+    DevBuf<uint32_t> d_counts, d_k, d_sel;
+    DevBuf<int32_t> d_slot;
+    DevBuf<float> d_out;
+    DevBuf<int64_t> d_kout;
+    HIP_TRY(d_counts.alloc(n * FPFH_BINS));
+    HIP_TRY(d_k.alloc(n));
+    HIP_TRY(d_slot.alloc(n));
+    HIP_TRY(d_sel.alloc((size_t)m));
+    HIP_TRY(d_out.alloc((size_t)m * FPFH_BINS));
+    if (k_or_null) HIP_TRY(d_kout.alloc((size_t)m));
+    HIP_TRY(hipMemcpyAsync(d_slot.p, slot_of.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d_sel.p, 0, 4 * (size_t)m, ctx->stream));    // (every slot is stored below; never an index out of range)
+    FpEvents ev;
+    if (fpfh_times()) HIP_TRY(ev.init());
+    ev.mark(0, ctx->stream);
+    hipLaunchKernelGGL(k_spfh<0>, fpfh_grid(t->n), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const PtN *)t->pn,
+                       (const uint32_t *)t->cell_start, t->n, r, d_counts.p, d_k.p);
+    HIP_TRY(hipGetLastError());
+    ev.mark(1, ctx->stream);
+    hipLaunchKernelGGL(k_fpfh_row_index, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, ctx->stream, (const PtF *)t->pts, t->n,
+                       (const int32_t *)d_slot.p, d_sel.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_fpfh_rows, fpfh_grid(m), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const uint32_t *)t->cell_start, m, r,
+                       (const uint32_t *)d_counts.p, (const uint32_t *)d_k.p, (const uint32_t *)d_sel.p, d_out.p,
+                       k_or_null ? d_kout.p : (int64_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+    ev.mark(2, ctx->stream);
+    HIP_TRY(hipMemcpyAsync(fpfh, d_out.p, 4 * (size_t)m * FPFH_BINS, hipMemcpyDeviceToHost, ctx->stream));
+    if (k_or_null) HIP_TRY(hipMemcpyAsync(k_or_null, d_kout.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ev.on)
+        fprintf(stderr, "pcr_fpfh_times points %lld rows %lld spfh_ms %.4f fpfh_rows_ms %.4f\n", (long long)t->n, (long long)m, ev.ms(0), ev.ms(1));
     return PCR_OK;
 }
 

@@ -24,7 +24,23 @@ def compute_fpfh(points, normals=None, radius=None, k_normals=15, device=None):
     """FPFH descriptors (N, 33) float32 of ``points`` at ``radius``: for every point the histogram of its own pair features
     plus the distance-weighted, normalised histograms of its neighbours, three blocks of 11 bins that each sum to 200 (a point
     with no neighbour inside the radius gets a zero row).  ``normals`` (N, 3), or ``None`` to estimate them from the
-    ``k_normals`` nearest neighbours as ``estimate_normals`` does."""
+    ``k_normals`` nearest neighbours as ``estimate_normals`` does.  Descriptors at some rows only: ``compute_fpfh_rows``."""
+    return _fpfh(points, normals, radius, k_normals, device, None)
+
+
+def compute_fpfh_rows(points, rows, normals=None, radius=None, k_normals=15, device=None):
+    """``compute_fpfh(points, normals, radius, ...)[rows]``, bit for bit, without computing or copying back the other rows'
+    second pass: ``rows`` are integer row indices into ``points`` in any order, with no repeats; -> (len(rows), 33) float32 in
+    the order given.  (The first pass still covers the whole cloud: the neighbours' histograms are needed.)"""
+    rows = np.asarray(rows)
+    if rows.ndim != 1:
+        raise ValueError("rows must be a vector of row indices")
+    if len(rows) and not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError("rows must be integer row indices")
+    return _fpfh(points, normals, radius, k_normals, device, rows.astype(np.int64))
+
+
+def _fpfh(points, normals, radius, k_normals, device, rows):
     points = _rows3(points, "points")
     if radius is None:
         raise ValueError("radius is required")
@@ -35,7 +51,15 @@ def compute_fpfh(points, normals=None, radius=None, k_normals=15, device=None):
             raise ValueError("normals must have the shape of points")
     else:
         k_normals = _capi.check_k(k_normals)
-    if len(points) == 0:
+    order = None
+    if rows is not None:
+        if len(rows) and (rows.min() < 0 or rows.max() >= len(points)):
+            raise ValueError("rows point outside points")
+        order = np.argsort(rows, kind="stable")
+        rows = np.ascontiguousarray(rows[order])
+        if np.any(rows[1:] == rows[:-1]):
+            raise ValueError("rows must not repeat")
+    if len(points) == 0 or (rows is not None and len(rows) == 0):
         return np.zeros((0, 33), np.float32)
     with np.errstate(over="ignore"):
         xyz = np.ascontiguousarray(points, dtype=np.float32)
@@ -44,7 +68,11 @@ def compute_fpfh(points, normals=None, radius=None, k_normals=15, device=None):
     target = _capi.Target.points(_capi.get_context(device), xyz, normals)
     if normals is None:
         target.estimate_normals(k_normals, want=False)
-    return target.fpfh(radius)
+    if rows is None:
+        return target.fpfh(radius)
+    out = np.empty((len(rows), 33), np.float32)
+    out[order] = target.fpfh(radius, rows=rows)                          # (sorted on the host, un-sorted here)
+    return out
 
 
 def select_matches(idx_ab, d2_first, d2_second, idx_ba=None, mutual=True, ratio=None):

@@ -3,7 +3,8 @@
 ``include/pcr.h``.  The reference has no counterpart.
 
 ``ransac_pose`` draws pose hypotheses from triples of matches, scores every one of them against every match on the GPU and
-refines the winner over its inliers; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose``.  The
+refines the winner over its inliers; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose`` --
+over every point, or over keypoints (``keypoints.py``) with descriptors at those rows only.  The
 result is an ``init_T`` for ``align`` of any of the local aligners.  Everything is computed over the **float32 copy** of the
 points, and the same call twice returns the same bits.
 """
@@ -11,7 +12,8 @@ points, and the same call twice returns the same bits.
 import numpy as np
 
 from . import _capi
-from .features import compute_fpfh, match_features
+from .features import compute_fpfh, compute_fpfh_rows, match_features
+from .keypoints import iss_keypoints
 
 
 def _pairs(source, target, ia, ib):
@@ -163,12 +165,58 @@ def ransac_pose(source, target, ia, ib, max_dist, n_hypotheses=100_000, seed=0, 
                "n_valid": int(res["n_valid"])}
 
 
-def register_global(source, target, feature_radius, max_dist, normals=None, mutual=True, ratio=None, device=None, **ransac):
+def _keypoint_rows(rows, n, name):
+    rows = np.asarray(rows)
+    if rows.ndim != 1 or (len(rows) and not np.issubdtype(rows.dtype, np.integer)):
+        raise ValueError(f"keypoints: the {name} rows must be a vector of integer row indices")
+    rows = rows.astype(np.int64)
+    if len(rows) and (rows.min() < 0 or rows.max() >= n):
+        raise ValueError(f"keypoints: the {name} rows point outside {name}")
+    if len(np.unique(rows)) != len(rows):
+        raise ValueError(f"keypoints: the {name} rows must not repeat")
+    return rows
+
+
+def register_global(source, target, feature_radius, max_dist, normals=None, mutual=True, ratio=None, device=None, keypoints=None,
+                    keypoint_args=None, **ransac):
     """Global registration end to end: ``compute_fpfh`` on both clouds at ``feature_radius``, ``match_features`` (source
     against target, ``mutual`` / ``ratio``), then ``ransac_pose`` with the remaining keywords.  ``normals``: ``None`` to
-    estimate them, or a pair ``(source_normals, target_normals)``."""
+    estimate them, or a pair ``(source_normals, target_normals)``.
+
+    ``keypoints``: ``None`` describes and matches every point; ``"iss"`` detects ISS keypoints on both clouds
+    (``iss_keypoints(cloud, **keypoint_args)``); a pair ``(source_rows, target_rows)`` uses the caller's own.  Descriptors are
+    then computed at those rows only (``compute_fpfh_rows``), a few thousand rows are matched instead of every point, and the
+    matches are mapped back to rows of ``source`` and ``target`` before ``ransac_pose``.  Fewer than 3 keypoints on either side
+    give no matches: ``ransac_pose``'s no-match result."""
     ns, nt = (None, None) if normals is None else normals
-    fs = compute_fpfh(source, ns, radius=feature_radius, device=device)
-    ft = compute_fpfh(target, nt, radius=feature_radius, device=device)
-    ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
+    if keypoints is None:
+        if keypoint_args is not None:
+            raise ValueError("keypoint_args needs keypoints")
+        fs = compute_fpfh(source, ns, radius=feature_radius, device=device)
+        ft = compute_fpfh(target, nt, radius=feature_radius, device=device)
+        ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
+        return ransac_pose(source, target, ia, ib, max_dist, device=device, **ransac)
+    if isinstance(keypoints, str):
+        if keypoints != "iss":
+            raise ValueError('keypoints must be None, "iss" or a pair (source_rows, target_rows)')
+        args = dict(keypoint_args or {})
+        if "return_saliency" in args or "device" in args:
+            raise ValueError("keypoint_args takes the detector's parameters only")
+        ks = iss_keypoints(source, device=device, **args)
+        kt = iss_keypoints(target, device=device, **args)
+    else:
+        if keypoint_args is not None:
+            raise ValueError('keypoint_args needs keypoints="iss"')
+        try:
+            ks, kt = keypoints
+        except (TypeError, ValueError):
+            raise ValueError('keypoints must be None, "iss" or a pair (source_rows, target_rows)') from None
+        ks, kt = _keypoint_rows(ks, len(np.asarray(source)), "source"), _keypoint_rows(kt, len(np.asarray(target)), "target")
+    if len(ks) < 3 or len(kt) < 3:
+        ia = ib = np.zeros(0, np.int64)
+    else:
+        fs = compute_fpfh_rows(source, ks, ns, radius=feature_radius, device=device)
+        ft = compute_fpfh_rows(target, kt, nt, radius=feature_radius, device=device)
+        ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
+        ia, ib = ks[ia], kt[ib]
     return ransac_pose(source, target, ia, ib, max_dist, device=device, **ransac)
