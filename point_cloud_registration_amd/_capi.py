@@ -281,6 +281,21 @@ def check(status):
     raise PcrError(f"libpcr_hip status {status}: {msg}")
 
 
+def cloud_f32(a, name, finite=True):
+    """``a`` as a C-contiguous float32 (N, 3) array, what every kernel reads, else ValueError (checked before the GPU is
+    touched): the shape and, with ``finite``, every value finite -- as given and still as float32."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{name} must have shape (N, 3)")
+    if finite and not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be finite")
+    with np.errstate(over="ignore"):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if finite and not np.all(np.isfinite(a)):
+        raise ValueError(f"{name} must be finite as float32")
+    return a
+
+
 def check_radius(r):
     """A search radius as a float: finite and >= 0, else ValueError (checked before the GPU is touched)."""
     r = float(r)
@@ -1026,11 +1041,7 @@ def check_pairs(src, dst):
         raise ValueError("src and dst must have one shape (M, 3)")
     if len(src) > RANSAC_M_MAX:
         raise ValueError("more than 2^24 correspondences")
-    with np.errstate(over="ignore"):
-        src, dst = np.ascontiguousarray(src, dtype=np.float32), np.ascontiguousarray(dst, dtype=np.float32)
-    if not (np.all(np.isfinite(src)) and np.all(np.isfinite(dst))):
-        raise ValueError("src and dst must be finite as float32")
-    return src, dst
+    return cloud_f32(src, "src and dst"), cloud_f32(dst, "src and dst")
 
 
 def check_distance(d, name):

@@ -14,7 +14,7 @@
 #include <chrono>
 #include <vector>
 
-#include "pcr_internal.h"
+#include "host_util.h"
 
 #define CS_BLOCK 256
 #define CS_MAX_D 12          // M = D (D + 1) / 2 + D + 1 <= 91
@@ -457,7 +457,7 @@ extern "C" pcr_status pcr_coreset(pcr_context *ctx, const double *P, int m, int6
     }
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
-    static const bool stats = getenv("PCR_CORESET_STATS") && atoi(getenv("PCR_CORESET_STATS"));
+    static const bool stats = env_flag("PCR_CORESET_STATS");
     const auto t_all = std::chrono::steady_clock::now();
     double ms_up = 0, ms_elim = 0, ms_down = 0;
     int levels = 0;
@@ -504,7 +504,7 @@ pcr_status pcr_terms_weighted_sum(pcr_context *ctx, const double *d_P, int64_t s
 
 pcr_status pcr_terms_coreset(pcr_context *ctx, const double *d_P, int64_t stride, const int64_t *d_col_idx, int64_t n_in, int k,
                              int64_t n_target, int64_t *idx_out, double *w_out, int64_t *n_out) {
-    static const bool stats = getenv("PCR_CORESET_STATS") && atoi(getenv("PCR_CORESET_STATS"));
+    static const bool stats = env_flag("PCR_CORESET_STATS");
     const auto t_all = std::chrono::steady_clock::now();
     double ms_elim = 0, ms_down = 0;
     int levels = 0;

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "gicp_weight.h"
+#include "host_util.h"
 
 // W points per lane in flight, the phases of reduce_stream (pass_device.h):
 //   phase A  index, coordinates and scan covariance of all W points.  A point past the end reads the lane's first point.
@@ -99,8 +100,6 @@ static pcr_status dist_launch(pcr_context *ctx, const char *range_name, void (*r
 }
 
 // ---- covariance arguments ------------------------------------------------------------------------------------------------
-static dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 static pcr_status check_cov_mode(int mode, double eps) {
     PCR_REQUIRE(mode == PCR_COV_PLANE || mode == PCR_COV_RAW, "mode must be PCR_COV_PLANE or PCR_COV_RAW");
     PCR_REQUIRE(mode == PCR_COV_RAW || (eps > 0.0 && eps <= 1.0), "eps must be in (0, 1]");

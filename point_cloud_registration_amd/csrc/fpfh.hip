@@ -26,9 +26,6 @@
 // so k_feature_merge's merge of the per-split top-2 is exact and the result does not depend on the split.  D = 33 is its own
 // instantiation; every other width runs the D = 64 one over rows padded with zeros ((0 - 0)^2 added to a float32 sum changes
 // no bit).
-#include <float.h>
-#include <stdlib.h>
-
 #include "radius_device.h"
 
 #define FPFH_BINS 33
@@ -127,9 +124,7 @@ __global__ void __launch_bounds__(FPFH_BLOCK) k_spfh(Geom<float> g, const PtF *p
     S.r = r; S.b2 = rad_bound2(r); S.me = pn[i]; S.pn = pn; S.cnt = s_cnt + threadIdx.x; S.k = 0;
 #pragma unroll
     for (int b = 0; b < FPFH_BINS; ++b) S.cnt[b * FPFH_BLOCK] = 0u;
-    const float big = RealTraits<float>::inf();
-    const bool finite = S.me.x > -big && S.me.x < big && S.me.y > -big && S.me.y < big && S.me.z > -big && S.me.z < big;
-    if (finite) rad_ball_walk(g, pts, cs, S.me.x, S.me.y, S.me.z, r, S);
+    if (rad_finite(S.me.x, S.me.y, S.me.z)) rad_ball_walk(g, pts, cs, S.me.x, S.me.y, S.me.z, r, S);
     const int64_t o = ORIG ? (int64_t)S.me.orig : i;
 #pragma unroll
     for (int b = 0; b < FPFH_BINS; ++b) counts[o * FPFH_BINS + b] = S.cnt[b * FPFH_BLOCK];
@@ -159,9 +154,7 @@ __device__ __forceinline__ void fpfh_walk(const Geom<float> &g, const PtF *pts, 
     S.r = r; S.b2 = rad_bound2(r); S.mx = me.x; S.my = me.y; S.mz = me.z; S.pts = pts; S.counts = counts; S.kk = kk;
 #pragma unroll
     for (int b = 0; b < FPFH_BINS; ++b) S.acc[b] = 0.0;
-    const float big = RealTraits<float>::inf();
-    const bool finite = me.x > -big && me.x < big && me.y > -big && me.y < big && me.z > -big && me.z < big;
-    if (finite) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
+    if (rad_finite(me.x, me.y, me.z)) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
 }
 
 __global__ void __launch_bounds__(FPFH_BLOCK) k_fpfh(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, float r,
@@ -286,36 +279,24 @@ __global__ void __launch_bounds__(256) k_feature_merge(const uint64_t *__restric
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-// PCR_FPFH_TIMES=1 (developer, tools/fpfh_time.py): the calls bracket their kernels with events and report the milliseconds on
-// stderr
-static bool fpfh_times() {
-    static const bool on = getenv("PCR_FPFH_TIMES") && atoi(getenv("PCR_FPFH_TIMES")) != 0;
-    return on;
-}
+// PCR_FPFH_TIMES=1 (developer, tools/fpfh_time.py, tools/iss_time.py): the calls bracket their kernels with events (StageTimes)
+// and report the milliseconds on stderr
 
-struct FpEvents {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool on = false;
-    ~FpEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t init() {
-        on = true;
-        for (hipEvent_t &e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) return s; }
-        return hipSuccess;
-    }
-    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
-    float ms(int i) { float m = 0; (void)hipEventElapsedTime(&m, ev[i], ev[i + 1]); return m; }
-};
-
-// a point target (else PCR_ERR_INVALID), a finite radius >= 0 (as radius_check of radius.hip), normals (else PCR_ERR_NO_TARGET;
-// an empty target has nothing that could lack one)
+// a point target (else PCR_ERR_INVALID), a finite radius >= 0, normals (else PCR_ERR_NO_TARGET; an empty target has nothing
+// that could lack one)
 static pcr_status fpfh_check(const pcr_target *t, float r, const char *who) {
-    if (t->is_voxel) { pcr_set_error("invalid argument: %s needs a point target", who); return PCR_ERR_INVALID; }
-    if (!(r >= 0 && r <= FLT_MAX)) { pcr_set_error("invalid argument: %s needs a finite radius >= 0", who); return PCR_ERR_INVALID; }
+    PCR_TRY(check_point_target(t, who));
+    PCR_TRY(check_radius<float>(r, who));
     if (t->n > 0 && !t->pn) { pcr_set_error("%s: the target has no per-point normals", who); return PCR_ERR_NO_TARGET; }
     return PCR_OK;
 }
 
-static dim3 fpfh_grid(int64_t n) { return dim3((unsigned)((n + FPFH_BLOCK - 1) / FPFH_BLOCK)); }
+// the first pass over the whole target: counts [n][33] and k [n], at the cell-sorted index (ORIG = 0) or the original one
+template <int ORIG>
+static void spfh_launch(pcr_target *t, float r, uint32_t *d_counts, uint32_t *d_k) {
+    hipLaunchKernelGGL(k_spfh<ORIG>, grid_for(t->n, FPFH_BLOCK), dim3(FPFH_BLOCK), 0, t->ctx->stream, t->gf, (const PtF *)t->pts, (const PtN *)t->pn,
+                       (const uint32_t *)t->cell_start, t->n, r, d_counts, d_k);
+}
 
 extern "C" pcr_status pcr_target_spfh(pcr_target *t, float r, uint32_t *counts, int64_t *k) {
     PCR_REQUIRE(t, "NULL argument");
@@ -329,14 +310,64 @@ extern "C" pcr_status pcr_target_spfh(pcr_target *t, float r, uint32_t *counts, 
     DevBuf<uint32_t> d_counts, d_k;
     HIP_TRY(d_counts.alloc(n * FPFH_BINS));
     HIP_TRY(d_k.alloc(n));
-    hipLaunchKernelGGL(k_spfh<1>, fpfh_grid(t->n), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const PtN *)t->pn,
-                       (const uint32_t *)t->cell_start, t->n, r, d_counts.p, d_k.p);
+    spfh_launch<1>(t, r, d_counts.p, d_k.p);
     HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> k32(n);
     HIP_TRY(hipMemcpyAsync(counts, d_counts.p, 4 * n * FPFH_BINS, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(k32.data(), d_k.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+    return download_u32_as_i64(ctx, d_k.p, n, k);
+}
+
+// the descriptors of every point (rows == NULL: m = n, in the caller's order) or of the m > 0 checked rows, in their order
+static pcr_status fpfh_run(pcr_target *t, float r, const int64_t *rows, int64_t m, float *fpfh, int64_t *k_or_null) {
+    PCR_REQUIRE(fpfh, "NULL argument");
+    pcr_context *ctx = t->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CtxScope scope(ctx);
+    const size_t n = (size_t)t->n;
+    DevBuf<uint32_t> d_counts, d_k, d_sel;
+    DevBuf<int32_t> d_slot;
+    DevBuf<float> d_out;
+    DevBuf<int64_t> d_kout;
+    HIP_TRY(d_counts.alloc(n * FPFH_BINS));
+    HIP_TRY(d_k.alloc(n));
+    std::vector<int32_t> slot_of;                  // slot_of[original index] = the row's place in the caller's list, or -1
+    if (rows) {
+        slot_of.assign(n, -1);
+        for (int64_t s = 0; s < m; ++s) slot_of[(size_t)rows[s]] = (int32_t)s;
+        HIP_TRY(d_slot.alloc(n));
+        HIP_TRY(d_sel.alloc((size_t)m));
+        HIP_TRY(hipMemcpyAsync(d_slot.p, slot_of.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemsetAsync(d_sel.p, 0, 4 * (size_t)m, ctx->stream));    // (every slot is stored below; never an index out of range)
+    }
+    HIP_TRY(d_out.alloc((size_t)m * FPFH_BINS));
+    if (k_or_null) HIP_TRY(d_kout.alloc((size_t)m));
+    int64_t *d_kp = k_or_null ? d_kout.p : (int64_t *)nullptr;
+    static const bool times = env_flag("PCR_FPFH_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
+    ev.mark(0, ctx->stream);
+    spfh_launch<0>(t, r, d_counts.p, d_k.p);
+    HIP_TRY(hipGetLastError());
+    ev.mark(1, ctx->stream);
+    if (rows) {
+        hipLaunchKernelGGL(k_fpfh_row_index, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const PtF *)t->pts, t->n, (const int32_t *)d_slot.p,
+                           d_sel.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_fpfh_rows, grid_for(m, FPFH_BLOCK), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts,
+                           (const uint32_t *)t->cell_start, m, r, (const uint32_t *)d_counts.p, (const uint32_t *)d_k.p, (const uint32_t *)d_sel.p,
+                           d_out.p, d_kp);
+    } else {
+        hipLaunchKernelGGL(k_fpfh, grid_for(t->n, FPFH_BLOCK), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts,
+                           (const uint32_t *)t->cell_start, t->n, r, (const uint32_t *)d_counts.p, (const uint32_t *)d_k.p, d_out.p, d_kp);
+    }
+    HIP_TRY(hipGetLastError());
+    ev.mark(2, ctx->stream);
+    HIP_TRY(hipMemcpyAsync(fpfh, d_out.p, 4 * (size_t)m * FPFH_BINS, hipMemcpyDeviceToHost, ctx->stream));
+    if (k_or_null) HIP_TRY(hipMemcpyAsync(k_or_null, d_kout.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i) k[i] = (int64_t)k32[i];
+    if (ev.on && rows)
+        fprintf(stderr, "pcr_fpfh_times points %lld rows %lld spfh_ms %.4f fpfh_rows_ms %.4f\n", (long long)t->n, (long long)m, ev.ms(0), ev.ms(1));
+    else if (ev.on)
+        fprintf(stderr, "pcr_fpfh_times points %lld spfh_ms %.4f fpfh_ms %.4f\n", (long long)t->n, ev.ms(0), ev.ms(1));
     return PCR_OK;
 }
 
@@ -344,34 +375,7 @@ extern "C" pcr_status pcr_target_fpfh(pcr_target *t, float r, float *fpfh, int64
     PCR_REQUIRE(t, "NULL argument");
     PCR_TRY(fpfh_check(t, r, "pcr_target_fpfh"));
     if (t->n == 0) return PCR_OK;
-    PCR_REQUIRE(fpfh, "NULL argument");
-    pcr_context *ctx = t->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    const size_t n = (size_t)t->n;
-    DevBuf<uint32_t> d_counts, d_k;
-    DevBuf<float> d_out;
-    DevBuf<int64_t> d_kout;
-    HIP_TRY(d_counts.alloc(n * FPFH_BINS));
-    HIP_TRY(d_k.alloc(n));
-    HIP_TRY(d_out.alloc(n * FPFH_BINS));
-    if (k_or_null) HIP_TRY(d_kout.alloc(n));
-    FpEvents ev;
-    if (fpfh_times()) HIP_TRY(ev.init());
-    ev.mark(0, ctx->stream);
-    hipLaunchKernelGGL(k_spfh<0>, fpfh_grid(t->n), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const PtN *)t->pn,
-                       (const uint32_t *)t->cell_start, t->n, r, d_counts.p, d_k.p);
-    HIP_TRY(hipGetLastError());
-    ev.mark(1, ctx->stream);
-    hipLaunchKernelGGL(k_fpfh, fpfh_grid(t->n), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const uint32_t *)t->cell_start, t->n, r,
-                       (const uint32_t *)d_counts.p, (const uint32_t *)d_k.p, d_out.p, k_or_null ? d_kout.p : (int64_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-    ev.mark(2, ctx->stream);
-    HIP_TRY(hipMemcpyAsync(fpfh, d_out.p, 4 * n * FPFH_BINS, hipMemcpyDeviceToHost, ctx->stream));
-    if (k_or_null) HIP_TRY(hipMemcpyAsync(k_or_null, d_kout.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ev.on) fprintf(stderr, "pcr_fpfh_times points %lld spfh_ms %.4f fpfh_ms %.4f\n", (long long)t->n, ev.ms(0), ev.ms(1));
-    return PCR_OK;
+    return fpfh_run(t, r, nullptr, t->n, fpfh, k_or_null);
 }
 
 extern "C" pcr_status pcr_target_fpfh_rows(pcr_target *t, float r, const int64_t *rows, int64_t m, float *fpfh, int64_t *k_or_null) {
@@ -386,46 +390,7 @@ extern "C" pcr_status pcr_target_fpfh_rows(pcr_target *t, float r, const int64_t
         }
     }
     if (m == 0) return PCR_OK;
-    PCR_REQUIRE(fpfh, "NULL argument");
-    pcr_context *ctx = t->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    const size_t n = (size_t)t->n;
-    std::vector<int32_t> slot_of(n, -1);
-    for (int64_t s = 0; s < m; ++s) slot_of[(size_t)rows[s]] = (int32_t)s;
-    DevBuf<uint32_t> d_counts, d_k, d_sel;
-    DevBuf<int32_t> d_slot;
-    DevBuf<float> d_out;
-    DevBuf<int64_t> d_kout;
-    HIP_TRY(d_counts.alloc(n * FPFH_BINS));
-    HIP_TRY(d_k.alloc(n));
-    HIP_TRY(d_slot.alloc(n));
-    HIP_TRY(d_sel.alloc((size_t)m));
-    HIP_TRY(d_out.alloc((size_t)m * FPFH_BINS));
-    if (k_or_null) HIP_TRY(d_kout.alloc((size_t)m));
-    HIP_TRY(hipMemcpyAsync(d_slot.p, slot_of.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(d_sel.p, 0, 4 * (size_t)m, ctx->stream));    // (every slot is stored below; never an index out of range)
-    FpEvents ev;
-    if (fpfh_times()) HIP_TRY(ev.init());
-    ev.mark(0, ctx->stream);
-    hipLaunchKernelGGL(k_spfh<0>, fpfh_grid(t->n), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const PtN *)t->pn,
-                       (const uint32_t *)t->cell_start, t->n, r, d_counts.p, d_k.p);
-    HIP_TRY(hipGetLastError());
-    ev.mark(1, ctx->stream);
-    hipLaunchKernelGGL(k_fpfh_row_index, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, ctx->stream, (const PtF *)t->pts, t->n,
-                       (const int32_t *)d_slot.p, d_sel.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fpfh_rows, fpfh_grid(m), dim3(FPFH_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const uint32_t *)t->cell_start, m, r,
-                       (const uint32_t *)d_counts.p, (const uint32_t *)d_k.p, (const uint32_t *)d_sel.p, d_out.p,
-                       k_or_null ? d_kout.p : (int64_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-    ev.mark(2, ctx->stream);
-    HIP_TRY(hipMemcpyAsync(fpfh, d_out.p, 4 * (size_t)m * FPFH_BINS, hipMemcpyDeviceToHost, ctx->stream));
-    if (k_or_null) HIP_TRY(hipMemcpyAsync(k_or_null, d_kout.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ev.on)
-        fprintf(stderr, "pcr_fpfh_times points %lld rows %lld spfh_ms %.4f fpfh_rows_ms %.4f\n", (long long)t->n, (long long)m, ev.ms(0), ev.ms(1));
-    return PCR_OK;
+    return fpfh_run(t, r, rows, m, fpfh, k_or_null);
 }
 
 // splits of B: enough blocks to fill the chip when A is short, every split at least two tiles long (a one-tile block has no
@@ -465,10 +430,11 @@ extern "C" pcr_status pcr_feature_match(pcr_context *ctx, const float *A, int64_
     HIP_TRY(d_part.alloc((size_t)na * ny * 2));
     HIP_TRY(hipMemcpyAsync(d_A.p, A, 4 * (size_t)na * dim, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_B.p, B, 4 * (size_t)nb * dim, hipMemcpyHostToDevice, ctx->stream));
-    FpEvents ev;
-    if (fpfh_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_FPFH_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
     ev.mark(0, ctx->stream);
-    const dim3 grid((unsigned)((na + FNN_BLOCK - 1) / FNN_BLOCK), (unsigned)ny);
+    const dim3 grid(grid_for(na, FNN_BLOCK).x, (unsigned)ny);
     if (dim == 33)
         hipLaunchKernelGGL(k_feature_nn<33>, grid, dim3(FNN_BLOCK), 0, ctx->stream, (const float *)d_A.p, na, (const float *)d_B.p, nb, dim, chunk,
                            d_part.p);
@@ -477,7 +443,7 @@ extern "C" pcr_status pcr_feature_match(pcr_context *ctx, const float *A, int64_
                            d_part.p);
     HIP_TRY(hipGetLastError());
     ev.mark(1, ctx->stream);
-    hipLaunchKernelGGL(k_feature_merge, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)d_part.p, na, ny, d_idx.p,
+    hipLaunchKernelGGL(k_feature_merge, grid_for(na, 256), dim3(256), 0, ctx->stream, (const uint64_t *)d_part.p, na, ny, d_idx.p,
                        d_d1.p, d_d2.p);
     HIP_TRY(hipGetLastError());
     ev.mark(2, ctx->stream);

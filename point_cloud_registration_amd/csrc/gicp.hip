@@ -28,21 +28,8 @@ extern __shared__ __attribute__((aligned(16))) char gicp_smem[];
 // ---- covariances ------------------------------------------------------------------------------------------------------
 template <typename LIST>
 __device__ __forceinline__ void gicp_cov_finish(const PtF *pts, const PtF me, int mode, double eps, float *cov, LIST &L) {
-    // two-pass float64 covariance over the neighbours found (knn_normals.hip: the compat == 0 branch of knn_normals_finish)
-    double mx = 0, my = 0, mz = 0;
-    L.for_each([&](int, float, uint32_t js) { const PtF p = pts[js]; mx += p.x; my += p.y; mz += p.z; });
-    const double kd = (double)(L.cnt > 0 ? L.cnt : 1);
-    mx /= kd; my /= kd; mz /= kd;
     double c[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) c[a] = 0;
-    L.for_each([&](int, float, uint32_t js) {
-        const PtF p = pts[js];
-        const double dx = p.x - mx, dy = p.y - my, dz = p.z - mz;
-        c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
-    });
-#pragma unroll
-    for (int a = 0; a < 6; ++a) c[a] /= kd;
+    knn_cov6_f64(L, pts, c);
     if (mode == PCR_COV_PLANE) {
         double n[3];
         smallest_eigvec3(c, n);
@@ -53,39 +40,21 @@ __device__ __forceinline__ void gicp_cov_finish(const PtF *pts, const PtF me, in
     for (int a = 0; a < 6; ++a) dst[a] = (float)c[a];
 }
 
-// REG = 1: the collect path (k <= 16); 0: the LDS list -- launch shape and LDS sizing of k_knn_normals
+// REG = 1: the collect path (k <= 16); 0: the LDS list (knn_self, knn_device.h)
 template <int REG>
 __global__ void __launch_bounds__(KNN_BLOCK) k_gicp_cov(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, int k, int mode,
                                                         double eps, float *cov) {
     const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
     if (i >= n) return;
     const PtF me = pts[i];
-    if (REG) {
-        KnnOut L;
-        L.init(gicp_smem);
-        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
-        gicp_cov_finish(pts, me, mode, eps, cov, L);
-    } else {
-        KnnList L;
-        L.k = k; L.cnt = 0; L.lane = threadIdx.x;
-        L.d = (float *)gicp_smem;
-        L.j = (uint32_t *)(gicp_smem + sizeof(float) * k * KNN_BLOCK);
-        L.pts = pts;
-        knn_search(g, pts, cs, me.x, me.y, me.z, L);
-        gicp_cov_finish(pts, me, mode, eps, cov, L);
-    }
+    knn_self<REG>(g, pts, cs, me, k, gicp_smem, [&](auto &L) { gicp_cov_finish(pts, me, mode, eps, cov, L); });
 }
 
 // the covariances of the n points behind the index (g, pts, cs), into cov[6 n] in the index's INPUT order
 static pcr_status gicp_estimate(pcr_context *ctx, const Geom<float> &g, const PtF *pts, const uint32_t *cs, int64_t n, int k, int mode,
                                 double eps, float *cov) {
     if (n <= 0) return PCR_OK;
-    const dim3 grid((unsigned)((n + KNN_BLOCK - 1) / KNN_BLOCK));
-    if (k <= KNN_REG_K)
-        hipLaunchKernelGGL(k_gicp_cov<1>, grid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream, g, pts, cs, n, k, mode, eps, cov);
-    else
-        hipLaunchKernelGGL(k_gicp_cov<0>, grid, dim3(KNN_BLOCK), 2 * sizeof(float) * (size_t)k * KNN_BLOCK, ctx->stream, g, pts, cs, n, k,
-                           mode, eps, cov);
+    knn_launch(k_gicp_cov<1>, k_gicp_cov<0>, k <= KNN_REG_K, n, k, ctx->stream, g, pts, cs, n, k, mode, eps, cov);
     HIP_TRY(hipGetLastError());
     return PCR_OK;
 }
@@ -163,7 +132,7 @@ extern "C" pcr_status pcr_target_estimate_covariances(pcr_target *t, int k, int 
     DevBuf<float> d_cov;                             // caller order
     HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
     PCR_TRY(gicp_estimate(ctx, t->gf, t->pts, t->cell_start, t->n, k, mode, eps, d_cov.p));
-    hipLaunchKernelGGL(k_gicp_tcov_in, grid256(t->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
+    hipLaunchKernelGGL(k_gicp_tcov_in, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
     HIP_TRY(hipGetLastError());
     if (cov_out_or_null) HIP_TRY(hipMemcpyAsync(cov_out_or_null, d_cov.p, 24 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -182,7 +151,7 @@ extern "C" pcr_status pcr_target_set_covariances(pcr_target *t, const float *cov
     DevBuf<float> d_cov;
     HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
     HIP_TRY(hipMemcpyAsync(d_cov.p, cov6, 24 * (size_t)t->n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gicp_tcov_in, grid256(t->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
+    hipLaunchKernelGGL(k_gicp_tcov_in, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const float *)d_cov.p, t->n, t->pts, (GicpRec *)t->gcov);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PCR_OK;
@@ -197,7 +166,7 @@ extern "C" pcr_status pcr_target_get_covariances(pcr_target *t, float *cov6) {
     CtxScope scope(ctx);
     DevBuf<float> d_cov;
     HIP_TRY(d_cov.alloc(6 * (size_t)t->n));
-    hipLaunchKernelGGL(k_gicp_tcov_out, grid256(t->n), dim3(256), 0, ctx->stream, (const GicpRec *)t->gcov, t->n, d_cov.p);
+    hipLaunchKernelGGL(k_gicp_tcov_out, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const GicpRec *)t->gcov, t->n, d_cov.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cov6, d_cov.p, 24 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -210,7 +179,7 @@ static pcr_status scan_cov_read(pcr_scan *s, float *cov6) {
     if (s->n == 0) return PCR_OK;
     DevBuf<float> d_cov;
     HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
-    hipLaunchKernelGGL(k_gicp_scov_perm<false>, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)s->cov, s->n, (const uint32_t *)s->order,
+    hipLaunchKernelGGL(k_gicp_scov_perm<false>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->cov, s->n, (const uint32_t *)s->order,
                        d_cov.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cov6, d_cov.p, 24 * (size_t)s->n, hipMemcpyDeviceToHost, ctx->stream));
@@ -248,7 +217,7 @@ extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode
     {
         DevBuf<float> xyz;
         HIP_TRY(xyz.alloc(3 * (size_t)s->n));
-        hipLaunchKernelGGL(k_gicp_soa_to_aos, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)s->x, (const float *)s->y, (const float *)s->z,
+        hipLaunchKernelGGL(k_gicp_soa_to_aos, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->x, (const float *)s->y, (const float *)s->z,
                            s->n, xyz.p);
         HIP_TRY(hipGetLastError());
         TmpIndex idx;
@@ -278,7 +247,7 @@ extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
     DevBuf<float> d_cov;
     HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
     HIP_TRY(hipMemcpyAsync(d_cov.p, cov6, 24 * (size_t)s->n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gicp_scov_perm<true>, grid256(s->n), dim3(256), 0, ctx->stream, (const float *)d_cov.p, s->n, (const uint32_t *)s->order,
+    hipLaunchKernelGGL(k_gicp_scov_perm<true>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)d_cov.p, s->n, (const uint32_t *)s->order,
                        s->cov);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -15,9 +15,6 @@
 //                    9 float64 accumulators, the anchor and k stay in registers; eigenvalues by eigen3.h's cyclic Jacobi.
 //   k_iss_nms        the same walk at the non-maximum radius; the sink reads the saliency at the neighbour's cell-sorted index
 //                    and keeps a count and a "beaten" flag.  A lane whose own saliency is 0 skips its walk.
-#include <float.h>
-#include <stdlib.h>
-
 #include "eigen3.h"
 #include "radius_device.h"
 
@@ -63,11 +60,6 @@ struct IssNmsSink {
     }
 };
 
-__device__ __forceinline__ bool iss_finite(const PtF &p) {
-    const float big = RealTraits<float>::inf();
-    return p.x > -big && p.x < big && p.y > -big && p.y < big && p.z > -big && p.z < big;
-}
-
 // ORIG = 0: the outputs at the lane's cell-sorted index (what k_iss_nms gathers); 1: at the point's original index.  eig and
 // kk may be NULL; sal_orig (or NULL): the saliency once more, at the original index.
 template <int ORIG>
@@ -84,7 +76,7 @@ __global__ void __launch_bounds__(ISS_BLOCK) k_iss_saliency(Geom<float> g, const
     for (int c = 0; c < 3; ++c) S.s1[c] = 0.0;
 #pragma unroll
     for (int c = 0; c < 6; ++c) S.s2[c] = 0.0;
-    if (iss_finite(me)) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
+    if (rad_finite(me.x, me.y, me.z)) rad_ball_walk(g, pts, cs, me.x, me.y, me.z, r, S);
     double lam[3] = {0.0, 0.0, 0.0};
     if (S.k != 0u) {
         const double kd = (double)S.k;
@@ -115,30 +107,13 @@ __global__ void __launch_bounds__(ISS_BLOCK) k_iss_nms(Geom<float> g, const PtF 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-// PCR_ISS_TIMES=1 (developer, tools/iss_time.py): the calls bracket their kernels with events and report the milliseconds on
-// stderr
-static bool iss_times() {
-    static const bool on = getenv("PCR_ISS_TIMES") && atoi(getenv("PCR_ISS_TIMES")) != 0;
-    return on;
-}
+// PCR_ISS_TIMES=1 (developer, tools/iss_time.py): the calls bracket their kernels with events (StageTimes) and report the
+// milliseconds on stderr
 
-struct IssEvents {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool on = false;
-    ~IssEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t init() {
-        on = true;
-        for (hipEvent_t &e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) return s; }
-        return hipSuccess;
-    }
-    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
-    float ms(int i) { float m = 0; (void)hipEventElapsedTime(&m, ev[i], ev[i + 1]); return m; }
-};
-
-// a point target, finite radii >= 0 (as radius_check of radius.hip), gammas finite and > 0, min_neighbors >= 1
+// a point target, a finite radius >= 0, gammas finite and > 0, min_neighbors >= 1
 static pcr_status iss_check(const pcr_target *t, float r, double g21, double g32, int min_neighbors, const char *who) {
-    if (t->is_voxel) { pcr_set_error("invalid argument: %s needs a point target", who); return PCR_ERR_INVALID; }
-    if (!(r >= 0 && r <= FLT_MAX)) { pcr_set_error("invalid argument: %s needs finite radii >= 0", who); return PCR_ERR_INVALID; }
+    PCR_TRY(check_point_target(t, who));
+    PCR_TRY(check_radius<float>(r, who));
     if (!(g21 > 0 && g21 <= DBL_MAX && g32 > 0 && g32 <= DBL_MAX)) {
         pcr_set_error("invalid argument: %s needs gamma_21 and gamma_32 finite and > 0", who);
         return PCR_ERR_INVALID;
@@ -147,7 +122,13 @@ static pcr_status iss_check(const pcr_target *t, float r, double g21, double g32
     return PCR_OK;
 }
 
-static dim3 iss_grid(int64_t n) { return dim3((unsigned)((n + ISS_BLOCK - 1) / ISS_BLOCK)); }
+// k_iss_saliency<ORIG> over the whole target; any of eig, kk, sal_orig may be NULL
+template <int ORIG>
+static void iss_saliency_launch(pcr_target *t, float r, double g21, double g32, int min_neighbors, double *eig, double *sal, uint32_t *kk,
+                                double *sal_orig) {
+    hipLaunchKernelGGL(k_iss_saliency<ORIG>, grid_for(t->n, ISS_BLOCK), dim3(ISS_BLOCK), 0, t->ctx->stream, t->gf, (const PtF *)t->pts,
+                       (const uint32_t *)t->cell_start, t->n, r, g21, g32, (uint32_t)min_neighbors, eig, sal, kk, sal_orig);
+}
 
 extern "C" pcr_status pcr_target_iss_saliency(pcr_target *t, float r, double gamma21, double gamma32, int min_neighbors, double *eig,
                                               double *saliency, int64_t *k) {
@@ -164,20 +145,16 @@ extern "C" pcr_status pcr_target_iss_saliency(pcr_target *t, float r, double gam
     HIP_TRY(d_eig.alloc(3 * n));
     HIP_TRY(d_sal.alloc(n));
     HIP_TRY(d_k.alloc(n));
-    IssEvents ev;
-    if (iss_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_ISS_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
     ev.mark(0, ctx->stream);
-    hipLaunchKernelGGL(k_iss_saliency<1>, iss_grid(t->n), dim3(ISS_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts,
-                       (const uint32_t *)t->cell_start, t->n, r, gamma21, gamma32, (uint32_t)min_neighbors, d_eig.p, d_sal.p, d_k.p,
-                       (double *)nullptr);
+    iss_saliency_launch<1>(t, r, gamma21, gamma32, min_neighbors, d_eig.p, d_sal.p, d_k.p, nullptr);
     HIP_TRY(hipGetLastError());
     ev.mark(1, ctx->stream);
-    std::vector<uint32_t> k32(n);
     HIP_TRY(hipMemcpyAsync(eig, d_eig.p, 8 * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(saliency, d_sal.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(k32.data(), d_k.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i) k[i] = (int64_t)k32[i];
+    PCR_TRY(download_u32_as_i64(ctx, d_k.p, n, k));
     if (ev.on) fprintf(stderr, "pcr_iss_times points %lld saliency_ms %.4f\n", (long long)t->n, ev.ms(0));
     return PCR_OK;
 }
@@ -198,16 +175,15 @@ extern "C" pcr_status pcr_target_iss_keypoints(pcr_target *t, float r_salient, f
     HIP_TRY(d_sal.alloc(n));
     HIP_TRY(d_key.alloc(n));
     if (saliency_or_null) HIP_TRY(d_sal_orig.alloc(n));
-    IssEvents ev;
-    if (iss_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_ISS_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
     ev.mark(0, ctx->stream);
-    hipLaunchKernelGGL(k_iss_saliency<0>, iss_grid(t->n), dim3(ISS_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts,
-                       (const uint32_t *)t->cell_start, t->n, r_salient, gamma21, gamma32, (uint32_t)min_neighbors, (double *)nullptr, d_sal.p,
-                       (uint32_t *)nullptr, saliency_or_null ? d_sal_orig.p : (double *)nullptr);
+    iss_saliency_launch<0>(t, r_salient, gamma21, gamma32, min_neighbors, nullptr, d_sal.p, nullptr, saliency_or_null ? d_sal_orig.p : nullptr);
     HIP_TRY(hipGetLastError());
     ev.mark(1, ctx->stream);
-    hipLaunchKernelGGL(k_iss_nms, iss_grid(t->n), dim3(ISS_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts, (const uint32_t *)t->cell_start, t->n,
-                       r_nonmax, (const double *)d_sal.p, (uint32_t)min_neighbors, d_key.p);
+    hipLaunchKernelGGL(k_iss_nms, grid_for(t->n, ISS_BLOCK), dim3(ISS_BLOCK), 0, ctx->stream, t->gf, (const PtF *)t->pts,
+                       (const uint32_t *)t->cell_start, t->n, r_nonmax, (const double *)d_sal.p, (uint32_t)min_neighbors, d_key.p);
     HIP_TRY(hipGetLastError());
     ev.mark(2, ctx->stream);
     HIP_TRY(hipMemcpyAsync(is_keypoint, d_key.p, n, hipMemcpyDeviceToHost, ctx->stream));

@@ -6,8 +6,12 @@
 //             queued unordered in LDS ([slot][lane]: a wave's accesses to one slot hit 64 banks) and ranked; queries it
 //             cannot answer (sparse neighbourhoods, overfull classes) take the ring search with the register list KnnReg
 //   k >  16   the ring expansion of nn_device.h with a sorted list in LDS (KnnList), the k-th best distance as the bound
+//
+// At the end: what the kernels over a cloud's OWN neighbourhoods share -- knn_self (one body, a finish functor), knn_cov6_f64
+// and the host's knn_launch.  A new unit of that kind starts from these and from host_util.h.
 #pragma once
 
+#include "host_util.h"
 #include "nn_device.h"
 
 #define KNN_BLOCK 64
@@ -410,4 +414,58 @@ __device__ __forceinline__ void knn_collect(const Geom<float> &g, const PtF *__r
         }
     }
     if (ok) O.cnt = min(m, k);
+}
+
+// ---- a cloud's own neighbourhoods: k_knn_normals, k_gicp_cov, k_knn_mean_dist ---------------------------------------------
+// smem: the block's dynamic LDS -- KNN_COLLECT_BYTES for the collect path, two floats per slot and lane for the list.
+__device__ __forceinline__ KnnList knn_list(char *smem, int k, const PtF *pts) {
+    KnnList L;
+    L.k = k; L.cnt = 0; L.lane = threadIdx.x;
+    L.d = (float *)smem;
+    L.j = (uint32_t *)(smem + sizeof(float) * k * KNN_BLOCK);
+    L.pts = pts;
+    return L;
+}
+
+// The k nearest neighbours of the record `me` within its own cloud (the point itself included), handed to finish(L) nearest
+// first.  REG = 1: the collect path (k <= KNN_REG_K); 0: the LDS list.
+template <int REG, typename FINISH>
+__device__ __forceinline__ void knn_self(const Geom<float> &g, const PtF *pts, const uint32_t *cs, const PtF me, int k, char *smem,
+                                         FINISH &&finish) {
+    if (REG) {
+        KnnOut L;
+        L.init(smem);
+        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
+        finish(L);
+    } else {
+        KnnList L = knn_list(smem, k, pts);
+        knn_search(g, pts, cs, me.x, me.y, me.z, L);
+        finish(L);
+    }
+}
+
+// two-pass float64 covariance (xx xy xz yy yz zz) over the neighbours found, divisor = their number
+template <typename LIST>
+__device__ __forceinline__ void knn_cov6_f64(LIST &L, const PtF *pts, double c[6]) {
+    double mx = 0, my = 0, mz = 0;
+    L.for_each([&](int, float, uint32_t js) { const PtF p = pts[js]; mx += p.x; my += p.y; mz += p.z; });
+    const double kd = (double)(L.cnt > 0 ? L.cnt : 1);
+    mx /= kd; my /= kd; mz /= kd;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) c[a] = 0;
+    L.for_each([&](int, float, uint32_t js) {
+        const PtF p = pts[js];
+        const double dx = p.x - mx, dy = p.y - my, dz = p.z - mz;
+        c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
+    });
+#pragma unroll
+    for (int a = 0; a < 6; ++a) c[a] /= kd;
+}
+
+// Host: one lane per query, the REG = 1 or the REG = 0 instantiation of a k-NN kernel with the LDS it needs.  `reg` is the
+// caller's decision: knn_use_registers(k) (knn_normals.hip, honours PCR_KNN_REG) or k <= KNN_REG_K.
+template <typename... KARGS, typename... ARGS>
+static void knn_launch(void (*k_reg)(KARGS...), void (*k_list)(KARGS...), bool reg, int64_t n, int k, hipStream_t stream, ARGS... args) {
+    hipLaunchKernelGGL(reg ? k_reg : k_list, grid_for(n, KNN_BLOCK), dim3(KNN_BLOCK),
+                       reg ? (size_t)KNN_COLLECT_BYTES : 2 * sizeof(float) * (size_t)k * KNN_BLOCK, stream, args...);
 }

@@ -11,15 +11,6 @@
 
 extern __shared__ __attribute__((aligned(16))) char knn_smem[];
 
-__device__ __forceinline__ KnnList knn_list(int k) {
-    KnnList L;
-    L.k = k; L.cnt = 0; L.lane = threadIdx.x;
-    L.d = (float *)knn_smem;
-    L.j = (uint32_t *)(knn_smem + sizeof(float) * k * KNN_BLOCK);
-    L.pts = nullptr;
-    return L;
-}
-
 template <typename LIST>
 __device__ __forceinline__ void knn_query_finish(const PtF *pts, int64_t n_target, int64_t i, int k, float *dist, int64_t *idx, LIST &L) {
     for (int s = L.cnt; s < k; ++s) { dist[i * k + s] = __int_as_float(0x7f800000); idx[i * k + s] = n_target; }
@@ -41,8 +32,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn_query(Geom<float> g, const Pt
         knn_collect(g, pts, cs, q[3 * i], q[3 * i + 1], q[3 * i + 2], k, L);
         knn_query_finish(pts, n_target, i, k, dist, idx, L);
     } else {
-        KnnList L = knn_list(k);
-        L.pts = pts;
+        KnnList L = knn_list(knn_smem, k, pts);
         knn_search(g, pts, cs, q[3 * i], q[3 * i + 1], q[3 * i + 2], L);
         knn_query_finish(pts, n_target, i, k, dist, idx, L);
     }
@@ -65,19 +55,7 @@ __device__ __forceinline__ void knn_normals_finish(const PtF *pts, const PtF me,
         c[0] = xx / kf - mx * mx; c[1] = xy / kf - mx * my; c[2] = xz / kf - mx * mz;
         c[3] = yy / kf - my * my; c[4] = yz / kf - my * mz; c[5] = zz / kf - mz * mz;
     } else {
-        double mx = 0, my = 0, mz = 0;
-        L.for_each([&](int, float, uint32_t js) { const PtF p = pts[js]; mx += p.x; my += p.y; mz += p.z; });
-        const double kd = (double)(L.cnt > 0 ? L.cnt : 1);
-        mx /= kd; my /= kd; mz /= kd;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) c[a] = 0;
-        L.for_each([&](int, float, uint32_t js) {
-            const PtF p = pts[js];
-            const double dx = p.x - mx, dy = p.y - my, dz = p.z - mz;
-            c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
-        });
-#pragma unroll
-        for (int a = 0; a < 6; ++a) c[a] /= kd;
+        knn_cov6_f64(L, pts, c);
     }
     double nv[3];
     smallest_eigvec3(c, nv);
@@ -136,23 +114,13 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_knn_normals(Geom<float> g, const 
     const int64_t i = (int64_t)(order ? order[blockIdx.x] : blockIdx.x) * KNN_BLOCK + threadIdx.x;
     if (i >= n) return;
     const PtF me = pts[i];
-    if (REG) {
-        KnnOut L;
-        L.init(knn_smem);
-        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
-        knn_normals_finish(pts, me, i, k, compat, pn, L);
-    } else {
-        KnnList L = knn_list(k);
-        L.pts = pts;
-        knn_search(g, pts, cs, me.x, me.y, me.z, L);
-        knn_normals_finish(pts, me, i, k, compat, pn, L);
-    }
+    knn_self<REG>(g, pts, cs, me, k, knn_smem, [&](auto &L) { knn_normals_finish(pts, me, i, k, compat, pn, L); });
 }
 
 // k <= 16: the register list (PCR_KNN_REG=0: the LDS list for every k, for A/B)
 static bool knn_use_registers(int k) {
-    static const int allow = getenv("PCR_KNN_REG") ? atoi(getenv("PCR_KNN_REG")) : 1;
-    return allow != 0 && k <= KNN_REG_K;
+    static const bool allow = env_i64("PCR_KNN_REG", 1, INT64_MIN, INT64_MAX) != 0;
+    return allow && k <= KNN_REG_K;
 }
 
 static pcr_status check_k(int k) {
@@ -174,15 +142,8 @@ extern "C" pcr_status pcr_knn_query(pcr_target *t, const float *q, int64_t m, in
     HIP_TRY(d_dist.alloc((size_t)m * k));
     HIP_TRY(d_idx.alloc((size_t)m * k));
     HIP_TRY(hipMemcpyAsync(d_q.p, q, 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-    const Geom<float> &g = t->gf;
-    const size_t smem = 2 * sizeof(float) * (size_t)k * KNN_BLOCK;
-    const dim3 qgrid((unsigned)((m + KNN_BLOCK - 1) / KNN_BLOCK));
-    if (knn_use_registers(k))
-        hipLaunchKernelGGL(k_knn_query<1>, qgrid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream,
-                           g, t->pts, t->cell_start, t->n, (const float *)d_q.p, m, k, d_dist.p, d_idx.p);
-    else
-        hipLaunchKernelGGL(k_knn_query<0>, qgrid, dim3(KNN_BLOCK), smem, ctx->stream,
-                           g, t->pts, t->cell_start, t->n, (const float *)d_q.p, m, k, d_dist.p, d_idx.p);
+    knn_launch(k_knn_query<1>, k_knn_query<0>, knn_use_registers(k), m, k, ctx->stream, t->gf, t->pts, t->cell_start, t->n, (const float *)d_q.p, m,
+               k, d_dist.p, d_idx.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(dist, d_dist.p, 4 * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(idx, d_idx.p, 8 * (size_t)m * k, hipMemcpyDeviceToHost, ctx->stream));
@@ -200,22 +161,18 @@ extern "C" pcr_status pcr_target_estimate_normals(pcr_target *t, int k, int comp
     if (!t->pn) HIP_TRY(pcr_persist_alloc((void **)&t->pn, sizeof(PtN) * (size_t)(t->n ? t->n : 1)));
     if (t->n > 0) {
         const Geom<float> &g = t->gf;
-        const size_t smem = 2 * sizeof(float) * (size_t)k * KNN_BLOCK;
-        const dim3 ngrid((unsigned)((t->n + KNN_BLOCK - 1) / KNN_BLOCK));
-        static const int sparse_first = getenv("PCR_KNN_SPARSE_FIRST") ? atoi(getenv("PCR_KNN_SPARSE_FIRST")) : 1;
-        if (knn_use_registers(k)) {
-            DevBuf<uint32_t> order, cnt;
-            // (only where the tail is a visible share of the kernel: at 1e7 / 1e8 points the reordering costs 3 % in locality)
-            if (sparse_first && ngrid.x > 1024 && ngrid.x <= 65536) {
-                HIP_TRY(order.alloc(ngrid.x)); HIP_TRY(cnt.alloc(2));
-                HIP_TRY(hipMemsetAsync(cnt.p, 0, 2 * sizeof(uint32_t), ctx->stream));
-                hipLaunchKernelGGL(k_knn_order, dim3((ngrid.x + 255) / 256), dim3(256), 0, ctx->stream, g, t->pts, t->cell_start, ngrid.x, order.p, cnt.p);
-            }
-            hipLaunchKernelGGL(k_knn_normals<1>, ngrid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream, g, t->pts, t->cell_start, t->n, k, compat, t->pn,
-                               (const uint32_t *)order.p);
-        } else {
-            hipLaunchKernelGGL(k_knn_normals<0>, ngrid, dim3(KNN_BLOCK), smem, ctx->stream, g, t->pts, t->cell_start, t->n, k, compat, t->pn, (const uint32_t *)nullptr);
+        const unsigned nb = grid_for(t->n, KNN_BLOCK).x;
+        static const bool sparse_first = env_i64("PCR_KNN_SPARSE_FIRST", 1, INT64_MIN, INT64_MAX) != 0;
+        const bool reg = knn_use_registers(k);
+        DevBuf<uint32_t> order, cnt;
+        // (only where the tail is a visible share of the kernel: at 1e7 / 1e8 points the reordering costs 3 % in locality)
+        if (reg && sparse_first && nb > 1024 && nb <= 65536) {
+            HIP_TRY(order.alloc(nb)); HIP_TRY(cnt.alloc(2));
+            HIP_TRY(hipMemsetAsync(cnt.p, 0, 2 * sizeof(uint32_t), ctx->stream));
+            hipLaunchKernelGGL(k_knn_order, grid_for(nb, 256), dim3(256), 0, ctx->stream, g, t->pts, t->cell_start, nb, order.p, cnt.p);
         }
+        knn_launch(k_knn_normals<1>, k_knn_normals<0>, reg, t->n, k, ctx->stream, g, t->pts, t->cell_start, t->n, k, compat, t->pn,
+                   (const uint32_t *)order.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }

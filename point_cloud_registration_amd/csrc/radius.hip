@@ -2,7 +2,7 @@
 //
 //   pcr_radius_count / _query        float32 queries against the float32 records (gf / pts)
 //   pcr_radius_count_dd / _query_dd  float64 queries against the float64 coordinates (gq / pts64)
-//   pcr_knn_mean_distance            k_knn_mean_dist<REG>, sibling of k_gicp_cov / k_knn_normals
+//   pcr_knn_mean_distance            k_knn_mean_dist<REG>: knn_self (knn_device.h) with its own finish, as k_gicp_cov / k_knn_normals
 //
 // One lane = one query, no atomics, the grid depends on the query count only.  k_radius<Real, MODE> walks the cell box of the
 // query's ball: MODE 0 counts the members, MODE 1 writes them into the lane's own segment [off[i], off[i + 1]) of the
@@ -88,9 +88,7 @@ __global__ void __launch_bounds__(RAD_BLOCK) k_radius(Geom<Real> g, const typena
         S.keys = keys + o;
         S.vals = vals ? vals + o : nullptr;
     }
-    const Real big = RealTraits<Real>::inf();
-    const bool finite = qx > -big && qx < big && qy > -big && qy < big && qz > -big && qz < big;      // (false for NaN)
-    if (finite) rad_ball_walk(g, pts, cs, qx, qy, qz, r, S);
+    if (rad_finite(qx, qy, qz)) rad_ball_walk(g, pts, cs, qx, qy, qz, r, S);
     if (MODE == 0) count[i] = (int64_t)S.cnt;
     else if (S.cnt != S.len) *flag = 1u;
 }
@@ -112,33 +110,13 @@ __global__ void __launch_bounds__(256) k_radius_unpack_dd(const uint64_t *__rest
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------
-// entries a call holds on the device at a time (PCR_RADIUS_CHUNK, read once)
+// entries a call holds on the device at a time (PCR_RADIUS_CHUNK, read once; unset or below 1: 2^26)
 static int64_t radius_budget() {
-    static const int64_t b = [] {
-        const char *e = getenv("PCR_RADIUS_CHUNK");
-        const long long v = e ? atoll(e) : 0;
-        return (int64_t)(v >= 1 ? v : (1ll << 26));
-    }();
-    return b;
+    static const int64_t v = env_i64("PCR_RADIUS_CHUNK", 0, 0, INT64_MAX);
+    return v >= 1 ? v : (int64_t)1 << 26;
 }
-// PCR_RADIUS_TIMES=1 (developer, tools/radius_time.py): a query call brackets fill / sort / unpack with events and reports
-// their milliseconds on stderr
-static bool radius_times() {
-    static const bool on = getenv("PCR_RADIUS_TIMES") && atoi(getenv("PCR_RADIUS_TIMES")) != 0;
-    return on;
-}
-
-struct RadEvents {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    ~RadEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t init() {
-        on = true;
-        for (hipEvent_t &e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) return s; }
-        return hipSuccess;
-    }
-    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
-};
+// PCR_RADIUS_TIMES=1 (developer, tools/radius_time.py): a count call brackets its kernel, a query call fill / sort / unpack of
+// every chunk, with events (StageTimes) and reports their milliseconds on stderr
 
 template <typename Real> struct RadTarget;
 template <> struct RadTarget<float> {
@@ -152,23 +130,17 @@ template <> struct RadTarget<double> {
 
 template <typename Real>
 static pcr_status radius_check(const pcr_target *t, Real r, const char *who) {
-    if (t->is_voxel) { pcr_set_error("invalid argument: %s needs a point target", who); return PCR_ERR_INVALID; }
+    PCR_TRY(check_point_target(t, who));
     if (sizeof(Real) == 8 && t->n > 0 && t->pts64 == nullptr) {
         pcr_set_error("invalid argument: %s needs a point target with float64 coordinates (pcr_target_points_set_f64)", who);
         return PCR_ERR_INVALID;
     }
-    if (!(r >= 0 && r <= (Real)(sizeof(Real) == 8 ? DBL_MAX : FLT_MAX))) {
-        pcr_set_error("invalid argument: %s needs a finite radius >= 0", who);
-        return PCR_ERR_INVALID;
-    }
-    return PCR_OK;
+    return check_radius<Real>(r, who);
 }
-
-static dim3 rad_grid(int64_t m) { return dim3((unsigned)((m + RAD_BLOCK - 1) / RAD_BLOCK)); }
 
 template <typename Real>
 static void radius_launch_count(pcr_target *t, const Real *d_q, int64_t m, Real r, int64_t *d_count) {
-    hipLaunchKernelGGL((k_radius<Real, 0>), rad_grid(m), dim3(RAD_BLOCK), 0, t->ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
+    hipLaunchKernelGGL((k_radius<Real, 0>), grid_for(m, RAD_BLOCK), dim3(RAD_BLOCK), 0, t->ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
                        (const uint32_t *)t->cell_start, d_q, m, r, d_count, (const uint32_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
                        (uint32_t *)nullptr);
 }
@@ -188,19 +160,16 @@ static pcr_status radius_count(pcr_target *t, const Real *q, int64_t m, Real r, 
     HIP_TRY(d_q.alloc(3 * (size_t)m));
     HIP_TRY(d_count.alloc((size_t)m));
     HIP_TRY(hipMemcpyAsync(d_q.p, q, sizeof(Real) * 3 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-    RadEvents ev;
-    if (radius_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_RADIUS_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
     ev.mark(0, ctx->stream);
     radius_launch_count<Real>(t, d_q.p, m, r, d_count.p);
     HIP_TRY(hipGetLastError());
     ev.mark(1, ctx->stream);
     HIP_TRY(hipMemcpyAsync(count, d_count.p, 8 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ev.on) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
-        fprintf(stderr, "pcr_radius_times %s queries %lld count_ms %.4f\n", who, (long long)m, ms);
-    }
+    if (ev.on) fprintf(stderr, "pcr_radius_times %s queries %lld count_ms %.4f\n", who, (long long)m, ev.ms(0));
     return PCR_OK;
 }
 
@@ -288,8 +257,9 @@ static pcr_status radius_query(pcr_target *t, const Real *q, int64_t m, Real r, 
     HIP_TRY(d_off.alloc((size_t)m_max + 1)); HIP_TRY(d_flag.alloc(1));
     HIP_TRY(d_dist.alloc(cap)); HIP_TRY(d_idx.alloc(cap));
     std::vector<uint32_t> rel((size_t)m_max + 1);
-    RadEvents ev;
-    if (radius_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_RADIUS_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
 
     for (size_t c = 0; c < n_chunks; ++c) {
         const int64_t a = cut[c], b = cut[c + 1], mc = b - a, E = offsets[b] - offsets[a];
@@ -297,7 +267,7 @@ static pcr_status radius_query(pcr_target *t, const Real *q, int64_t m, Real r, 
         HIP_TRY(hipMemcpyAsync(d_off.p, rel.data(), 4 * (size_t)(mc + 1), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemsetAsync(d_flag.p, 0, 4, ctx->stream));
         ev.mark(0, ctx->stream);
-        hipLaunchKernelGGL((k_radius<Real, 1>), rad_grid(mc), dim3(RAD_BLOCK), 0, ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
+        hipLaunchKernelGGL((k_radius<Real, 1>), grid_for(mc, RAD_BLOCK), dim3(RAD_BLOCK), 0, ctx->stream, RadTarget<Real>::geom(t), RadTarget<Real>::pts(t),
                            (const uint32_t *)t->cell_start, (const Real *)(d_q.p + 3 * a), mc, r, (int64_t *)nullptr, (const uint32_t *)d_off.p,
                            k0.p, v0.p, d_flag.p);
         HIP_TRY(hipGetLastError());
@@ -308,10 +278,10 @@ static pcr_status radius_query(pcr_target *t, const Real *q, int64_t m, Real r, 
             PCR_TRY(radius_sort(ctx, f64, k0.p, k1.p, v0.p, v1.p, (unsigned)E, (unsigned)mc, d_off.p, &ks, &vs));
             ev.mark(2, ctx->stream);
             if (f64)
-                hipLaunchKernelGGL(k_radius_unpack_dd, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)ks,
+                hipLaunchKernelGGL(k_radius_unpack_dd, grid_for(E, 256), dim3(256), 0, ctx->stream, (const uint64_t *)ks,
                                    (const uint32_t *)vs, E, (double *)d_dist.p, d_idx.p);
             else
-                hipLaunchKernelGGL(k_radius_unpack, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)ks, E,
+                hipLaunchKernelGGL(k_radius_unpack, grid_for(E, 256), dim3(256), 0, ctx->stream, (const uint64_t *)ks, E,
                                    (float *)d_dist.p, d_idx.p);
             HIP_TRY(hipGetLastError());
         } else {
@@ -323,12 +293,9 @@ static pcr_status radius_query(pcr_target *t, const Real *q, int64_t m, Real r, 
         HIP_TRY(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         PCR_REQUIRE(flag == 0, "offsets are not the prefix sum of the counts");
-        if (ev.on) {
-            float ms[3] = {0, 0, 0};
-            for (int p = 0; p < 3; ++p) (void)hipEventElapsedTime(&ms[p], ev.ev[p], ev.ev[p + 1]);
+        if (ev.on)
             fprintf(stderr, "pcr_radius_times %s queries %lld entries %lld fill_ms %.4f sort_ms %.4f unpack_ms %.4f\n", who, (long long)mc,
-                    (long long)E, ms[0], ms[1], ms[2]);
-        }
+                    (long long)E, ev.ms(0), ev.ms(1), ev.ms(2));
         if (E > 0) {
             HIP_TRY(hipMemcpyAsync(dist + offsets[a], d_dist.p, sizeof(Real) * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipMemcpyAsync(idx + offsets[a], d_idx.p, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
@@ -361,26 +328,13 @@ __device__ __forceinline__ void knn_mean_finish(const PtF me, double *mean, LIST
     mean[pt_orig(me)] = s / (double)(L.cnt > 0 ? L.cnt : 1);
 }
 
-// REG = 1: the collect path (k <= 16); 0: the LDS list -- launch shape and LDS sizing of k_knn_normals / k_gicp_cov
+// REG = 1: the collect path (k <= 16); 0: the LDS list (knn_self, knn_device.h)
 template <int REG>
 __global__ void __launch_bounds__(KNN_BLOCK) k_knn_mean_dist(Geom<float> g, const PtF *pts, const uint32_t *cs, int64_t n, int k, double *mean) {
     const int64_t i = (int64_t)blockIdx.x * KNN_BLOCK + threadIdx.x;
     if (i >= n) return;
     const PtF me = pts[i];
-    if (REG) {
-        KnnOut L;
-        L.init(rad_smem);
-        knn_collect(g, pts, cs, me.x, me.y, me.z, k, L);
-        knn_mean_finish(me, mean, L);
-    } else {
-        KnnList L;
-        L.k = k; L.cnt = 0; L.lane = threadIdx.x;
-        L.d = (float *)rad_smem;
-        L.j = (uint32_t *)(rad_smem + sizeof(float) * k * KNN_BLOCK);
-        L.pts = pts;
-        knn_search(g, pts, cs, me.x, me.y, me.z, L);
-        knn_mean_finish(me, mean, L);
-    }
+    knn_self<REG>(g, pts, cs, me, k, rad_smem, [&](auto &L) { knn_mean_finish(me, mean, L); });
 }
 
 extern "C" pcr_status pcr_knn_mean_distance(pcr_target *t, int k, double *mean_out) {
@@ -394,13 +348,8 @@ extern "C" pcr_status pcr_knn_mean_distance(pcr_target *t, int k, double *mean_o
     CtxScope scope(ctx);
     DevBuf<double> d_mean;
     HIP_TRY(d_mean.alloc((size_t)t->n));
-    const dim3 grid((unsigned)((t->n + KNN_BLOCK - 1) / KNN_BLOCK));
-    if (k <= KNN_REG_K)
-        hipLaunchKernelGGL(k_knn_mean_dist<1>, grid, dim3(KNN_BLOCK), KNN_COLLECT_BYTES, ctx->stream, t->gf, (const PtF *)t->pts,
-                           (const uint32_t *)t->cell_start, t->n, k, d_mean.p);
-    else
-        hipLaunchKernelGGL(k_knn_mean_dist<0>, grid, dim3(KNN_BLOCK), 2 * sizeof(float) * (size_t)k * KNN_BLOCK, ctx->stream, t->gf,
-                           (const PtF *)t->pts, (const uint32_t *)t->cell_start, t->n, k, d_mean.p);
+    knn_launch(k_knn_mean_dist<1>, k_knn_mean_dist<0>, k <= KNN_REG_K, t->n, k, ctx->stream, t->gf, (const PtF *)t->pts,
+               (const uint32_t *)t->cell_start, t->n, k, d_mean.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(mean_out, d_mean.p, 8 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -24,6 +24,12 @@ __device__ __forceinline__ bool rad_member(double d2, double r) { return __built
 // covers radii whose square is subnormal.
 __device__ __forceinline__ float rad_bound2(float r) { return r * r * 1.00001f + FLT_MIN; }
 __device__ __forceinline__ double rad_bound2(double r) { const double rr = r * 1.0000001; return rr * rr + DBL_MIN; }
+// all three coordinates of a query finite (false for NaN): a query that is not walks nothing
+template <typename Real>
+__device__ __forceinline__ bool rad_finite(Real x, Real y, Real z) {
+    const Real big = RealTraits<Real>::inf();
+    return x > -big && x < big && y > -big && y < big && z > -big && z < big;
+}
 
 // ---- the float32 ball walk ------------------------------------------------------------------------------------------------
 template <typename SINK>

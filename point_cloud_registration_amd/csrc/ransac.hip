@@ -17,10 +17,7 @@
 // k_ransac_best: the maximum over the 64-bit key (count + 1, ~h) of the valid hypotheses -- the largest count, ties to the
 // smallest h -- by wave shuffles and one integer atomic maximum per wave: associative, so the winner does not depend on the
 // grid or on the chunks.
-#include <float.h>
-#include <stdlib.h>
-
-#include "pcr_internal.h"
+#include "host_util.h"
 
 #define RS_TILE PCR_RANSAC_TILE      // rows per LDS tile
 #define RS_BLOCK 256                 // poses per block, one per lane
@@ -206,28 +203,7 @@ __global__ void __launch_bounds__(256) k_ransac_best(const float *__restrict__ p
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 // PCR_RANSAC_TIMES=1 (developer, tools/ransac_time.py): the calls bracket their kernels with events and report the milliseconds
-// on stderr.  PCR_RANSAC_CHUNK: hypotheses per chunk (default 2^20).  Both are read once per process.
-static int64_t rs_env(const char *name, int64_t dflt) {
-    const char *v = getenv(name);
-    return v && *v ? atoll(v) : dflt;
-}
-static bool rs_times() { static const bool on = rs_env("PCR_RANSAC_TIMES", 0) != 0; return on; }
-static int64_t rs_chunk() {
-    static const int64_t c = [] { const int64_t v = rs_env("PCR_RANSAC_CHUNK", (int64_t)1 << 20); return v < 1 ? 1 : (v > RS_H_MAX ? RS_H_MAX : v); }();
-    return c;
-}
-struct RsEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool on = false;
-    ~RsEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t init() {
-        on = true;
-        for (hipEvent_t &e : ev) { const hipError_t s = hipEventCreate(&e); if (s != hipSuccess) return s; }
-        return hipSuccess;
-    }
-    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
-    float ms() { float t = 0; (void)hipEventSynchronize(ev[1]); (void)hipEventElapsedTime(&t, ev[0], ev[1]); return t; }
-};
+// on stderr (StageTimes).  PCR_RANSAC_CHUNK: hypotheses per chunk (default 2^20).  Both are read once per process.
 
 // splits of the rows: with few poses, enough blocks to fill the chip (RS_FILL_BLOCKS: on 256 CUs, 16 poses over 10^6 rows take
 // 49 ms unsplit, 0.81 ms in 64 splits, 0.23 ms in 245), whole tiles per split; from b and m alone
@@ -257,7 +233,7 @@ static pcr_status rs_score(pcr_context *ctx, const float *d_src, const float *d_
     int64_t rows = m;
     const int ny = rs_splits(m, b, &rows);
     if (ny > 1) HIP_TRY(hipMemsetAsync(d_count, 0, 4 * (size_t)b, ctx->stream));
-    const dim3 grid((unsigned)((b + RS_BLOCK - 1) / RS_BLOCK), (unsigned)ny), blk(RS_BLOCK);
+    const dim3 grid(grid_for(b, RS_BLOCK).x, (unsigned)ny), blk(RS_BLOCK);
     if (d_mask) hipLaunchKernelGGL(k_pose_score<true>, grid, blk, 0, ctx->stream, d_src, d_dst, m, d_poses, b, thr, rows, d_count, d_mask);
     else hipLaunchKernelGGL(k_pose_score<false>, grid, blk, 0, ctx->stream, d_src, d_dst, m, d_poses, b, thr, rows, d_count, d_mask);
     HIP_TRY(hipGetLastError());
@@ -307,8 +283,9 @@ extern "C" pcr_status pcr_pose_score(pcr_context *ctx, const float *src, const f
     HIP_TRY(hipMemcpyAsync(d_src.p, src, 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_dst.p, dst, 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_poses.p, poses, 48 * (size_t)b, hipMemcpyHostToDevice, ctx->stream));
-    RsEvents ev;
-    if (rs_times()) HIP_TRY(ev.init());
+    static const bool times = env_flag("PCR_RANSAC_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
     int ny = 1;
     ev.mark(0, ctx->stream);
     PCR_TRY(rs_score(ctx, d_src.p, d_dst.p, m, d_poses.p, b, thr, d_count.p, mask_or_null ? d_mask.p : (uint8_t *)nullptr, &ny));
@@ -317,7 +294,7 @@ extern "C" pcr_status pcr_pose_score(pcr_context *ctx, const float *src, const f
     if (mask_or_null) HIP_TRY(hipMemcpyAsync(mask_or_null, d_mask.p, (size_t)b * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ev.on)
-        fprintf(stderr, "pcr_ransac_times score m %lld b %lld splits %d score_ms %.4f\n", (long long)m, (long long)b, ny, ev.ms());
+        fprintf(stderr, "pcr_ransac_times score m %lld b %lld splits %d score_ms %.4f\n", (long long)m, (long long)b, ny, ev.ms(0));
     return PCR_OK;
 }
 
@@ -350,7 +327,8 @@ extern "C" pcr_status pcr_ransac_poses(pcr_context *ctx, const float *src, const
     const float thr = max_dist * max_dist;
     const double sim2 = (double)edge_similarity * (double)edge_similarity, e2min = (double)min_edge * (double)min_edge;
     const uint64_t s = rs_mix(seed);
-    const int64_t chunk = rs_chunk() < n_hyp ? rs_chunk() : n_hyp;
+    static const int64_t chunk_max = env_i64("PCR_RANSAC_CHUNK", (int64_t)1 << 20, 1, RS_H_MAX);
+    const int64_t chunk = chunk_max < n_hyp ? chunk_max : n_hyp;
     DevBuf<float> d_src, d_dst, d_poses;
     DevBuf<int32_t> d_count, d_samples;
     DevBuf<unsigned long long> d_acc;
@@ -360,29 +338,27 @@ extern "C" pcr_status pcr_ransac_poses(pcr_context *ctx, const float *src, const
     HIP_TRY(hipMemcpyAsync(d_src.p, src, 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_dst.p, dst, 12 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(d_acc.p, 0, 16, ctx->stream));
-    const bool times = rs_times();
+    static const bool times = env_flag("PCR_RANSAC_TIMES");
     double fit_ms = 0, score_ms = 0, best_ms = 0;
     for (int64_t h0 = 0; h0 < n_hyp; h0 += chunk) {
         const int64_t n = n_hyp - h0 < chunk ? n_hyp - h0 : chunk;
-        const dim3 grid((unsigned)((n + 255) / 256));
-        RsEvents e_fit, e_score, e_best;
-        if (times) { HIP_TRY(e_fit.init()); HIP_TRY(e_score.init()); HIP_TRY(e_best.init()); }
-        e_fit.mark(0, ctx->stream);
+        const dim3 grid = grid_for(n, 256);
+        StageTimes ev;                                    // fit | score | best
+        HIP_TRY(ev.init(times));
+        ev.mark(0, ctx->stream);
         hipLaunchKernelGGL(k_ransac_fit, grid, dim3(256), 0, ctx->stream, (const float *)d_src.p, (const float *)d_dst.p, m, h0, n, s, sim2, e2min,
                            d_poses.p, samples_or_null ? d_samples.p : (int32_t *)nullptr);
         HIP_TRY(hipGetLastError());
-        e_fit.mark(1, ctx->stream);
-        e_score.mark(0, ctx->stream);
+        ev.mark(1, ctx->stream);
         PCR_TRY(rs_score(ctx, d_src.p, d_dst.p, m, d_poses.p, n, thr, d_count.p, nullptr, nullptr));
-        e_score.mark(1, ctx->stream);
-        e_best.mark(0, ctx->stream);
+        ev.mark(2, ctx->stream);
         hipLaunchKernelGGL(k_ransac_best, grid, dim3(256), 0, ctx->stream, (const float *)d_poses.p, d_count.p, h0, n, d_acc.p);
         HIP_TRY(hipGetLastError());
-        e_best.mark(1, ctx->stream);
+        ev.mark(3, ctx->stream);
         if (samples_or_null) HIP_TRY(hipMemcpyAsync(samples_or_null + 3 * h0, d_samples.p, 12 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         if (poses_or_null) HIP_TRY(hipMemcpyAsync(poses_or_null + 12 * h0, d_poses.p, 48 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         if (counts_or_null) HIP_TRY(hipMemcpyAsync(counts_or_null + h0, d_count.p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        if (times) { fit_ms += e_fit.ms(); score_ms += e_score.ms(); best_ms += e_best.ms(); }
+        if (times) { fit_ms += ev.ms(0); score_ms += ev.ms(1); best_ms += ev.ms(2); }
     }
     unsigned long long acc[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(acc, d_acc.p, 16, hipMemcpyDeviceToHost, ctx->stream));

@@ -71,7 +71,7 @@ extern "C" pcr_status pcr_target_voxels_set_covariances(pcr_target *t, int mode,
         } else {
             DevBuf<double> key;
             HIP_TRY(key.alloc(6 * rows));
-            hipLaunchKernelGGL(k_vgicp_plane_cov, grid256(t->n), dim3(256), 0, ctx->stream, (const double *)t->st_norm, t->n, eps, key.p);
+            hipLaunchKernelGGL(k_vgicp_plane_cov, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const double *)t->st_norm, t->n, eps, key.p);
             HIP_TRY(hipGetLastError());
             PCR_TRY(pcr_permute_rows_f64(ctx, key.p, t->n, 6, cols6, 6, t->means, t->vcov));
         }
@@ -89,7 +89,7 @@ extern "C" pcr_status pcr_target_voxels_get_covariances(pcr_target *t, double *c
     CtxScope scope(ctx);
     DevBuf<double> key;
     HIP_TRY(key.alloc(6 * (size_t)t->n));
-    hipLaunchKernelGGL(k_vgicp_cov_out, grid256(t->n), dim3(256), 0, ctx->stream, (const double *)t->vcov, t->n, (const PtD *)t->means, key.p);
+    hipLaunchKernelGGL(k_vgicp_cov_out, grid_for(t->n, 256), dim3(256), 0, ctx->stream, (const double *)t->vcov, t->n, (const PtD *)t->means, key.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(cov6, key.p, sizeof(double) * 6 * (size_t)t->n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -11,15 +11,6 @@ import numpy as np
 from . import _capi
 
 
-def _rows3(a, name):
-    a = np.asarray(a)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"{name} must have shape (N, 3)")
-    if not np.all(np.isfinite(a)):
-        raise ValueError(f"{name} must be finite")
-    return a
-
-
 def compute_fpfh(points, normals=None, radius=None, k_normals=15, device=None):
     """FPFH descriptors (N, 33) float32 of ``points`` at ``radius``: for every point the histogram of its own pair features
     plus the distance-weighted, normalised histograms of its neighbours, three blocks of 11 bins that each sum to 200 (a point
@@ -41,12 +32,12 @@ def compute_fpfh_rows(points, rows, normals=None, radius=None, k_normals=15, dev
 
 
 def _fpfh(points, normals, radius, k_normals, device, rows):
-    points = _rows3(points, "points")
+    points = _capi.cloud_f32(points, "points")
     if radius is None:
         raise ValueError("radius is required")
     radius = _capi.check_radius(radius)
     if normals is not None:
-        normals = _rows3(normals, "normals")
+        normals = _capi.cloud_f32(normals, "normals")
         if normals.shape != points.shape:
             raise ValueError("normals must have the shape of points")
     else:
@@ -61,11 +52,7 @@ def _fpfh(points, normals, radius, k_normals, device, rows):
             raise ValueError("rows must not repeat")
     if len(points) == 0 or (rows is not None and len(rows) == 0):
         return np.zeros((0, 33), np.float32)
-    with np.errstate(over="ignore"):
-        xyz = np.ascontiguousarray(points, dtype=np.float32)
-    if not np.all(np.isfinite(xyz)):
-        raise ValueError("points must be finite as float32")
-    target = _capi.Target.points(_capi.get_context(device), xyz, normals)
+    target = _capi.Target.points(_capi.get_context(device), points, normals)
     if normals is None:
         target.estimate_normals(k_normals, want=False)
     if rows is None:

@@ -18,10 +18,7 @@ from .keypoints import iss_keypoints
 
 def _pairs(source, target, ia, ib):
     """The paired float32 rows source[ia], target[ib]."""
-    source, target = np.asarray(source), np.asarray(target)
-    for a, name in ((source, "source"), (target, "target")):
-        if a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f"{name} must have shape (N, 3)")
+    source, target = _capi.cloud_f32(source, "source", finite=False), _capi.cloud_f32(target, "target", finite=False)
     ia, ib = np.asarray(ia), np.asarray(ib)
     if ia.ndim != 1 or ia.shape != ib.shape:
         raise ValueError("ia and ib must be vectors of one length")

@@ -12,7 +12,6 @@ returns the same rows.
 import numpy as np
 
 from . import _capi
-from .features import _rows3
 
 
 def _radius_or_none(r, name):
@@ -47,17 +46,13 @@ def iss_keypoints(points, salient_radius=None, non_max_radius=None, gamma_21=0.9
     keypoint when it is salient, its ``non_max_radius`` ball holds at least ``min_neighbors`` points and no other point in
     that ball has a larger saliency (an exact tie goes to the smaller row index).  A radius of ``None``: 6 x (salient) and 4 x
     (non-maximum) the cloud's resolution -- twice the mean distance of ``knn_mean_distance(2)``."""
-    points = _rows3(points, "points")
+    xyz = _capi.cloud_f32(points, "points")
     salient_radius = _radius_or_none(salient_radius, "salient_radius")
     non_max_radius = _radius_or_none(non_max_radius, "non_max_radius")
     g21, g32, mn = _capi.check_iss(gamma_21, gamma_32, min_neighbors)
-    if len(points) == 0:
+    if len(xyz) == 0:
         rows = np.zeros(0, np.int64)
         return (rows, np.zeros(0, np.float64)) if return_saliency else rows
-    with np.errstate(over="ignore"):
-        xyz = np.ascontiguousarray(points, dtype=np.float32)
-    if not np.all(np.isfinite(xyz)):
-        raise ValueError("points must be finite as float32")
     target = _capi.Target.points(_capi.get_context(device), xyz)
     rs, rn = iss_radii(target, salient_radius, non_max_radius)
     res = target.iss_keypoints(rs, rn, g21, g32, mn, want_saliency=return_saliency)

@@ -10,13 +10,6 @@ import numpy as np
 from . import _capi
 
 
-def _cloud(points):
-    points = np.asarray(points)
-    if points.ndim != 2 or points.shape[1] != 3:
-        raise ValueError("points must have shape (N, 3)")
-    return points
-
-
 def _keep(points, mask):
     kept_idx = np.flatnonzero(mask).astype(np.int64)
     return points[kept_idx], kept_idx
@@ -28,13 +21,13 @@ def remove_radius_outliers(points, radius, min_neighbors, device=None):
 
     -> ``(kept_points, kept_idx)``: rows of ``points`` in the caller's dtype and their ascending int64 indices.  The search
     runs over the float32 copy of the points."""
-    points = _cloud(points)
+    points = np.asarray(points)
+    xyz = _capi.cloud_f32(points, "points", finite=False)
     radius = _capi.check_radius(radius)
     if int(min_neighbors) != min_neighbors or min_neighbors < 0:
         raise ValueError("min_neighbors must be an integer >= 0")
     if len(points) == 0:
         return _keep(points, np.zeros(0, bool))
-    xyz = np.ascontiguousarray(points, dtype=np.float32)
     count = _capi.Target.points(_capi.get_context(device), xyz).radius_count(xyz, radius)
     return _keep(points, count - 1 >= int(min_neighbors))
 
@@ -46,13 +39,13 @@ def remove_statistical_outliers(points, k=20, std_ratio=2.0, device=None):
 
     -> ``(kept_points, kept_idx)``: rows of ``points`` in the caller's dtype and their ascending int64 indices.  The search
     runs over the float32 copy of the points."""
-    points = _cloud(points)
+    points = np.asarray(points)
+    xyz = _capi.cloud_f32(points, "points", finite=False)
     k = _capi.check_k(k)
     std_ratio = float(std_ratio)
     if not np.isfinite(std_ratio):
         raise ValueError("std_ratio must be finite")
     if len(points) == 0:
         return _keep(points, np.zeros(0, bool))
-    xyz = np.ascontiguousarray(points, dtype=np.float32)
     mean_d = _capi.Target.points(_capi.get_context(device), xyz).knn_mean_distance(k)
     return _keep(points, mean_d <= np.mean(mean_d) + std_ratio * np.std(mean_d))

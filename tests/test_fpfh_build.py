@@ -3,31 +3,17 @@
 in LDS, the rest in registers, none of it in scratch memory."""
 import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "point_cloud_registration_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_fpfh_kernels_stay_out_of_scratch(tmp_path):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
-                        f"-I{REPO}/include", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(CSRC, "fpfh.hip"), "-o", str(tmp_path / "f.o")], capture_output=True, text=True, check=True)
-    usage, lds, name = {}, {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
-        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", line)
-        if m and name:
-            lds[name] = int(m.group(1))
+def test_fpfh_kernels_stay_out_of_scratch():
+    report = kernel_resources("fpfh.hip")
+    usage = {n: u["scratch"] for n, u in report.items()}
+    lds = {n: u["lds"] for n, u in report.items()}
     # k_spfh<cell-sorted / caller order>, k_fpfh, k_feature_nn<33 / 64> and its merge
     spfh = [n for n in usage if re.match(r"_Z6k_spfhILi[01]E", n)]
     fpfh = [n for n in usage if re.match(r"_Z6k_fpfh", n)]

@@ -3,31 +3,17 @@ k_iss_saliency keeps the anchor, 9 float64 sums and the Jacobi's matrix per lane
 in registers, none of it in scratch memory."""
 import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "point_cloud_registration_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_iss_kernels_stay_out_of_scratch(tmp_path):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
-                        f"-I{REPO}/include", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(CSRC, "keypoints.hip"), "-o", str(tmp_path / "k.o")], capture_output=True, text=True, check=True)
-    usage, vgprs, name = {}, {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
-        m = re.search(r" VGPRs: (\d+)", line)
-        if m and name:
-            vgprs[name] = int(m.group(1))
+def test_iss_kernels_stay_out_of_scratch():
+    report = kernel_resources("keypoints.hip")
+    usage = {n: u["scratch"] for n, u in report.items()}
+    vgprs = {n: u["vgprs"] for n, u in report.items()}
     # k_iss_saliency<cell-sorted / caller order> and k_iss_nms
     sal = [n for n in usage if re.match(r"_Z14k_iss_saliencyILi[01]E", n)]
     nms = [n for n in usage if re.match(r"_Z9k_iss_nms", n)]

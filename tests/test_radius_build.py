@@ -3,28 +3,16 @@ kernels carry a ball walk with batched loads, the mean-distance kernels the whol
 scratch memory unnoticed."""
 import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "point_cloud_registration_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_radius_kernels_stay_out_of_scratch(tmp_path):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
-                        f"-I{REPO}/include", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(CSRC, "radius.hip"), "-o", str(tmp_path / "r.o")], capture_output=True, text=True, check=True)
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
+def test_radius_kernels_stay_out_of_scratch():
+    report = kernel_resources("radius.hip")
+    usage = {n: u["scratch"] for n, u in report.items()}
     # k_radius<float / double, count / fill>, k_knn_mean_dist<list / collect>, the two unpack kernels
     assert sum(bool(re.match(r"_Z8k_radiusI[fd]Li[01]E", n)) for n in usage) == 4 and sum("k_knn_mean_dist" in n for n in usage) == 2 \
         and sum("k_radius_unpack" in n for n in usage) == 2, f"the resource report was not parsed: {sorted(usage)}"

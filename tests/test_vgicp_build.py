@@ -2,32 +2,17 @@
 the translation unit is a k_vgicp_ kernel, the reduce and fold kernels stay out of scratch memory altogether, and no kernel
 ends up there unnoticed."""
 import os
-import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "point_cloud_registration_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from kernel_resources import HIPCC, kernel_resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_vgicp_kernels_stay_out_of_scratch(tmp_path):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
-                        f"-I{REPO}/include", f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(CSRC, "vgicp.hip"), "-o", str(tmp_path / "v.o")], capture_output=True, text=True, check=True)
-    usage, vgprs, name = {}, {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            usage[name] = int(m.group(1))
-        m = re.search(r" VGPRs: (\d+)", line)
-        if m and name:
-            vgprs[name] = int(m.group(1))
+def test_vgicp_kernels_stay_out_of_scratch():
+    report = kernel_resources("vgicp.hip")
+    usage = {n: u["scratch"] for n, u in report.items()}
+    vgprs = {n: u["vgprs"] for n, u in report.items()}
     vg = {n: b for n, b in usage.items() if "k_vgicp_" in n}
     assert sum("k_vgicp_reduce" in n for n in vg) == 1 and sum("k_vgicp_fold" in n for n in vg) == 1 \
         and sum("k_vgicp_plane_cov" in n for n in vg) == 1, f"the resource report was not parsed: {sorted(usage)}"

@@ -14,91 +14,31 @@ Matching: 33-column rows, 20 k x 20 k and 100 k x 100 k (descriptors of the clou
 otherwise).  Its arithmetic is 3 D lane-operations per pair (subtract, multiply, add; no fma by contract); the share printed
 is that count over the kernel time, against one unpacked float32 VALU operation per lane and cycle on every CU:
 256 CUs x 64 lanes x 2.4 GHz = 39.3 T lane-operations/s."""
-import ctypes
 import json
 import os
-import re
 import sys
-import tempfile
 
 import numpy as np
 
 os.environ["PCR_FPFH_TIMES"] = "1"                # (read once, by the first call)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing import WARM, REPS, quiet, radius_for, timed  # noqa: E402
 from point_cloud_registration_amd import _capi  # noqa: E402
 from point_cloud_registration_amd.synthetic import street, street_normals  # noqa: E402
 
 n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 1_060_000
 out_path = sys.argv[2] if len(sys.argv) > 2 else None
-WARM, REPS = 2, 5
 VALU_LANE_OPS = 256 * 64 * 2.4e9
 
 ctx = _capi.get_context(0)
-hip = ctypes.CDLL("libamdhip64.so.7")             # (already in the process: the library's own runtime)
-stream = ctypes.c_void_p(ctx.stream())
-e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
-
-def call_ms(fn):
-    """-> (milliseconds by events around the call, what the library wrote to stderr meanwhile)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+") as f:
-        os.dup2(f.fileno(), 2)
-        try:
-            assert hip.hipEventRecord(e0, stream) == 0
-            fn()
-            assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        f.seek(0)
-        text = f.read()
-    t = ctypes.c_float(0)
-    assert hip.hipEventElapsedTime(ctypes.byref(t), e0, e1) == 0
-    return t.value, text
-
-
-def timed(fn, phases):
-    """Medians over the timed calls: {"call_ms": ..., phase: ...}"""
-    rows = []
-    for r in range(WARM + REPS):
-        ms, text = call_ms(fn)
-        row = {"call_ms": ms}
-        for p in phases:
-            row[p] = sum(float(v) for v in re.findall(rf"\b{p} ([0-9.]+)", text))
-        if r >= WARM:
-            rows.append(row)
-    return {k: float(np.median([row[k] for row in rows])) for k in rows[0]}
-
-
-def quiet(fn):
-    box = []
-    call_ms(lambda: box.append(fn()))
-    return box[0]
-
-
 pts = street(n, seed=0)
 t = _capi.Target.points(ctx, pts, street_normals(pts))
 sample = pts[np.random.default_rng(3).choice(n, min(n, 20_000), replace=False)]
 
-
-def radius_for(mean):
-    lo, hi = 0.0, 5.0
-    for _ in range(30):
-        mid = 0.5 * (lo + hi)
-        if quiet(lambda: t.radius_count(sample, mid)).mean() < mean:
-            lo = mid
-        else:
-            hi = mid
-    return float(np.float32(hi))
-
-
 res = {"n": n, "warmups": WARM, "timed_calls": REPS, "rows": []}
 F = None
 for want in (15, 60):
-    r = radius_for(want)
+    r = radius_for(t, sample, want)
     F, k = quiet(lambda: t.fpfh(r, want_k=True))
     m = timed(lambda: t.fpfh(r), ("spfh_ms", "fpfh_ms"))
     row = {"what": f"fpfh, mean neighbours {k.mean():.1f}", "r": r, "pairs": int(k.sum()), "most_neighbours": int(k.max()),

@@ -12,12 +12,9 @@ call, with HIP events on the context's stream and reports their milliseconds on 
 prints the median of the timed calls after the warm-ups, beside the time of the whole call by events around it.  The full
 pcr_target_fpfh call is timed beside the rows call, and register_global on a pair of clouds of at most 100 k points with and
 without keypoints="iss" by the wall clock."""
-import ctypes
 import json
 import os
-import re
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -25,80 +22,23 @@ import numpy as np
 os.environ["PCR_ISS_TIMES"] = "1"                 # (both read once, by the first call)
 os.environ["PCR_FPFH_TIMES"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing import WARM, REPS, quiet, radius_for, timed  # noqa: E402
 import point_cloud_registration_amd as pcr  # noqa: E402
 from point_cloud_registration_amd import _capi  # noqa: E402
 from point_cloud_registration_amd.synthetic import street, street_normals  # noqa: E402
 
 n = int(float(sys.argv[1])) if len(sys.argv) > 1 else 1_060_000
 out_path = sys.argv[2] if len(sys.argv) > 2 else None
-WARM, REPS = 2, 5
 
 ctx = _capi.get_context(0)
-hip = ctypes.CDLL("libamdhip64.so.7")             # (already in the process: the library's own runtime)
-stream = ctypes.c_void_p(ctx.stream())
-e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
-
-def call_ms(fn):
-    """-> (milliseconds by events around the call, what the library wrote to stderr meanwhile)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+") as f:
-        os.dup2(f.fileno(), 2)
-        try:
-            assert hip.hipEventRecord(e0, stream) == 0
-            fn()
-            assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        f.seek(0)
-        text = f.read()
-    t = ctypes.c_float(0)
-    assert hip.hipEventElapsedTime(ctypes.byref(t), e0, e1) == 0
-    return t.value, text
-
-
-def timed(fn, phases):
-    """Medians over the timed calls: {"call_ms": ..., phase: ...}"""
-    rows = []
-    for r in range(WARM + REPS):
-        ms, text = call_ms(fn)
-        row = {"call_ms": ms}
-        for p in phases:
-            row[p] = sum(float(v) for v in re.findall(rf"\b{p} ([0-9.]+)", text))
-        if r >= WARM:
-            rows.append(row)
-    return {k: float(np.median([row[k] for row in rows])) for k in rows[0]}
-
-
-def quiet(fn):
-    box = []
-    call_ms(lambda: box.append(fn()))
-    return box[0]
-
-
 pts = street(n, seed=0)
 nrm = street_normals(pts)
 t = _capi.Target.points(ctx, pts, nrm)
 sample = pts[np.random.default_rng(3).choice(n, min(n, 20_000), replace=False)]
 
-
-def radius_for(mean):
-    lo, hi = 0.0, 5.0
-    for _ in range(30):
-        mid = 0.5 * (lo + hi)
-        if quiet(lambda: t.radius_count(sample, mid)).mean() < mean:
-            lo = mid
-        else:
-            hi = mid
-    return float(np.float32(hi))
-
-
 res = {"n": n, "warmups": WARM, "timed_calls": REPS, "rows": []}
 for want in (15, 60):
-    rs = radius_for(want)
+    rs = radius_for(t, sample, want)
     rn = float(np.float32(rs * 2.0 / 3.0))
     mask = quiet(lambda: t.iss_keypoints(rs, rn))
     keys = np.flatnonzero(mask).astype(np.int64)
@@ -124,15 +64,8 @@ R = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0,
 b = (a.astype(np.float64) @ R.T + np.array([2.0, -1.0, 0.3])).astype(np.float32)
 nb = (na.astype(np.float64) @ R.T).astype(np.float32)
 ta = _capi.Target.points(ctx, a)
-lo, hi = 0.0, 5.0
 probe = a[np.random.default_rng(3).choice(m, min(m, 20_000), replace=False)]
-for _ in range(30):
-    mid = 0.5 * (lo + hi)
-    if quiet(lambda: ta.radius_count(probe, mid)).mean() < 60:
-        lo = mid
-    else:
-        hi = mid
-r60 = float(np.float32(hi))
+r60 = radius_for(ta, probe, 60)
 for kp in (None, "iss"):
     walls = []
     for _ in range(1 + 3):

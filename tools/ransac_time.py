@@ -13,64 +13,22 @@ hypothesis alike, so its time does not depend on the data -- and a pcr_pose_scor
 the refinement, where the rows are split over blocks.  The arithmetic of the inlier rule is 27 float32 operations and one
 integer add per (pose, row) pair; the floor printed is that count over the packed float32 rate of the chip, two operations per
 lane and cycle on every CU: 256 CUs x 64 lanes x 2 x 2.4 GHz = 78.6 T operations/s."""
-import ctypes
 import json
 import os
-import re
 import sys
-import tempfile
 
 import numpy as np
 
 os.environ["PCR_RANSAC_TIMES"] = "1"              # (read once, by the first call)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from timing import WARM, REPS, timed  # noqa: E402
 from point_cloud_registration_amd import _capi  # noqa: E402
 
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
-WARM, REPS = 2, 5
 PACKED_OPS = 256 * 64 * 2 * 2.4e9
 OPS_PER_PAIR = 28
 
 ctx = _capi.get_context(0)
-hip = ctypes.CDLL("libamdhip64.so.7")             # (already in the process: the library's own runtime)
-stream = ctypes.c_void_p(ctx.stream())
-e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
-
-
-def call_ms(fn):
-    """-> (milliseconds by events around the call, what the library wrote to stderr meanwhile)"""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+") as f:
-        os.dup2(f.fileno(), 2)
-        try:
-            assert hip.hipEventRecord(e0, stream) == 0
-            fn()
-            assert hip.hipEventRecord(e1, stream) == 0 and hip.hipEventSynchronize(e1) == 0
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        f.seek(0)
-        text = f.read()
-    t = ctypes.c_float(0)
-    assert hip.hipEventElapsedTime(ctypes.byref(t), e0, e1) == 0
-    return t.value, text
-
-
-def timed(fn, phases):
-    """Medians over the timed calls: {"call_ms": ..., phase: ...}, and the last report line"""
-    rows, text = [], ""
-    for r in range(WARM + REPS):
-        ms, text = call_ms(fn)
-        row = {"call_ms": ms}
-        for p in phases:
-            row[p] = sum(float(v) for v in re.findall(rf"\b{p} ([0-9.]+)", text))
-        if r >= WARM:
-            rows.append(row)
-    return {k: float(np.median([row[k] for row in rows])) for k in rows[0]}, text.strip()
-
-
 def pairs(m, seed):
     """Half of the rows a rigid copy with noise, the rest unrelated points."""
     rng = np.random.default_rng(seed)
@@ -88,7 +46,7 @@ H = 1 << 20
 for m in (5_000, 50_000):
     src, dst = pairs(m, seed=m)
     box = []
-    t, line = timed(lambda: box.append(_capi.ransac_poses(ctx, src, dst, H, 0, 0.1, 0.9, 1.0)), ("fit_ms", "score_ms", "best_ms"))
+    t, line = timed(lambda: box.append(_capi.ransac_poses(ctx, src, dst, H, 0, 0.1, 0.9, 1.0)), ("fit_ms", "score_ms", "best_ms"), report=True)
     floor = OPS_PER_PAIR * float(H) * m / PACKED_OPS * 1e3
     row = {"what": f"ransac M {m} H 2^20", "fit_kernel_ms": t["fit_ms"], "score_kernel_ms": t["score_ms"], "best_kernel_ms": t["best_ms"],
            "call_ms": t["call_ms"], "score_floor_ms": floor, "score_share_of_packed_peak": floor / t["score_ms"] if t["score_ms"] > 0 else None,
@@ -98,7 +56,7 @@ for m in (5_000, 50_000):
 m, b = 1_000_000, 16
 src, dst = pairs(m, seed=1)
 poses = np.tile(np.float32([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]), (b, 1))
-t, line = timed(lambda: _capi.pose_score(ctx, src, dst, poses, 0.1), ("score_ms",))
+t, line = timed(lambda: _capi.pose_score(ctx, src, dst, poses, 0.1), ("score_ms",), report=True)
 row = {"what": f"pose_score b {b} M {m}", "score_kernel_ms": t["score_ms"], "call_ms": t["call_ms"], "splits": _capi.pose_score_splits(m, b), "report": line}
 res["rows"].append(row)
 print(row, flush=True)
