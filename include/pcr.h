@@ -385,6 +385,51 @@ PCR_API pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double 
 PCR_API pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                    unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 
+/* ---- Symmetric point-to-plane ICP: the normals of BOTH clouds ---------------------------------
+ * No reference counterpart (Rusinkiewicz: "A Symmetric Objective Function for ICP", SIGGRAPH 2019; the fixed-normal-sum form
+ * of PCL).  A point target with normals (the PtN records PCR_PLANE gathers) and a scan that carries one float32 normal per
+ * point.  Every correspondence pulls along the mean of the two normals, so the error vanishes for any pair of points on the
+ * same second-order patch, not only on the same plane.  Everything is float64 from widened float32 inputs and nothing is
+ * contracted but the explicit fma()s of the accumulation.  For scan point p (untransformed) with normal n_p, matched target
+ * record (q, n_q) and pose T = (R, t), in this order of operations:
+ *   tp = xform(T, p)                                    float32, ((R_i0 x + R_i1 y) + R_i2 z) + t_i, exactly PCR_ICP's
+ *   d  = tp - q                                         float32; kept iff sqrt(d . d) < (float)max_dist (strict, float32):
+ *                                                       correspondence and gate are exactly PCR_ICP's
+ *   v_i = (R[3i] n_p.x + R[3i+1] n_p.y) + R[3i+2] n_p.z   the rotated scan normal, R the float64 rotation of T
+ *   c  = (n_q.x v_0 + n_q.y v_1) + n_q.z v_2
+ *   normal gate: skipped unless |c| >= min_cos (a NaN c is skipped); min_cos = 0 keeps every finite pair
+ *   s  = c < 0 ? -1 : +1                                PCA normals carry no sign: the objective does not depend on it -- negating
+ *                                                       any n_p or n_q returns the same bits
+ *   m  = 0.5 (n_q + s v)                                componentwise; the products with s and 0.5 are exact
+ *   r  = (m_0 d_0 + m_1 d_1) + m_2 d_2,  J = [m, p x (R^T m)]      PCR_PLANE's row with m in the place of the normal
+ *   H += J^T J, g += J^T r, e2 += r r (fma), count += 1            PCR_PLANE's accumulation; out[29] as pcr_linearize
+ * m is held fixed within a pass: its dependence on the pose is ignored, as GICP ignores its weight's.  Where R n_p = +-n_q the
+ * pass is PCR_PLANE's.  The Gauss-Newton step of pcr_align drives the loop unchanged (quirks Q2, Q3, Q4, Q7).
+ * pcr_scan_estimate_normals: what pcr_target_estimate_normals(compat = 0) computes, for every scan point within the scan: the
+ *   k nearest neighbours, the point itself included (1 <= k <= 64, else PCR_ERR_INVALID; fewer points than k: the neighbours
+ *   found), centred float64 covariance, the unit eigenvector of its smallest eigenvalue (a one-point neighbourhood: (1, 0, 0)).
+ *   The scan builds a temporary index over its own device points and releases it before returning.  A failure never leaves a
+ *   scan holding uninitialised normals.
+ * Arrays that cross the boundary (set, get, normals_out) are (n, 3) float32 in the CALLER's order; the scan must know that
+ *   order (PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT, else PCR_ERR_INVALID).  Estimating without normals_out works on any
+ *   scan.  set: a non-finite entry gives PCR_ERR_INVALID and leaves the old normals.  get: PCR_ERR_NO_TARGET when there are none.
+ *   Normals and GICP covariances coexist on a scan.
+ * pcr_symm_linearize: PCR_ERR_NO_TARGET for a voxel target, a point target without normals or a scan without normals;
+ *   PCR_ERR_INVALID for min_cos outside [0, 1] or NaN.  A full search into a match buffer of the call (the scan's reuse state is
+ *   left alone), then a reduce launch that writes one row of sums per block with plain stores and a one-block fold that adds
+ *   the rows in block order: no atomics, the grid depends on the scan size and the device only -- two calls return the same
+ *   bits.  An empty scan gives zeros.
+ * pcr_symm_align: the host-driven loop of pcr_align(PCR_FLAG_HOST_LOOP) over pcr_symm_linearize: same step, same trace rows
+ *   (16 + 29 doubles), PCR_ERR_SINGULAR as there.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group).                        */
+PCR_API pcr_status pcr_scan_estimate_normals(pcr_scan *s, int k, float *normals_out_or_null);
+PCR_API pcr_status pcr_scan_set_normals(pcr_scan *s, const float *normals);
+PCR_API pcr_status pcr_scan_get_normals(pcr_scan *s, float *normals);
+PCR_API pcr_status pcr_symm_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos,
+                                      unsigned flags, double out[29]);
+PCR_API pcr_status pcr_symm_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                  double min_cos, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

@@ -15,6 +15,7 @@ from .icp import ICP
 from .ndt import NDT
 from .gicp import GICP
 from .vgicp import VGICP
+from .symmetric_icp import SymmetricICP
 from .kdtree import KDTree
 from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
 from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
@@ -25,7 +26,7 @@ from .keypoints import iss_keypoints
 from .global_registration import score_poses, fit_rigid, ransac_pose, register_global
 
 __all__ = [
-    "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "KDTree", "VoxelGrid", "voxel_filter",
+    "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "SymmetricICP", "KDTree", "VoxelGrid", "voxel_filter",
     "color_by_voxel", "get_keys", "estimate_normals", "get_norm_lines", "estimate_norm_with_tree",
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",

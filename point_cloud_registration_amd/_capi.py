@@ -152,6 +152,12 @@ PROTOTYPES = {
     "pcr_scan_get_covariances": (C.c_int, [_vp, _f32p]),
     "pcr_gicp_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
     "pcr_gicp_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    # Symmetric point-to-plane ICP: normals on a scan and the pass that uses both clouds' normals (include/pcr.h)
+    "pcr_scan_estimate_normals": (C.c_int, [_vp, C.c_int, _vp]),
+    "pcr_scan_set_normals": (C.c_int, [_vp, _f32p]),
+    "pcr_scan_get_normals": (C.c_int, [_vp, _f32p]),
+    "pcr_symm_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _f64p]),
+    "pcr_symm_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
     # Voxelized GICP: per-voxel covariances and the distribution-to-voxel pass (include/pcr.h)
     "pcr_target_voxels_set_covariances": (C.c_int, [_vp, C.c_int, C.c_double, _vp]),
     "pcr_target_voxels_get_covariances": (C.c_int, [_vp, _f64p]),
@@ -892,6 +898,23 @@ class Scan:
         check(lib().pcr_scan_get_covariances(self.handle, out))
         return out
 
+    # -- SymmetricICP normals: float32 (N, 3), in the caller's order (include/pcr.h)
+    def estimate_normals(self, k=10, want=True):
+        out = np.empty((self.n, 3), np.float32) if want else None
+        check(lib().pcr_scan_estimate_normals(self.handle, int(k), _ptr(out)))
+        return out
+
+    def set_normals(self, normals):
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if normals.shape != (self.n, 3):
+            raise ValueError("normals must have shape (N, 3)")
+        check(lib().pcr_scan_set_normals(self.handle, normals))
+
+    def get_normals(self):
+        out = np.empty((self.n, 3), np.float32)
+        check(lib().pcr_scan_get_normals(self.handle, out))
+        return out
+
     def member(self, i):
         """Member i's shard of a group scan (borrowed: destroyed with the group scan; ``ctx`` is the member's context).  A plain
         ``linearize`` over it needs FLAG_LOCAL_ONLY: the member's context takes part in the group's exchange."""
@@ -1221,6 +1244,18 @@ def vgicp_linearize(target, scan, T, max_dist, flags=0):
 def vgicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
     """pcr_vgicp_align: the host-driven Gauss-Newton loop over pcr_vgicp_linearize, behind the boundary."""
     return _align(lib().pcr_vgicp_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
+
+
+def symm_linearize(target, scan, T, max_dist, min_cos=0.0, flags=0):
+    """pcr_symm_linearize -> the 29 sums of one symmetric point-to-plane pass."""
+    entry = lambda t, s, T, md, fl, out: lib().pcr_symm_linearize(t, s, T, md, float(min_cos), fl, out)
+    return _linearize29(entry, target, scan, T, max_dist, flags)
+
+
+def symm_align(target, scan, T_init, max_iter, tol, max_dist, min_cos=0.0, flags=0, want_trace=False):
+    """pcr_symm_align: the host-driven Gauss-Newton loop over pcr_symm_linearize, behind the boundary."""
+    entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_symm_align(t, s, T0, it, tol, md, float(min_cos), *rest)
+    return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
 
 
 _linearize_fast = None

@@ -108,8 +108,6 @@ static pcr_status check_cov_args(int k, int mode, double eps) {
     if (k < 1 || k > KNN_MAX_K) { pcr_set_error("k must be in [1, %d]", KNN_MAX_K); return PCR_ERR_INVALID; }
     return check_cov_mode(mode, eps);
 }
-static bool scan_knows_order(const pcr_scan *s) { return !s->sorted || s->order != nullptr; }
-#define GICP_NEED_ORDER "the scan must know the caller's order: PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT"
 
 static pcr_status target_cov_alloc(pcr_target *t) {
     if (!t->gcov) HIP_TRY(pcr_persist_alloc((void **)&t->gcov, sizeof(GicpRec) * (size_t)(t->n ? t->n : 1)));
@@ -187,16 +185,24 @@ static pcr_status scan_cov_read(pcr_scan *s, float *cov6) {
     return PCR_OK;
 }
 
-// a temporary point index over a scan's own device points, released on scope exit (its blocks go back to the context's cache)
-struct TmpIndex {
-    pcr_target *t = nullptr;
-    ~TmpIndex() { pcr_target_release(t); }
-};
+pcr_status pcr_scan_self_index(pcr_scan *s, TmpIndex *idx) {
+    pcr_context *ctx = s->ctx;
+    DevBuf<float> xyz;
+    HIP_TRY(xyz.alloc(3 * (size_t)s->n));
+    hipLaunchKernelGGL(k_gicp_soa_to_aos, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->x, (const float *)s->y, (const float *)s->z,
+                       s->n, xyz.p);
+    HIP_TRY(hipGetLastError());
+    idx->t = new pcr_target();
+    idx->t->ctx = ctx; idx->t->n = s->n;
+    // (no extended lists: the k-NN search reads cell_start and the cell-sorted points only)
+    PCR_TRY(pcr_build_point_grid(ctx, xyz.p, s->n, 0.f, idx->t, false, 0.0));
+    return PCR_OK;      // (xyz goes back to the context's cache: a later user of the block queues behind the build on the one stream)
+}
 
 extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode, double eps, float *cov_out_or_null) {
     PCR_REQUIRE(s, "NULL argument");
     PCR_TRY(check_cov_args(k, mode, eps));
-    PCR_REQUIRE(!cov_out_or_null || scan_knows_order(s), GICP_NEED_ORDER);
+    PCR_REQUIRE(!cov_out_or_null || pcr_scan_knows_order(s), PCR_NEED_ORDER);
     pcr_context *ctx = s->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
@@ -215,16 +221,8 @@ extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode
     } undo{s, dst, fresh};
     if (!fresh) { s->cov = nullptr; undo.armed = true; }      // (re-estimating: a failure leaves the scan without covariances)
     {
-        DevBuf<float> xyz;
-        HIP_TRY(xyz.alloc(3 * (size_t)s->n));
-        hipLaunchKernelGGL(k_gicp_soa_to_aos, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->x, (const float *)s->y, (const float *)s->z,
-                           s->n, xyz.p);
-        HIP_TRY(hipGetLastError());
         TmpIndex idx;
-        idx.t = new pcr_target();
-        idx.t->ctx = ctx; idx.t->n = s->n;
-        // (no extended lists: the k-NN search reads cell_start and the cell-sorted points only)
-        PCR_TRY(pcr_build_point_grid(ctx, xyz.p, s->n, 0.f, idx.t, false, 0.0));
+        PCR_TRY(pcr_scan_self_index(s, &idx));
         // the index's input order is the scan's device order: pt_orig lands every point's six floats in the scan's array directly
         PCR_TRY(gicp_estimate(ctx, idx.t->gf, idx.t->pts, idx.t->cell_start, s->n, k, mode, eps, dst));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -237,7 +235,7 @@ extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode
 
 extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
     PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
-    PCR_REQUIRE(scan_knows_order(s), GICP_NEED_ORDER);
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
     PCR_TRY(check_cov_finite(cov6, 6 * (size_t)s->n));
     pcr_context *ctx = s->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -257,7 +255,7 @@ extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
 extern "C" pcr_status pcr_scan_get_covariances(pcr_scan *s, float *cov6) {
     PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
     if (!s->cov) { pcr_set_error("scan has no per-point covariances"); return PCR_ERR_NO_TARGET; }
-    PCR_REQUIRE(scan_knows_order(s), GICP_NEED_ORDER);
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
     HIP_TRY(hipSetDevice(s->ctx->device));
     CtxScope scope(s->ctx);
     return scan_cov_read(s, cov6);

@@ -335,6 +335,8 @@ struct pcr_scan {
     bool sorted = false;                              // the points were Morton-sorted: device order != caller order
     uint32_t *order = nullptr;                        // PCR_FLAG_KEEP_ORDER on a sorted scan: device position -> caller index
     float *cov = nullptr;                             // GICP: covariances in DEVICE order, 6 floats per point (xx xy xz yy yz zz); NULL = none
+    float *nrm = nullptr;                             // SymmetricICP: normals in DEVICE order, 3 floats per point; NULL = none (symm.hip)
+    double symm_min_cos = 0;                          // ... and the normal gate of the pass under way: pcr_pass_fn has no slot for it
     // matched cell-sorted index per scan point (PCR_NONE = gated out), written by k_nn_scan and read
     // by the reduce kernel; kept across passes: the previous match is an exact upper bound for the
     // next search against the SAME target (nn_serial)
@@ -364,6 +366,9 @@ struct pcr_scan {
 // device memory owned by a scan: from the context's block cache when a block fits, else hipMalloc
 hipError_t pcr_scan_alloc(pcr_scan *s, void **p, size_t bytes);
 void pcr_scan_free(pcr_scan *s, void *p);      // one block back to the cache (nullptr: no-op)
+// per-point payloads (covariances, normals) cross the boundary in the CALLER's order: the scan must know it
+static inline bool pcr_scan_knows_order(const pcr_scan *s) { return !s->sorted || s->order != nullptr; }
+#define PCR_NEED_ORDER "the scan must know the caller's order: PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT"
 
 // S scans uploaded together (pcr_scan_batch_create): each one sorted exactly as pcr_scan_create sorts it, each owning its blocks
 struct pcr_scan_batch {
@@ -379,6 +384,15 @@ struct pcr_scan_batch {
 
 // ---- api.hip
 void pcr_target_release(pcr_target *t);      // frees a target and everything it owns (blocks back to its context's cache)
+
+// a temporary point index, released on scope exit (its blocks go back to the context's cache)
+struct TmpIndex {
+    pcr_target *t = nullptr;
+    ~TmpIndex() { pcr_target_release(t); }
+};
+// ---- gicp.hip: the index over a scan's OWN device points that its per-point estimates (covariances, normals) search.  Its
+// input order is the scan's device order, so pt_orig lands a point's payload in the scan's array directly.  s->n > 0
+pcr_status pcr_scan_self_index(pcr_scan *s, TmpIndex *idx);
 
 // ---- index_build.hip
 pcr_status pcr_build_point_grid(pcr_context *ctx, const float *d_xyz, int64_t n, float cell_hint, pcr_target *t, bool use_env = true,
