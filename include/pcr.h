@@ -430,6 +430,69 @@ PCR_API pcr_status pcr_symm_linearize(pcr_target *t, pcr_scan *s, const double T
 PCR_API pcr_status pcr_symm_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                   double min_cos, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
 
+/* ---- Colored ICP: geometry plus intensity on the target's tangent planes -----------------------
+ * No reference counterpart (Park, Zhou, Koltun: "Colored Point Cloud Registration Revisited", ICCV 2017; the form Open3D
+ * offers).  "Intensity" is one float32 per point: a LiDAR return strength, or a colour reduced to one channel; its scale is the
+ * caller's business (Open3D: values in [0, 1] with coordinates in metres).  A point target with normals (the PtN records
+ * PCR_PLANE gathers) carries an intensity I_q and a gradient g_q (three floats) per point; a scan carries an intensity I_p per
+ * point.  Everything is float64 from widened float32 inputs and nothing is contracted but the explicit fma()s of the
+ * accumulation.
+ * The gradient of target point q with unit normal n (pcr_target_estimate_color_gradients): over its k nearest neighbours q_i
+ *   within the target, nearest first (1 <= k <= 64; the point itself is found as always and left out here with every other
+ *   neighbour whose float32 squared distance is not > 0; w = the number that remain), in this order of operations:
+ *   e  = q_i - q                                        per component, float64
+ *   en = (e_0 n_0 + e_1 n_1) + e_2 n_2,  u = e - en n   the neighbour's offset within the tangent plane
+ *   M += u u^T (xx xy xz yy yz zz),  b += u (I_i - I_q) neighbour by neighbour, a product and an addition each
+ *   M_ab += (double)(w w) (n_a n_b)                     Open3D's constraint row: the component along n is pinned to zero
+ *   det = a bc + 2 de f - a f^2 - b e^2 - c d^2         (a b c = M_xx M_yy M_zz, d e f = M_xy M_xz M_yz; left to right)
+ *   s  = M^-1 b                                         the adjugate over det, the expressions of the GICP weight's inverse;
+ *                                                       s_i = (o_i0 b_0 + o_i1 b_1) + o_i2 b_2
+ *   sn = (s_0 n_0 + s_1 n_1) + s_2 n_2,  g = s - sn n   one projection, so g is tangent to rounding; rounded to float32
+ *   g is EXACTLY zero when w < 3, when det is not > 0, or when a component of the float32 result is not finite.  There is no
+ *   conditioning guard beyond det > 0: near-collinear neighbourhoods give large gradients, as they do in Open3D.  The result
+ *   does not depend on the sign of n; doubling every intensity doubles it bit for bit.
+ * One correspondence: found and gated exactly as PCR_ICP's.  For scan point p (untransformed) with intensity I_p, matched
+ *   target record (q, n, I_q, g) and pose T = (R, t):
+ *   tp = xform(T, p),  d = tp - q                       float32, kept iff sqrt(d . d) < (float)max_dist (strict, float32)
+ *   r_G = (n_0 d_0 + n_1 d_1) + n_2 d_2,  J_G = [n, p x (R^T n)]          PCR_PLANE's row
+ *   gn  = (g_0 n_0 + g_1 n_1) + g_2 n_2,  m = g - gn n                    the gradient's tangent part (given gradients need not
+ *                                                                         be tangent)
+ *   r_C = (I_q - I_p) + ((m_0 d_0 + m_1 d_1) + m_2 d_2),  J_C = [m, p x (R^T m)]   PCR_PLANE's row with m in the place of n:
+ *                                                       Open3D's I_q + g . (s' - q) - I_p, s' = tp projected onto the tangent
+ *                                                       plane of q, and its exact derivative
+ *   with a_G = sqrt(lambda), a_C = sqrt(1 - lambda), taken once on the host in double:
+ *   J = a_G J_G, r = a_G r_G:   H += J^T J, g += J^T r, e2 += r r (fma)   PCR_PLANE's accumulation
+ *   J = a_C J_C, r = a_C r_C:   the same                                  count += 1 once per CORRESPONDENCE: out[28]
+ *   A pair whose target gradient is zero adds (a_C (I_q - I_p))^2 to e2 and nothing else on the colour side.  lambda = 1 returns
+ *   the bits of the same call with zero gradients and any intensities.  Negating any target normal returns the same bits.
+ * pcr_target_set_intensity: (n,) intensities and optionally (n, 3) gradients, float32, in the CALLER's order.  Needs a point
+ *   target with normals, else PCR_ERR_NO_TARGET.  A non-finite entry gives PCR_ERR_INVALID and leaves the old payload.  Given
+ *   gradients are stored as they are; without them the gradients are zero until estimated.
+ * pcr_target_estimate_color_gradients: needs intensities (PCR_ERR_NO_TARGET); k outside [1, 64]: PCR_ERR_INVALID.
+ * pcr_target_get_color: caller's order; either array may be NULL.  PCR_ERR_NO_TARGET when there is no colour payload.
+ * pcr_target_set_normals / pcr_target_estimate_normals FREE a target's colour payload: the gradients lie in the tangent planes
+ *   of the normals they were estimated with, and a later coloured pass is refused instead of reading stale ones.
+ * pcr_scan_set_intensity / _get_intensity: (n,) float32 in the CALLER's order; the scan must know that order
+ *   (PCR_FLAG_KEEP_ORDER or PCR_FLAG_NO_SCAN_SORT, else PCR_ERR_INVALID).  set: a non-finite entry gives PCR_ERR_INVALID and
+ *   leaves the old intensities.  get: PCR_ERR_NO_TARGET when there are none.  Intensities, normals and GICP covariances coexist
+ *   on a scan.
+ * pcr_color_linearize: PCR_ERR_NO_TARGET for a voxel target, a point target without normals or without colour records, or a
+ *   scan without intensities; PCR_ERR_INVALID for lambda_geometric outside [0, 1] or NaN.  Search, reduce and fold as
+ *   pcr_symm_linearize: no atomics, two calls return the same bits.  An empty scan gives zeros.
+ * pcr_color_align: the host-driven loop of pcr_align(PCR_FLAG_HOST_LOOP) over pcr_color_linearize: same step, same trace rows
+ *   (16 + 29 doubles), PCR_ERR_SINGULAR as there.
+ * PCR_ERR_UNSUPPORTED: a context with a communicator attached (pcr_comm_*, members of a pcr_group).                        */
+PCR_API pcr_status pcr_target_set_intensity(pcr_target *t, const float *intensity, const float *gradient_or_null);
+PCR_API pcr_status pcr_target_estimate_color_gradients(pcr_target *t, int k, float *gradient_out_or_null);
+PCR_API pcr_status pcr_target_get_color(pcr_target *t, float *intensity_or_null, float *gradient_or_null);
+PCR_API pcr_status pcr_scan_set_intensity(pcr_scan *s, const float *intensity);
+PCR_API pcr_status pcr_scan_get_intensity(pcr_scan *s, float *intensity);
+PCR_API pcr_status pcr_color_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                       unsigned flags, double out[29]);
+PCR_API pcr_status pcr_color_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                   double lambda_geometric, unsigned flags, double T_out[16], int *iterations,
+                                   double *trace_or_null);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

@@ -16,6 +16,7 @@ from .ndt import NDT
 from .gicp import GICP
 from .vgicp import VGICP
 from .symmetric_icp import SymmetricICP
+from .colored_icp import ColoredICP
 from .kdtree import KDTree
 from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
 from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
@@ -26,7 +27,7 @@ from .keypoints import iss_keypoints
 from .global_registration import score_poses, fit_rigid, ransac_pose, register_global
 
 __all__ = [
-    "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "SymmetricICP", "KDTree", "VoxelGrid", "voxel_filter",
+    "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "SymmetricICP", "ColoredICP", "KDTree", "VoxelGrid", "voxel_filter",
     "color_by_voxel", "get_keys", "estimate_normals", "get_norm_lines", "estimate_norm_with_tree",
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",

@@ -158,6 +158,14 @@ PROTOTYPES = {
     "pcr_scan_get_normals": (C.c_int, [_vp, _f32p]),
     "pcr_symm_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _f64p]),
     "pcr_symm_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    # Colored ICP: intensities and tangent-plane gradients on a target, intensities on a scan, the two-row pass (include/pcr.h)
+    "pcr_target_set_intensity": (C.c_int, [_vp, _f32p, _vp]),
+    "pcr_target_estimate_color_gradients": (C.c_int, [_vp, C.c_int, _vp]),
+    "pcr_target_get_color": (C.c_int, [_vp, _vp, _vp]),
+    "pcr_scan_set_intensity": (C.c_int, [_vp, _f32p]),
+    "pcr_scan_get_intensity": (C.c_int, [_vp, _f32p]),
+    "pcr_color_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _f64p]),
+    "pcr_color_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
     # Voxelized GICP: per-voxel covariances and the distribution-to-voxel pass (include/pcr.h)
     "pcr_target_voxels_set_covariances": (C.c_int, [_vp, C.c_int, C.c_double, _vp]),
     "pcr_target_voxels_get_covariances": (C.c_int, [_vp, _f64p]),
@@ -627,6 +635,28 @@ class Target:
         check(lib().pcr_target_get_normals(self.handle, out))
         return out
 
+    # -- ColoredICP: float32 intensities (N,) and tangent-plane gradients (N, 3), in the caller's order (include/pcr.h)
+    def set_intensity(self, intensity, gradient=None):
+        intensity = np.ascontiguousarray(intensity, dtype=np.float32)
+        if intensity.shape != (self.size(),):
+            raise ValueError("intensity must have shape (N,)")
+        if gradient is not None:
+            gradient = np.ascontiguousarray(gradient, dtype=np.float32)
+            if gradient.shape != (self.size(), 3):
+                raise ValueError("gradient must have shape (N, 3)")
+        check(lib().pcr_target_set_intensity(self.handle, intensity, _ptr(gradient)))
+
+    def estimate_color_gradients(self, k=10, want=True):
+        out = np.empty((self.size(), 3), np.float32) if want else None
+        check(lib().pcr_target_estimate_color_gradients(self.handle, int(k), _ptr(out)))
+        return out
+
+    def get_color(self):
+        """-> (intensity (N,), gradient (N, 3))"""
+        inten, grad = np.empty(self.size(), np.float32), np.empty((self.size(), 3), np.float32)
+        check(lib().pcr_target_get_color(self.handle, _ptr(inten), _ptr(grad)))
+        return inten, grad
+
     # -- GICP covariances: float32 (N, 6) = xx xy xz yy yz zz, in the caller's order (include/pcr.h)
     def estimate_covariances(self, k=10, mode=COV_PLANE, eps=1e-3, want=True):
         out = np.empty((self.size(), 6), np.float32) if want else None
@@ -913,6 +943,18 @@ class Scan:
     def get_normals(self):
         out = np.empty((self.n, 3), np.float32)
         check(lib().pcr_scan_get_normals(self.handle, out))
+        return out
+
+    # -- ColoredICP intensities: float32 (N,), in the caller's order (include/pcr.h)
+    def set_intensity(self, intensity):
+        intensity = np.ascontiguousarray(intensity, dtype=np.float32)
+        if intensity.shape != (self.n,):
+            raise ValueError("intensity must have shape (N,)")
+        check(lib().pcr_scan_set_intensity(self.handle, intensity))
+
+    def get_intensity(self):
+        out = np.empty(self.n, np.float32)
+        check(lib().pcr_scan_get_intensity(self.handle, out))
         return out
 
     def member(self, i):
@@ -1255,6 +1297,18 @@ def symm_linearize(target, scan, T, max_dist, min_cos=0.0, flags=0):
 def symm_align(target, scan, T_init, max_iter, tol, max_dist, min_cos=0.0, flags=0, want_trace=False):
     """pcr_symm_align: the host-driven Gauss-Newton loop over pcr_symm_linearize, behind the boundary."""
     entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_symm_align(t, s, T0, it, tol, md, float(min_cos), *rest)
+    return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
+
+
+def color_linearize(target, scan, T, max_dist, lambda_geometric=0.968, flags=0):
+    """pcr_color_linearize -> the 29 sums of one coloured pass (two rows per correspondence, out[28] counts correspondences)."""
+    entry = lambda t, s, T, md, fl, out: lib().pcr_color_linearize(t, s, T, md, float(lambda_geometric), fl, out)
+    return _linearize29(entry, target, scan, T, max_dist, flags)
+
+
+def color_align(target, scan, T_init, max_iter, tol, max_dist, lambda_geometric=0.968, flags=0, want_trace=False):
+    """pcr_color_align: the host-driven Gauss-Newton loop over pcr_color_linearize, behind the boundary."""
+    entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_color_align(t, s, T0, it, tol, md, float(lambda_geometric), *rest)
     return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
 
 

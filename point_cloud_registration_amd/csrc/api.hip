@@ -457,7 +457,7 @@ static void target_free(pcr_target *t) { pcr_target_release(t); }
 void pcr_target_release(pcr_target *t) {
     if (!t) return;
     target_free(t->filter);
-    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->lbox_h2, t->gbox_h2, t->cs_h, t->pts_h, t->j_h, t->cs_h2, t->pts_h2, t->j_h2, t->pts, t->pn, t->gcov, t->pts64, t->means, t->vnorm, t->vicov, t->vcov,
+    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->lbox_h2, t->gbox_h2, t->cs_h, t->pts_h, t->j_h, t->cs_h2, t->pts_h2, t->j_h2, t->pts, t->pn, t->col, t->cint, t->gcov, t->pts64, t->means, t->vnorm, t->vicov, t->vcov,
                     t->st_mean, t->st_cov, t->st_norm, t->st_icov, t->st_counts, t->st_keys};
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     for (void *p : ptrs) pcr_persist_free(t->ctx, p);
@@ -511,6 +511,7 @@ extern "C" pcr_status pcr_target_set_normals(pcr_target *t, const float *normals
     CtxScope scope(ctx);
     DevBuf<float> d_nrm;
     PCR_TRY(upload<float>(ctx, normals, (size_t)t->n * 3, &d_nrm));
+    pcr_target_drop_color(t);       // (colour gradients lie in the tangent planes of the OLD normals)
     if (!t->pn) HIP_TRY(pcr_persist_alloc((void **)&t->pn, sizeof(PtN) * (size_t)(t->n ? t->n : 1)));
     PCR_TRY(pcr_permute_normals(ctx, d_nrm.p, t->n, t->pts, t->pn));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -158,6 +158,7 @@ extern "C" pcr_status pcr_target_estimate_normals(pcr_target *t, int k, int comp
     pcr_context *ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
+    pcr_target_drop_color(t);       // (colour gradients lie in the tangent planes of the OLD normals)
     if (!t->pn) HIP_TRY(pcr_persist_alloc((void **)&t->pn, sizeof(PtN) * (size_t)(t->n ? t->n : 1)));
     if (t->n > 0) {
         const Geom<float> &g = t->gf;

@@ -298,6 +298,9 @@ struct pcr_target {
     Geom<float> gf;
     PtF *pts = nullptr;        // cell-sorted (the NN search reads these 16-byte records)
     PtN *pn = nullptr;         // cell-sorted point + normal records (PlaneICP gathers these); NULL = no normals
+    float4 *col = nullptr;     // ColoredICP: cell-sorted 16-byte records {I, gx, gy, gz}: intensity and its gradient along the tangent
+                               // plane (color.hip); NULL = none.  Freed when the normals are replaced: the gradients belong to them
+    float *cint = nullptr;     // ... and the intensities alone, cell-sorted: what the gradient estimate reads of a point's neighbours
     float *gcov = nullptr;     // GICP: cell-sorted 64-byte records {xyz, orig, xx xy xz yy yz zz, padding} (gicp.hip: GicpRec, one
                                // line per correspondence); NULL = no covariances
     uint64_t serial = 0;
@@ -337,6 +340,8 @@ struct pcr_scan {
     float *cov = nullptr;                             // GICP: covariances in DEVICE order, 6 floats per point (xx xy xz yy yz zz); NULL = none
     float *nrm = nullptr;                             // SymmetricICP: normals in DEVICE order, 3 floats per point; NULL = none (symm.hip)
     double symm_min_cos = 0;                          // ... and the normal gate of the pass under way: pcr_pass_fn has no slot for it
+    float *inten = nullptr;                           // ColoredICP: intensities in DEVICE order, 1 float per point; NULL = none (color.hip)
+    double color_ag = 0, color_ac = 0;                // ... and sqrt(lambda), sqrt(1 - lambda) of the pass under way, as symm_min_cos
     // matched cell-sorted index per scan point (PCR_NONE = gated out), written by k_nn_scan and read
     // by the reduce kernel; kept across passes: the previous match is an exact upper bound for the
     // next search against the SAME target (nn_serial)
@@ -384,6 +389,12 @@ struct pcr_scan_batch {
 
 // ---- api.hip
 void pcr_target_release(pcr_target *t);      // frees a target and everything it owns (blocks back to its context's cache)
+
+// ColoredICP's records go with the normals they were estimated against (api.hip: set_normals; knn_normals.hip: estimate_normals)
+static inline void pcr_target_drop_color(pcr_target *t) {
+    pcr_persist_free(t->ctx, t->col); pcr_persist_free(t->ctx, t->cint);
+    t->col = nullptr; t->cint = nullptr;
+}
 
 // a temporary point index, released on scope exit (its blocks go back to the context's cache)
 struct TmpIndex {
