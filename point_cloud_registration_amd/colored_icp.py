@@ -16,8 +16,8 @@ import numpy as np
 from . import _capi
 from .gicp import _xform32
 from .kdtree import KDTree
-from .math_tools import plus, skew
-from .registration import Registration
+from .math_tools import skew
+from .registration import MatchPass
 
 
 def as_intensity(values, n, name):
@@ -31,21 +31,18 @@ def as_intensity(values, n, name):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class ColoredICP(Registration):
-    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_color_*)
+class ColoredICP(MatchPass):
+    _capi_linearize, _capi_align = staticmethod(_capi.color_linearize), staticmethod(_capi.color_align)
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, lambda_geometric=0.968, **kw):
-        if kw.get("devices") is not None or kw.get("comm") is not None:
-            raise ValueError("ColoredICP runs on one GPU of one process: not with comm= or devices=")
-        if not 1 <= int(k) <= 64:
-            raise ValueError("k must be in [1, 64]")
+        super().__init__(max_iter, max_dist, tol, k, **kw)
         if not 0.0 <= float(lambda_geometric) <= 1.0:             # (false for NaN)
             raise ValueError("lambda_geometric must be in [0, 1]")
-        super().__init__(max_iter=max_iter, tol=tol, **kw)
-        self.max_dist = max_dist
-        self.k = int(k)
         self.lambda_geometric = float(lambda_geometric)
         self._normal = self._intensity = self._gradient = None
+
+    def _pass_params(self):
+        return (self.lambda_geometric,)
 
     # -- target ----------------------------------------------------------------------------------
     def set_target(self, target, intensity, norm=None, gradient=None):
@@ -130,28 +127,7 @@ class ColoredICP(Registration):
         return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
 
     def align(self, source, source_intensity=None, init_T=np.eye(4), verbose=False):
-        if self.is_target_set() is False:
-            raise ValueError("Target is not set.")
-        scan = self._color_scan(source, source_intensity, fresh=True)
-        cur_T = np.array(init_T, dtype=np.float64)
-        if self._native_loop and not verbose:
-            T, iters, trace = _capi.color_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
-                                                self.lambda_geometric, self._flags, want_trace=True)
-            self.last_iterations = iters
-            if iters:
-                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
-            return T
-        it = 0
-        for it in range(self.max_iter):
-            H, g, e2 = self._linearize(cur_T, scan)
-            if verbose:
-                print(f"iter {it}, error {e2}")
-            dx = -np.linalg.solve(H, g)
-            if np.linalg.norm(dx) < self.tol:
-                break
-            cur_T = plus(cur_T, dx)
-        self.last_iterations = it + 1 if self.max_iter > 0 else 0
-        return cur_T
+        return self._align(self._color_scan(source, source_intensity, fresh=True), init_T, verbose)
 
     def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_intensity=None):
         """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
@@ -176,27 +152,4 @@ class ColoredICP(Registration):
                 H += wgt * np.outer(J, J)
                 g += wgt * J * r
                 e2 += wgt * r * r
-        return H, g, e2
-
-    # -- out of scope ----------------------------------------------------------------------------
-    def linearize(self, *a, **kw):
-        self._unsupported("linearize()")
-
-    def coreset(self, *a, **kw):
-        self._unsupported("coreset()")
-
-    def align_batch(self, *a, **kw):
-        self._unsupported("align_batch()")
-
-    def calc_H_g_e2_batch(self, *a, **kw):
-        self._unsupported("calc_H_g_e2_batch()")
-
-    # -- internals -------------------------------------------------------------------------------
-    def _unsupported(self, what):
-        raise NotImplementedError(f"ColoredICP does not support {what}")
-
-    def _linearize(self, cur_T, scan):
-        out = _capi.color_linearize(self._target, scan, cur_T, self._max_dist(), self.lambda_geometric, self._flags)
-        H, g, e2, cnt = _capi.unpack29(out)
-        self.last_correspondences = cnt
         return H, g, e2

@@ -784,15 +784,17 @@ extern "C" pcr_status pcr_scan_coreset(pcr_target *t, pcr_scan *s, int kind, con
 // ---- Gauss-Newton driver behind the boundary (registration.py:71-113) -------------------------
 // Default: the device-resident loop (pass.hip: pcr_run_align).  PCR_FLAG_HOST_LOOP keeps the
 // host-driven form (one pcr_linearize + host solve per iteration), the same arithmetic from gn_math.h.
-// `pass`: what one iteration evaluates (pcr_run_linearize; gicp.hip passes its own)
-pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
-                               double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
+// `pass`: what one iteration evaluates (pcr_run_linearize; gicp.hip, vgicp.hip, symm.hip, color.hip pass their own), `params`
+// what it takes beside the common arguments
+pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const void *params, const double T_init[16],
+                               int max_iter, double tol, double max_dist, unsigned flags, double T_out[16], int *iterations,
+                               double *trace_or_null) {
     double T[16];
     memcpy(T, T_init, sizeof T);
     int it = 0;
     for (; it < max_iter; ++it) {
         double o[29];
-        PCR_TRY(pass(t, s, kind, T, max_dist, flags, o));
+        PCR_TRY(pass(t, s, kind, T, max_dist, flags, params, o));
         if (trace_or_null) {
             memcpy(trace_or_null + (size_t)it * 45, T, 16 * sizeof(double));
             memcpy(trace_or_null + (size_t)it * 45 + 16, o, 29 * sizeof(double));
@@ -822,8 +824,11 @@ extern "C" pcr_status pcr_align(pcr_target *t, pcr_scan *s, int kind, const doub
     // way, but the step costs ~3 us on one GPU thread against < 1 us on the host)
     const bool use_comm = t->ctx->comm != nullptr && !(flags & PCR_FLAG_LOCAL_ONLY);
     const bool small_host = !(flags & PCR_FLAG_DEVICE_LOOP) && !use_comm && pcr_pass_is_fused(t->ctx, s);
-    if ((flags & PCR_FLAG_HOST_LOOP) || t->ctx->reuse == 2 || small_host)
-        return pcr_align_host_loop(pcr_run_linearize, t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    if ((flags & PCR_FLAG_HOST_LOOP) || t->ctx->reuse == 2 || small_host) {
+        const pcr_pass_fn pass = [](pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *,
+                                    double out[29]) { return pcr_run_linearize(t, s, kind, T, max_dist, flags, out); };
+        return pcr_align_host_loop(pass, t, s, kind, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    }
     return pcr_run_align(t, s, kind, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }
 

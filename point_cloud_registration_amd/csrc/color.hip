@@ -1,7 +1,7 @@
 // Colored ICP (Park, Zhou, Koltun: "Colored Point Cloud Registration Revisited", ICCV 2017; the form Open3D offers): PlaneICP's
 // row plus a second row per correspondence, the difference of the two points' intensities with the target's intensity carried
 // along its tangent plane by a per-point gradient.  Built BESIDE the hot path like symm.hip: its own kernels and entry points, no
-// new kind in the templated pass kernels (pass_device.h / dist_pass.h / knn_device.h are included; every other unit keeps its
+// new kind in the templated pass kernels (pass_device.h / match_pass.h / knn_device.h are included; every other unit keeps its
 // device code).  The definition is in include/pcr.h.
 //
 //   k_color_gather         caller-order intensities -> the index's cell-sorted order (pt_orig): pcr_target::cint
@@ -10,19 +10,20 @@
 //   k_color_gradient<REG>  one lane per target point, a knn_self finish functor: the least-squares gradient of the intensity over
 //                          the k nearest neighbours, in the tangent plane of the point's normal.  Reads the neighbours'
 //                          intensities from cint and writes {I, gx, gy, gz} into col -- a different array
-//   k_color_perm<TO_DEV>   one float per point, caller order <-> device order through pcr_scan::order
+//   k_color_perm<TO_DEV>   one float per point, caller order <-> device order through pcr_scan::order: ScanPayload<1>
+//                          (scan_payload.h)
 //   k_color_reduce         sits where k_symm_reduce sits: behind a full search (pass.hip: pcr_rows_search, ICP's) into a match
-//   k_color_fold           buffer of the call.  color_reduce is the three-phase loop of symm_reduce with an intensity where that
-//                          has a normal and one more 16-byte record per match; fold and the two launches are dist_fold /
-//                          dist_launch as they are.
+//   k_color_fold           buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold,
+//                          match_pass) with ColorArgs as its SIDE, COLOR_W points per lane in flight.
 //
 // Scan side: pcr_scan::inten, one float per point in device order.  Target side: the PtN records PlaneICP gathers and the
 // 16-byte colour records, 48 bytes per match from two arrays.
 #include <math.h>
 #include <string.h>
 
-#include "dist_pass.h"
 #include "knn_device.h"
+#include "match_pass.h"
+#include "scan_payload.h"
 
 extern __shared__ __attribute__((aligned(16))) char color_smem[];
 
@@ -115,11 +116,6 @@ static pcr_status check_color_target(const pcr_target *t) {
     if (t->is_voxel || !t->pn) { pcr_set_error("intensities belong to point targets with normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
     return PCR_OK;
 }
-static pcr_status check_finite(const float *v, size_t count, const char *what) {
-    for (size_t i = 0; i < count; ++i)
-        if (!isfinite(v[i])) { pcr_set_error("invalid argument: %s must be finite", what); return PCR_ERR_INVALID; }
-    return PCR_OK;
-}
 
 extern "C" pcr_status pcr_target_set_intensity(pcr_target *t, const float *intensity, const float *gradient_or_null) {
     PCR_REQUIRE(t && (intensity || t->n == 0), "NULL argument");
@@ -184,58 +180,70 @@ extern "C" pcr_status pcr_target_estimate_color_gradients(pcr_target *t, int k, 
 }
 
 // ---- intensities on a scan --------------------------------------------------------------------------------------------
-// TO_DEVICE: dev[i] = caller[order[i]]; else caller[order[i]] = dev[i] (order NULL: the same order)
+// caller order <-> device order through pcr_scan::order (scan_payload.h)
 template <bool TO_DEVICE>
 __global__ void __launch_bounds__(256) k_color_perm(const float *__restrict__ in, int64_t n, const uint32_t *__restrict__ order, float *out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const size_t c = order ? (size_t)order[i] : (size_t)i;
-    if (TO_DEVICE) out[i] = in[c];
-    else out[c] = in[i];
+    payload_perm<1, TO_DEVICE>(in, n, order, out);
 }
+static const ScanPayload<1> scan_inten{&pcr_scan::inten, k_color_perm<true>, k_color_perm<false>};
 
 extern "C" pcr_status pcr_scan_set_intensity(pcr_scan *s, const float *intensity) {
     PCR_REQUIRE(s && (intensity || s->n == 0), "NULL argument");
     PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
     // (checked before anything of the scan changes: a refused set leaves the old intensities)
     PCR_TRY(check_finite(intensity, (size_t)s->n, "intensities"));
-    pcr_context *ctx = s->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    if (!s->inten) HIP_TRY(pcr_scan_alloc(s, (void **)&s->inten, 4 * (size_t)(s->n ? s->n : 1)));
-    if (s->n == 0) return PCR_OK;
-    DevBuf<float> d;
-    HIP_TRY(d.alloc((size_t)s->n));
-    HIP_TRY(hipMemcpyAsync(d.p, intensity, 4 * (size_t)s->n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_color_perm<true>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)d.p, s->n, (const uint32_t *)s->order, s->inten);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    return scan_inten.set(s, intensity);
 }
 
 extern "C" pcr_status pcr_scan_get_intensity(pcr_scan *s, float *intensity) {
     PCR_REQUIRE(s && (intensity || s->n == 0), "NULL argument");
     if (!s->inten) { pcr_set_error("scan has no per-point intensities"); return PCR_ERR_NO_TARGET; }
     PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    pcr_context *ctx = s->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    if (s->n == 0) return PCR_OK;
-    DevBuf<float> d;
-    HIP_TRY(d.alloc((size_t)s->n));
-    hipLaunchKernelGGL(k_color_perm<false>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->inten, s->n, (const uint32_t *)s->order, d.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(intensity, d.p, 4 * (size_t)s->n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    return scan_inten.get(s, intensity);
 }
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------
+// A SIDE of match_pass.h.  Phase A carries the intensity of a scan point, phase B the PtN record of the match (two 16-byte
+// loads of one sector) and its colour record (one 16-byte load); add is the arithmetic of include/pcr.h: two rows per
+// correspondence, one count
 struct ColorArgs {
     const float *sint;       // scan intensities, device order
     const float4 *col;       // the target's colour records, cell-sorted
     double ag, ac;           // sqrt(lambda), sqrt(1 - lambda)
     double *rows;            // [gridDim.x][32]
+
+    typedef float Scan;
+    struct Match { float4 q, nq, cq; };
+    __device__ __forceinline__ void load(int64_t i, Scan &ip) const { ip = sint[i]; }
+    __device__ __forceinline__ void gather(const LinArgs &a, uint32_t j, Match &m) const {
+        const float4 *rec = reinterpret_cast<const float4 *>(a.pn + j);
+        m.q = rec[0]; m.nq = rec[1];
+        m.cq = col[j];
+    }
+    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                        const Scan &ip, const Match &m) const {
+        float dx, dy, dz;
+        if (!residual_f32<true>(a, m.q, tx, ty, tz, dx, dy, dz)) return;
+        const double n0 = m.nq.x, n1 = m.nq.y, n2 = m.nq.z;
+        const double g0 = m.cq.y, g1 = m.cq.z, g2 = m.cq.w;
+        const double d0 = dx, d1 = dy, d2 = dz;
+        const double px = x, py = y, pz = z;
+        double J[6];
+        // the geometric row: PlaneICP's, times sqrt(lambda)
+        double r = plane_row(P, px, py, pz, n0, n1, n2, d0, d1, d2, J);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) J[i] *= ag;
+        acc_rank1(acc, J, ag * r);
+        // the colour row: the gradient's tangent part in the place of the normal, times sqrt(1 - lambda)
+        const double gn = (g0 * n0 + g1 * n1) + g2 * n2;
+        const double m0 = g0 - gn * n0, m1 = g1 - gn * n1, m2 = g2 - gn * n2;
+        r = ((double)m.cq.x - (double)ip) + plane_row(P, px, py, pz, m0, m1, m2, d0, d1, d2, J);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) J[i] *= ac;
+        const double count = acc[28];                                // (acc_rank1 counts rows; out[28] counts correspondences)
+        acc_rank1(acc, J, ac * r);
+        acc[28] = count;
+    }
 };
 
 // points per lane in flight.  A point carries 5 registers through phase A and 12 more through phase B.  2: 126 registers, four
@@ -244,116 +252,44 @@ struct ColorArgs {
 #define COLOR_W 2
 #endif
 
-// The three-phase loop of symm_reduce (symm.hip) with an intensity where that carries a normal:
-//   phase A  index, coordinates and intensity of all W points.  A point past the end reads the lane's first point.
-//   phase B  the W PtN records, two 16-byte loads of one sector, and the W colour records, one 16-byte load each.  No match:
-//            record 0 through a select on the index.
-//   phase C  the arithmetic of include/pcr.h, in index order: two rows per correspondence, one count.
-template <int W>
-__device__ __forceinline__ void color_reduce(const LinArgs &a, const ColorArgs &ca) {
-    const PoseK &P = a.hp;                           // host-driven: the pose came by value
-    double acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < a.n; t0 += W * stride) {
-        uint32_t j[W];
-        float x[W], y[W], z[W], ip[W];
-        float4 q[W], nq[W], cq[W];
-        bool use[W];
-        // phase A
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const int64_t t = t0 + u * stride;
-            use[u] = t < a.n;
-            const int64_t i = use[u] ? t : t0;
-            j[u] = a.nn_j[i];
-            x[u] = a.sx[i]; y[u] = a.sy[i]; z[u] = a.sz[i];
-            ip[u] = ca.sint[i];
-        }
-        reduce_phase();
-#pragma unroll
-        for (int u = 0; u < W; ++u) reduce_pin(j[u]);
-        // phase B
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            use[u] = use[u] && j[u] != PCR_NONE;
-            const uint32_t jj = use[u] ? j[u] : 0u;
-            const float4 *rec = reinterpret_cast<const float4 *>(a.pn + jj);
-            q[u] = rec[0]; nq[u] = rec[1];
-            cq[u] = ca.col[jj];
-        }
-        reduce_phase();
-        // phase C
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (!use[u]) continue;
-            float tx, ty, tz, dx, dy, dz;
-            xform(P, x[u], y[u], z[u], tx, ty, tz);
-            if (!residual_f32<true>(a, q[u], tx, ty, tz, dx, dy, dz)) continue;
-            const double n0 = nq[u].x, n1 = nq[u].y, n2 = nq[u].z;
-            const double g0 = cq[u].y, g1 = cq[u].z, g2 = cq[u].w;
-            const double d0 = dx, d1 = dy, d2 = dz;
-            const double px = x[u], py = y[u], pz = z[u];
-            double J[6];
-            // the geometric row: PlaneICP's, times sqrt(lambda)
-            double r = plane_row(P, px, py, pz, n0, n1, n2, d0, d1, d2, J);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) J[i] *= ca.ag;
-            acc_rank1(acc, J, ca.ag * r);
-            // the colour row: the gradient's tangent part in the place of the normal, times sqrt(1 - lambda)
-            const double gn = (g0 * n0 + g1 * n1) + g2 * n2;
-            const double m0 = g0 - gn * n0, m1 = g1 - gn * n1, m2 = g2 - gn * n2;
-            r = ((double)cq[u].x - (double)ip[u]) + plane_row(P, px, py, pz, m0, m1, m2, d0, d1, d2, J);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) J[i] *= ca.ac;
-            const double count = acc[28];                            // (acc_rank1 counts rows; out[28] counts correspondences)
-            acc_rank1(acc, J, ca.ac * r);
-            acc[28] = count;
-        }
-    }
-    block_store_partials<false>(acc, ca.rows);
-}
+__global__ void __launch_bounds__(256) k_color_reduce(const LinArgs a, const ColorArgs ca) { match_reduce<COLOR_W>(a, ca); }
+__global__ void __launch_bounds__(64) k_color_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-__global__ void __launch_bounds__(256) k_color_reduce(const LinArgs a, const ColorArgs ca) { color_reduce<COLOR_W>(a, ca); }
-__global__ void __launch_bounds__(64) k_color_fold(const double *__restrict__ rows, int nb, double *out) { dist_fold(rows, nb, out); }
-
-// sqrt(lambda) and sqrt(1 - lambda), once, in double, onto the scan: pcr_pass_fn has no slot for them (as pcr_scan::symm_min_cos)
-static pcr_status set_lambda(pcr_scan *s, double lambda) {
-    PCR_REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda_geometric must be in [0, 1]");      // (false for NaN)
-    s->color_ag = sqrt(lambda);
-    s->color_ac = sqrt(1.0 - lambda);
-    return PCR_OK;
-}
-
-// search + the coloured pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records too)
-static pcr_status pcr_run_color(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
+// search + the coloured pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
+// too); params: two doubles, lambda_pair's sqrt(lambda) and sqrt(1 - lambda) of the call
+static pcr_status pcr_run_color(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
     if (t->is_voxel) { pcr_set_error("ColoredICP needs a point target"); return PCR_ERR_NO_TARGET; }
     if (!t->pn) { pcr_set_error("ColoredICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
     if (!t->col) { pcr_set_error("ColoredICP target has no colour records (pcr_target_set_intensity; replacing the normals frees them)"); return PCR_ERR_NO_TARGET; }
     if (!s->inten) { pcr_set_error("ColoredICP scan has no intensities (pcr_scan_set_intensity)"); return PCR_ERR_NO_TARGET; }
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_ICP, T, max_dist, flags, false));
-    for (int i = 0; i < 29; ++i) out[i] = 0.0;
-    if (s->n == 0) return PCR_OK;
-    const ColorArgs ca{s->inten, t->col, s->color_ag, s->color_ac, nullptr};
-    return dist_launch(t->ctx, "pcr:color_reduce", k_color_reduce, k_color_fold, a, ca, s->n, out);
+    const double *w = (const double *)params;
+    const ColorArgs ca{s->inten, t->col, w[0], w[1], nullptr};
+    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_reduce", k_color_reduce, k_color_fold, ca, out);
+}
+
+// sqrt(lambda) and sqrt(1 - lambda), once, in double
+static pcr_status lambda_pair(double lambda, double w[2]) {
+    PCR_REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda_geometric must be in [0, 1]");      // (false for NaN)
+    w[0] = sqrt(lambda);
+    w[1] = sqrt(1.0 - lambda);
+    return PCR_OK;
 }
 
 extern "C" pcr_status pcr_color_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                           unsigned flags, double out[29]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
-    PCR_TRY(set_lambda(s, lambda_geometric));
+    double w[2];
+    PCR_TRY(lambda_pair(lambda_geometric, w));
     CtxScope scope(t->ctx);
-    return pcr_run_color(t, s, PCR_ICP, T, max_dist, flags, out);
+    return pcr_run_color(t, s, PCR_ICP, T, max_dist, flags, w, out);
 }
 
 // the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_color_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                       double lambda_geometric, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    PCR_TRY(set_lambda(s, lambda_geometric));
+    double w[2];
+    PCR_TRY(lambda_pair(lambda_geometric, w));
     CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_color, t, s, PCR_ICP, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return pcr_align_host_loop(pcr_run_color, t, s, PCR_ICP, w, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }

@@ -8,9 +8,11 @@
 //                     usual "eigenvalues -> (eps, 1, 1)", which depends on the normal only -- or PCR_COV_RAW: cov itself.
 //                     Six floats (xx xy xz yy yz zz) per point, written through pt_orig: the INPUT order of the indexed cloud.
 //   k_gicp_reduce     sits where k_rows sits: behind a full search (pass.hip: pcr_rows_search) into a match buffer of the call.
-//   k_gicp_fold       The distribution pass of dist_pass.h (dist_reduce, dist_fold, dist_launch) with GicpArgs as its target
-//                     side, GICP_W points per lane in flight.  The correspondence is ICP's (xform, the matched PtF,
-//                     residual_f32<true>), the sums are acc_ndt's with M6 from icov_closed_form: nothing is restated here.
+//   k_gicp_fold       The pass over a match list of match_pass.h (match_reduce, match_fold, match_pass) with GicpArgs as its
+//                     SIDE -- the scan side and the sums are DistSide's (gicp_weight.h), shared with vgicp.hip -- GICP_W points
+//                     per lane in flight.  The correspondence is ICP's (xform, the matched PtF, residual_f32<true>), the sums
+//                     are acc_ndt's with M6 from icov_closed_form: nothing is restated here.
+//   k_gicp_scov_perm  the scan's covariances between caller and device order: ScanPayload<6> (scan_payload.h)
 //
 // Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
 // correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line); its
@@ -20,8 +22,10 @@
 #include <math.h>
 #include <string.h>
 
-#include "dist_pass.h"
+#include "gicp_weight.h"
 #include "knn_device.h"
+#include "match_pass.h"
+#include "scan_payload.h"
 
 extern __shared__ __attribute__((aligned(16))) char gicp_smem[];
 
@@ -86,17 +90,12 @@ __global__ void __launch_bounds__(256) k_gicp_tcov_out(const GicpRec *__restrict
     float *c = out + 6 * (size_t)pt_orig(p);
     c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y;
 }
-// scan: caller order <-> device order through pcr_scan::order (NULL: the same order); TO_DEVICE: dev[i] = caller[order[i]]
+// scan: caller order <-> device order through pcr_scan::order (scan_payload.h)
 template <bool TO_DEVICE>
 __global__ void __launch_bounds__(256) k_gicp_scov_perm(const float *__restrict__ in, int64_t n, const uint32_t *__restrict__ order, float *out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const size_t c = order ? (size_t)order[i] : (size_t)i;
-    const float *src = in + 6 * (TO_DEVICE ? c : (size_t)i);
-    float *dst = out + 6 * (TO_DEVICE ? (size_t)i : c);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) dst[a] = src[a];
+    payload_perm<6, TO_DEVICE>(in, n, order, out);
 }
+static const ScanPayload<6> scan_cov{&pcr_scan::cov, k_gicp_scov_perm<true>, k_gicp_scov_perm<false>};
 __global__ void __launch_bounds__(256) k_gicp_soa_to_aos(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
                                                          int64_t n, float *xyz) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -111,10 +110,6 @@ static pcr_status check_cov_args(int k, int mode, double eps) {
 
 static pcr_status target_cov_alloc(pcr_target *t) {
     if (!t->gcov) HIP_TRY(pcr_persist_alloc((void **)&t->gcov, sizeof(GicpRec) * (size_t)(t->n ? t->n : 1)));
-    return PCR_OK;
-}
-static pcr_status scan_cov_alloc(pcr_scan *s) {
-    if (!s->cov) HIP_TRY(pcr_scan_alloc(s, (void **)&s->cov, 24 * (size_t)(s->n ? s->n : 1)));
     return PCR_OK;
 }
 
@@ -140,7 +135,7 @@ extern "C" pcr_status pcr_target_estimate_covariances(pcr_target *t, int k, int 
 extern "C" pcr_status pcr_target_set_covariances(pcr_target *t, const float *cov6) {
     PCR_REQUIRE(t && (cov6 || t->n == 0), "NULL argument");
     PCR_REQUIRE(!t->is_voxel, "covariances belong to point targets");
-    PCR_TRY(check_cov_finite(cov6, 6 * (size_t)t->n));
+    PCR_TRY(check_finite(cov6, 6 * (size_t)t->n, "covariances"));
     pcr_context *ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     CtxScope scope(ctx);
@@ -171,20 +166,6 @@ extern "C" pcr_status pcr_target_get_covariances(pcr_target *t, float *cov6) {
     return PCR_OK;
 }
 
-// device-order covariances of a scan -> the caller's array
-static pcr_status scan_cov_read(pcr_scan *s, float *cov6) {
-    pcr_context *ctx = s->ctx;
-    if (s->n == 0) return PCR_OK;
-    DevBuf<float> d_cov;
-    HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
-    hipLaunchKernelGGL(k_gicp_scov_perm<false>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)s->cov, s->n, (const uint32_t *)s->order,
-                       d_cov.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cov6, d_cov.p, 24 * (size_t)s->n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
-}
-
 pcr_status pcr_scan_self_index(pcr_scan *s, TmpIndex *idx) {
     pcr_context *ctx = s->ctx;
     DevBuf<float> xyz;
@@ -203,71 +184,31 @@ extern "C" pcr_status pcr_scan_estimate_covariances(pcr_scan *s, int k, int mode
     PCR_REQUIRE(s, "NULL argument");
     PCR_TRY(check_cov_args(k, mode, eps));
     PCR_REQUIRE(!cov_out_or_null || pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    pcr_context *ctx = s->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    if (s->n == 0) return scan_cov_alloc(s);
-    // into the scan's array when it has one, else into a block the scan takes over only once the estimate is complete: a
-    // failure on the way must not leave a scan that "has covariances" holding uninitialised ones
-    float *dst = s->cov;
-    bool fresh = false;
-    if (!dst) {
-        HIP_TRY(pcr_scan_alloc(s, (void **)&dst, 24 * (size_t)s->n));
-        fresh = true;
-    }
-    struct Undo {
-        pcr_scan *s; float *p; bool armed;
-        ~Undo() { if (armed) { pcr_scan_free(s, p); } }
-    } undo{s, dst, fresh};
-    if (!fresh) { s->cov = nullptr; undo.armed = true; }      // (re-estimating: a failure leaves the scan without covariances)
-    {
-        TmpIndex idx;
-        PCR_TRY(pcr_scan_self_index(s, &idx));
-        // the index's input order is the scan's device order: pt_orig lands every point's six floats in the scan's array directly
-        PCR_TRY(gicp_estimate(ctx, idx.t->gf, idx.t->pts, idx.t->cell_start, s->n, k, mode, eps, dst));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    undo.armed = false;
-    s->cov = dst;
-    if (cov_out_or_null) return scan_cov_read(s, cov_out_or_null);
-    return PCR_OK;
+    return scan_cov.estimate(s, cov_out_or_null, [&](const pcr_target *idx, float *dst) {
+        return gicp_estimate(s->ctx, idx->gf, idx->pts, idx->cell_start, s->n, k, mode, eps, dst);
+    });
 }
 
 extern "C" pcr_status pcr_scan_set_covariances(pcr_scan *s, const float *cov6) {
     PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
     PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    PCR_TRY(check_cov_finite(cov6, 6 * (size_t)s->n));
-    pcr_context *ctx = s->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    CtxScope scope(ctx);
-    PCR_TRY(scan_cov_alloc(s));
-    if (s->n == 0) return PCR_OK;
-    DevBuf<float> d_cov;
-    HIP_TRY(d_cov.alloc(6 * (size_t)s->n));
-    HIP_TRY(hipMemcpyAsync(d_cov.p, cov6, 24 * (size_t)s->n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gicp_scov_perm<true>, grid_for(s->n, 256), dim3(256), 0, ctx->stream, (const float *)d_cov.p, s->n, (const uint32_t *)s->order,
-                       s->cov);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    PCR_TRY(check_finite(cov6, 6 * (size_t)s->n, "covariances"));
+    return scan_cov.set(s, cov6);
 }
 
 extern "C" pcr_status pcr_scan_get_covariances(pcr_scan *s, float *cov6) {
     PCR_REQUIRE(s && (cov6 || s->n == 0), "NULL argument");
     if (!s->cov) { pcr_set_error("scan has no per-point covariances"); return PCR_ERR_NO_TARGET; }
     PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    CtxScope scope(s->ctx);
-    return scan_cov_read(s, cov6);
+    return scan_cov.get(s, cov6);
 }
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------
-struct GicpArgs {
-    const float *scov;       // scan covariances, device order, 6 floats per point
+struct GicpArgs : DistSide<GicpArgs> {
     const GicpRec *trec;     // target records, cell-sorted: point + covariance in one line
     double *rows;            // [gridDim.x][32]
 
-    // dist_pass.h's view of a match: the record, whole (one line, three 16-byte loads)
+    // the match: the record, whole (one line, three 16-byte loads)
     struct Match { float4 p, c0, c1; };
     typedef float Res;
     __device__ __forceinline__ void gather(const LinArgs &, uint32_t j, Match &m) const {
@@ -289,26 +230,21 @@ struct GicpArgs {
 #define GICP_W 3
 #endif
 
-__global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) { dist_reduce<GICP_W>(a, ga); }
-__global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) { dist_fold(rows, nb, out); }
+__global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) { match_reduce<GICP_W>(a, ga); }
+__global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-// search + the distribution pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's
-static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
+// search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is ICP's
+static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
     if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_ICP, T, max_dist, flags, false));
-    for (int i = 0; i < 29; ++i) out[i] = 0.0;
-    if (s->n == 0) return PCR_OK;
-    const GicpArgs ga{s->cov, (const GicpRec *)t->gcov, nullptr};
-    return dist_launch(t->ctx, "pcr:gicp_reduce", k_gicp_reduce, k_gicp_fold, a, ga, s->n, out);
+    const GicpArgs ga{{s->cov}, (const GicpRec *)t->gcov, nullptr};
+    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_reduce", k_gicp_reduce, k_gicp_fold, ga, out);
 }
 
 extern "C" pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_run_gicp(t, s, PCR_ICP, T, max_dist, flags, out);
+    return pcr_run_gicp(t, s, PCR_ICP, T, max_dist, flags, nullptr, out);
 }
 
 // the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
@@ -316,5 +252,5 @@ extern "C" pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_
                                      unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_gicp, t, s, PCR_ICP, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return pcr_align_host_loop(pcr_run_gicp, t, s, PCR_ICP, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }

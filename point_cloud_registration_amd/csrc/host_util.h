@@ -4,6 +4,7 @@
 #pragma once
 
 #include <float.h>
+#include <math.h>
 #include <stdlib.h>
 
 #include "pcr_internal.h"
@@ -61,6 +62,14 @@ static inline pcr_status check_radius(Real r, const char *who) {
         pcr_set_error("invalid argument: %s needs a finite radius >= 0", who);
         return PCR_ERR_INVALID;
     }
+    return PCR_OK;
+}
+
+// every value of a caller's per-point payload (covariances, normals, intensities, gradients) is finite
+template <typename T>
+static inline pcr_status check_finite(const T *v, size_t count, const char *what) {
+    for (size_t i = 0; i < count; ++i)
+        if (!isfinite(v[i])) { pcr_set_error("invalid argument: %s must be finite", what); return PCR_ERR_INVALID; }
     return PCR_OK;
 }
 

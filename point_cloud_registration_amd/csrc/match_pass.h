@@ -1,25 +1,28 @@
-// The distribution pass behind GICP and VGICP, stated once: the three-phase reduce loop, the fold, and the host driver of
-// the two launches.  Included by gicp.hip and vgicp.hip only; each keeps its own __global__ one-liners (k_gicp_* / k_vgicp_*).
+// A pass over a match list, stated once: the three-phase reduce loop, the fold, the host driver of the two launches and the
+// scaffold of a pcr_pass_fn around them.  Behind GICP, VGICP, SymmetricICP and ColoredICP (gicp.hip, vgicp.hip, symm.hip,
+// color.hip); each keeps its own __global__ one-liners (k_gicp_* / k_vgicp_* / k_symm_* / k_color_*) and its *_W.
 //
-// A SIDE is the target side's kernel-argument struct (GicpArgs, VgicpArgs): scov, the target array, rows -- and
-//   Match, Res                what phase B gathers per correspondence, and the type of the residual (float / double)
+// A SIDE is a unit's kernel-argument struct (GicpArgs, VgicpArgs, SymmArgs, ColorArgs): its arrays, its parameters, rows -- and
+//   Scan                      what phase A carries per scan point beside index and coordinates
+//   load(i, Scan&)            the loads of scan point i (device order); nothing else
+//   Match                     what phase B carries per correspondence
 //   gather(a, j, Match&)      the loads of one match at cell-sorted index j; nothing else
-//   residual(a, m, t.., d..)  residual_f32<true> / residual_f64<true> on the gathered match: residual and gate
-//   weight(P, cp, m, m6)      gicp_weight with the match's covariance
+//   add(acc, a, P, x, y, z, tx, ty, tz, scan, match)
+//                             residual, gate and sums of one correspondence; (tx, ty, tz) = xform(P, x, y, z)
 #pragma once
 
-#include "gicp_weight.h"
 #include "host_util.h"
+#include "pass_device.h"
 
 // W points per lane in flight, the phases of reduce_stream (pass_device.h):
-//   phase A  index, coordinates and scan covariance of all W points.  A point past the end reads the lane's first point.
+//   phase A  index, coordinates and Scan of all W points.  A point past the end reads the lane's first point.
 //   phase B  the W matches.  No match: element 0 through a select on the index -- always there -- and skipped in phase C;
 //            no branch between the gathers.
-//   phase C  residual, gate, weight, sums (acc_ndt with M6) -- in index order.
+//   phase C  SIDE::add -- in index order.
 // Fold: wave shuffles in a fixed order, LDS across the waves in wave order, ONE row of 32 doubles per block with plain
 // stores (block_store_partials).  No tickets, no atomics, no in-launch hand-off.
 template <int W, typename SIDE>
-__device__ __forceinline__ void dist_reduce(const LinArgs &a, const SIDE &sd) {
+__device__ __forceinline__ void match_reduce(const LinArgs &a, const SIDE &sd) {
     const PoseK &P = a.hp;                           // host-driven: the pose came by value
     double acc[32];
 #pragma unroll
@@ -28,7 +31,7 @@ __device__ __forceinline__ void dist_reduce(const LinArgs &a, const SIDE &sd) {
     for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < a.n; t0 += W * stride) {
         uint32_t j[W];
         float x[W], y[W], z[W];
-        float2 cp[W][3];
+        typename SIDE::Scan sc[W];
         typename SIDE::Match m[W];
         bool use[W];
         // phase A
@@ -39,8 +42,7 @@ __device__ __forceinline__ void dist_reduce(const LinArgs &a, const SIDE &sd) {
             const int64_t i = use[u] ? t : t0;
             j[u] = a.nn_j[i];
             x[u] = a.sx[i]; y[u] = a.sy[i]; z[u] = a.sz[i];
-            const float2 *c = reinterpret_cast<const float2 *>(sd.scov + 6 * i);
-            cp[u][0] = c[0]; cp[u][1] = c[1]; cp[u][2] = c[2];
+            sd.load(i, sc[u]);
         }
         reduce_phase();
 #pragma unroll
@@ -57,13 +59,8 @@ __device__ __forceinline__ void dist_reduce(const LinArgs &a, const SIDE &sd) {
         for (int u = 0; u < W; ++u) {
             if (!use[u]) continue;
             float tx, ty, tz;
-            typename SIDE::Res dx, dy, dz;
             xform(P, x[u], y[u], z[u], tx, ty, tz);
-            if (!sd.residual(a, m[u], tx, ty, tz, dx, dy, dz)) continue;
-            const float cpv[6] = {cp[u][0].x, cp[u][0].y, cp[u][1].x, cp[u][1].y, cp[u][2].x, cp[u][2].y};
-            double m6[6];
-            sd.weight(P, cpv, m[u], m6);
-            acc_ndt(acc, P, (double)x[u], (double)y[u], (double)z[u], m6, (double)dx, (double)dy, (double)dz);
+            sd.add(acc, a, P, x[u], y[u], z[u], tx, ty, tz, sc[u], m[u]);
         }
     }
     block_store_partials<false>(acc, sd.rows);
@@ -71,7 +68,7 @@ __device__ __forceinline__ void dist_reduce(const LinArgs &a, const SIDE &sd) {
 
 // one block: thread e < 29 adds rows 0 .. nb-1 in order.  The kernel boundary is the only ordering between the two launches;
 // the grid depends on n and the device only, so two calls return the same bits.
-__device__ __forceinline__ void dist_fold(const double *__restrict__ rows, int nb, double *out) {
+__device__ __forceinline__ void match_fold(const double *__restrict__ rows, int nb, double *out) {
     const int e = threadIdx.x;
     if (e >= 29) return;
     double s = 0.0;
@@ -80,10 +77,10 @@ __device__ __forceinline__ void dist_fold(const double *__restrict__ rows, int n
 }
 
 // reduce + fold + 29 doubles back behind a search into `a`: one stream synchronisation, device blocks from the context's
-// block cache.  sd comes with scov and the target array set.
+// block cache.  sd comes with everything but rows set.
 template <typename SIDE>
-static pcr_status dist_launch(pcr_context *ctx, const char *range_name, void (*reduce)(const LinArgs, const SIDE),
-                              void (*fold)(const double *, int, double *), const LinArgs &a, SIDE sd, int64_t n, double out[29]) {
+static pcr_status match_launch(pcr_context *ctx, const char *range_name, void (*reduce)(const LinArgs, const SIDE),
+                               void (*fold)(const double *, int, double *), const LinArgs &a, SIDE sd, int64_t n, double out[29]) {
     const int nb = choose_blocks(ctx, n);            // n and the device only
     DevBuf<double> rows, sums;
     HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
@@ -99,15 +96,16 @@ static pcr_status dist_launch(pcr_context *ctx, const char *range_name, void (*r
     return PCR_OK;
 }
 
-// ---- covariance arguments ------------------------------------------------------------------------------------------------
-static pcr_status check_cov_mode(int mode, double eps) {
-    PCR_REQUIRE(mode == PCR_COV_PLANE || mode == PCR_COV_RAW, "mode must be PCR_COV_PLANE or PCR_COV_RAW");
-    PCR_REQUIRE(mode == PCR_COV_RAW || (eps > 0.0 && eps <= 1.0), "eps must be in (0, 1]");
-    return PCR_OK;
-}
-template <typename T>
-static pcr_status check_cov_finite(const T *v, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-        if (!isfinite(v[i])) { pcr_set_error("invalid argument: covariances must be finite"); return PCR_ERR_INVALID; }
-    return PCR_OK;
+// What a pcr_pass_fn does once the unit has checked its payloads: kind's full search (pass.hip: pcr_rows_search) into a match
+// buffer of the call, 29 zeros, and -- for a scan with points -- match_launch
+template <typename SIDE>
+static pcr_status match_pass(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const char *range_name,
+                             void (*reduce)(const LinArgs, const SIDE), void (*fold)(const double *, int, double *), const SIDE &sd,
+                             double out[29]) {
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, kind, T, max_dist, flags, false));
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    if (s->n == 0) return PCR_OK;
+    return match_launch(t->ctx, range_name, reduce, fold, a, sd, s->n, out);
 }

@@ -339,9 +339,7 @@ struct pcr_scan {
     uint32_t *order = nullptr;                        // PCR_FLAG_KEEP_ORDER on a sorted scan: device position -> caller index
     float *cov = nullptr;                             // GICP: covariances in DEVICE order, 6 floats per point (xx xy xz yy yz zz); NULL = none
     float *nrm = nullptr;                             // SymmetricICP: normals in DEVICE order, 3 floats per point; NULL = none (symm.hip)
-    double symm_min_cos = 0;                          // ... and the normal gate of the pass under way: pcr_pass_fn has no slot for it
     float *inten = nullptr;                           // ColoredICP: intensities in DEVICE order, 1 float per point; NULL = none (color.hip)
-    double color_ag = 0, color_ac = 0;                // ... and sqrt(lambda), sqrt(1 - lambda) of the pass under way, as symm_min_cos
     // matched cell-sorted index per scan point (PCR_NONE = gated out), written by k_nn_scan and read
     // by the reduce kernel; kept across passes: the previous match is an exact upper bound for the
     // next search against the SAME target (nn_serial)
@@ -453,10 +451,14 @@ pcr_status pcr_terms_coreset(pcr_context *ctx, const double *d_P, int64_t stride
 struct LinArgs;
 pcr_status pcr_rows_search(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
                            unsigned flags, bool caller_order);
-// ---- api.hip: the host-driven Gauss-Newton loop (align_host_loop of pcr_align) over a pass of the caller's choice
-typedef pcr_status (*pcr_pass_fn)(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, double out[29]);
-pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const double T_init[16], int max_iter, double tol,
-                               double max_dist, unsigned flags, double T_out[16], int *iterations, double *trace_or_null);
+// ---- api.hip: the host-driven Gauss-Newton loop (align_host_loop of pcr_align) over a pass of the caller's choice.  `params`:
+// what the pass takes beside the common arguments (symm.hip: min_cos; color.hip: the two weights; else NULL), handed through
+// to every iteration: a parameter of the call travels with the call
+typedef pcr_status (*pcr_pass_fn)(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                  const void *params, double out[29]);
+pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const void *params, const double T_init[16],
+                               int max_iter, double tol, double max_dist, unsigned flags, double T_out[16], int *iterations,
+                               double *trace_or_null);
 bool pcr_pass_is_fused(const pcr_context *ctx, const pcr_scan *s);      // this scan runs the one-kernel (small-scan) form of a pass
 
 // ---- roctx ranges around the hot-path launches (PCR_ROCTX=1; libroctx64 bound with dlopen, so the

@@ -2,16 +2,16 @@
 // every correspondence -- found and gated exactly as NDT / VPlaneICP find and gate it -- is weighed with
 // M = (Cv + R Cp R^T)^-1, Cv the float64 covariance of the matched voxel, Cp the float32 covariance of the scan point (GICP's:
 // gicp.hip puts them on a scan).  Built BESIDE the hot path like gicp.hip: its own kernels and entry points, no new kind in the
-// templated pass kernels (pass_device.h / dist_pass.h are included; kernels.hip, rows.hip, gicp.hip, seam64.hip do not change).
+// templated pass kernels (pass_device.h / match_pass.h are included; kernels.hip, rows.hip, gicp.hip, seam64.hip do not change).
 //
 //   k_vgicp_plane_cov  one thread per kept voxel, key order: C = I - (1 - eps) n n^T from the voxel's normal (st_norm), float64,
 //                      six values xx xy xz yy yz zz.  Eigenvalues (eps, 1, 1); the sign of n cancels.
 //   k_vgicp_cov_out    cell-sorted rows back into key order (the inverse of pcr_permute_rows_f64), for the read-back.
 //   k_vgicp_reduce     sits where k_gicp_reduce sits: behind a full float64 centroid search (pass.hip: pcr_rows_search with
-//   k_vgicp_fold       PCR_VPLANE, which needs the voxel normals only) into a match buffer of the call.  The distribution pass
-//                      of dist_pass.h (dist_reduce, dist_fold, dist_launch) with VgicpArgs as its target side, VGICP_W points
-//                      per lane in flight: residual_f64<true> on the gathered centroid, gicp_weight, acc_ndt -- nothing is
-//                      restated here.
+//   k_vgicp_fold       PCR_VPLANE, which needs the voxel normals only) into a match buffer of the call.  The pass over a match
+//                      list of match_pass.h (match_reduce, match_fold, match_pass) with VgicpArgs as its SIDE -- the scan side
+//                      and the sums are DistSide's (gicp_weight.h), shared with gicp.hip -- VGICP_W points per lane in flight:
+//                      residual_f64<true> on the gathered centroid, gicp_weight, acc_ndt -- nothing is restated here.
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -19,7 +19,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "dist_pass.h"
+#include "gicp_weight.h"
+#include "match_pass.h"
 
 // ---- voxel covariances --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_vgicp_plane_cov(const double *__restrict__ norm, int64_t n, double eps, double *out) {
@@ -47,7 +48,7 @@ extern "C" pcr_status pcr_target_voxels_set_covariances(pcr_target *t, int mode,
         if (mode == PCR_COV_RAW && !t->st_cov) { pcr_set_error("voxel target does not hold 'cov'"); return PCR_ERR_NO_TARGET; }
     } else {
         // (checked before anything of the target changes: a refused set leaves the old covariances)
-        PCR_TRY(check_cov_finite(cov6_or_null, 6 * (size_t)t->n));
+        PCR_TRY(check_finite(cov6_or_null, 6 * (size_t)t->n, "covariances"));
     }
     pcr_context *ctx = t->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -97,12 +98,11 @@ extern "C" pcr_status pcr_target_voxels_get_covariances(pcr_target *t, double *c
 }
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------
-struct VgicpArgs {
-    const float *scov;       // scan covariances, device order, 6 floats per point
+struct VgicpArgs : DistSide<VgicpArgs> {
     const double *vcov;      // voxel covariances, cell-sorted, 6 doubles per voxel (16-byte aligned rows)
     double *rows;            // [gridDim.x][32]
 
-    // dist_pass.h's view of a match: the centroid (32 bytes of `means`, as halves) and the voxel covariance (48 bytes of vcov)
+    // the match: the centroid (32 bytes of `means`, as halves) and the voxel covariance (48 bytes of vcov)
     struct Match { double2 m0, m1, cv[3]; };
     typedef double Res;
     __device__ __forceinline__ void gather(const LinArgs &a, uint32_t j, Match &m) const {
@@ -126,11 +126,11 @@ struct VgicpArgs {
 #define VGICP_W 2
 #endif
 
-__global__ void __launch_bounds__(256) k_vgicp_reduce(const LinArgs a, const VgicpArgs va) { dist_reduce<VGICP_W>(a, va); }
-__global__ void __launch_bounds__(64) k_vgicp_fold(const double *__restrict__ rows, int nb, double *out) { dist_fold(rows, nb, out); }
+__global__ void __launch_bounds__(256) k_vgicp_reduce(const LinArgs a, const VgicpArgs va) { match_reduce<VGICP_W>(a, va); }
+__global__ void __launch_bounds__(64) k_vgicp_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-// centroid search + the distribution pass.  A pcr_pass_fn: `kind` is not read, the search is VPlaneICP's
-static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, double out[29]) {
+// centroid search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is VPlaneICP's
+static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
     if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
     if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
@@ -142,18 +142,14 @@ static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[
         if (ctx->comm != nullptr) { pcr_set_error("VGICP passes are not available on a context with a communicator attached"); return PCR_ERR_UNSUPPORTED; }
         return PCR_OK;
     }
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, PCR_VPLANE, T, max_dist, flags, false));
-    if (s->n == 0) return PCR_OK;
-    const VgicpArgs va{s->cov, t->vcov, nullptr};
-    return dist_launch(ctx, "pcr:vgicp_reduce", k_vgicp_reduce, k_vgicp_fold, a, va, s->n, out);
+    const VgicpArgs va{{s->cov}, t->vcov, nullptr};
+    return match_pass(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_reduce", k_vgicp_reduce, k_vgicp_fold, va, out);
 }
 
 extern "C" pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, out);
+    return pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, nullptr, out);
 }
 
 // the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
@@ -161,5 +157,5 @@ extern "C" pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T
                                       unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_vgicp, t, s, PCR_VPLANE, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return pcr_align_host_loop(pcr_run_vgicp, t, s, PCR_VPLANE, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _capi
 from .kdtree import KDTree
-from .math_tools import plus, skew
-from .registration import Registration
+from .math_tools import skew
+from .registration import MatchPass
 
 _MODES = {"plane": _capi.COV_PLANE, "raw": _capi.COV_RAW}
 
@@ -53,22 +53,14 @@ class ScanCovariances:
         return scan
 
 
-class DistributionPass(ScanCovariances, Registration):
+class DistributionPass(ScanCovariances, MatchPass):
     """The distribution-to-distribution pass behind ``GICP`` and ``VGICP``.  A subclass supplies the target side:
     ``set_target``, ``covariance``, its pair of ``_capi`` entry points and ``_match`` for the per-point loop."""
-    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_gicp_* / pcr_vgicp_*)
-    _capi_linearize = _capi_align = None
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
-        if kw.get("devices") is not None or kw.get("comm") is not None:
-            raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
+        super().__init__(max_iter, max_dist, tol, k, **kw)
         if regularization not in _MODES:
             raise ValueError(f"regularization must be one of {sorted(_MODES)}, not {regularization!r}")
-        if not 1 <= int(k) <= 64:
-            raise ValueError("k must be in [1, 64]")
-        super().__init__(max_iter=max_iter, tol=tol, **kw)
-        self.max_dist = max_dist
-        self.k = int(k)
         self.eps = float(eps)
         self.regularization = regularization
         self._covariance = None
@@ -83,28 +75,7 @@ class DistributionPass(ScanCovariances, Registration):
         return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
 
     def align(self, source, init_T=np.eye(4), verbose=False, source_cov=None):
-        if self.is_target_set() is False:
-            raise ValueError("Target is not set.")
-        scan = self._gicp_scan(source, source_cov, fresh=True)
-        cur_T = np.array(init_T, dtype=np.float64)
-        if self._native_loop and not verbose:
-            T, iters, trace = self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
-                                               self._flags, want_trace=True)
-            self.last_iterations = iters
-            if iters:
-                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
-            return T
-        it = 0
-        for it in range(self.max_iter):
-            H, g, e2 = self._linearize(cur_T, scan)
-            if verbose:
-                print(f"iter {it}, error {e2}")
-            dx = -np.linalg.solve(H, g)
-            if np.linalg.norm(dx) < self.tol:
-                break
-            cur_T = plus(cur_T, dx)
-        self.last_iterations = it + 1 if self.max_iter > 0 else 0
-        return cur_T
+        return self._align(self._gicp_scan(source, source_cov, fresh=True), init_T, verbose)
 
     def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_cov=None):
         """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
@@ -128,29 +99,6 @@ class DistributionPass(ScanCovariances, Registration):
         """(scan points that pass the gate, the target element each is matched to, its float64 residual) for the
         transformed float32 scan."""
         raise NotImplementedError
-
-    # -- out of scope ----------------------------------------------------------------------------
-    def linearize(self, *a, **kw):
-        self._unsupported("linearize()")
-
-    def coreset(self, *a, **kw):
-        self._unsupported("coreset()")
-
-    def align_batch(self, *a, **kw):
-        self._unsupported("align_batch()")
-
-    def calc_H_g_e2_batch(self, *a, **kw):
-        self._unsupported("calc_H_g_e2_batch()")
-
-    # -- internals -------------------------------------------------------------------------------
-    def _unsupported(self, what):
-        raise NotImplementedError(f"{type(self).__name__} does not support {what}")
-
-    def _linearize(self, cur_T, scan):
-        out = self._capi_linearize(self._target, scan, cur_T, self._max_dist(), self._flags)
-        H, g, e2, cnt = _capi.unpack29(out)
-        self.last_correspondences = cnt
-        return H, g, e2
 
 
 class GICP(DistributionPass):

@@ -202,10 +202,13 @@ class Registration:
         if self.is_target_set() is False:
             raise ValueError("Target is not set.")
         scan = self._scan_for(source, fresh=True)     # the reference copies the scan per call
+        return self._align(scan, init_T, verbose)
+
+    def _align(self, scan, init_T, verbose):
+        """``align`` once the scan is on the device: the native loop, or the reference's Python loop over ``_linearize``."""
         cur_T = np.array(init_T, dtype=np.float64)
         if self._native_loop and not verbose and not self._needs_host_reduce():
-            T, iters, trace = _capi.align(self._target, scan, self.KIND, cur_T, self.max_iter, self.tol,
-                                          self._max_dist(), self._call_flags(), want_trace=True)
+            T, iters, trace = self._native_align(scan, cur_T)
             self.last_iterations = iters
             if iters:
                 self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
@@ -336,8 +339,16 @@ class Registration:
         self._scan_key = key
         return self._scan
 
+    # the two entry points of a pass: its 29 sums at cur_T, and its whole Gauss-Newton loop -> (T, iterations, trace)
+    def _native_linearize(self, scan, cur_T):
+        return _capi.linearize(self._target, scan, self.KIND, cur_T, self._max_dist(), self._call_flags())
+
+    def _native_align(self, scan, cur_T):
+        return _capi.align(self._target, scan, self.KIND, cur_T, self.max_iter, self.tol, self._max_dist(), self._call_flags(),
+                           want_trace=True)
+
     def _linearize(self, cur_T, scan):
-        out = _capi.linearize(self._target, scan, self.KIND, cur_T, self._max_dist(), self._call_flags())
+        out = self._native_linearize(scan, cur_T)
         if self._needs_host_reduce():
             out = self._comm.allreduce(out)
         H, g, e2, cnt = _capi.unpack29(out)
@@ -349,3 +360,47 @@ class Registration:
             self._target.close()
         self._target = handle
         self._is_target_set = True
+
+
+class MatchPass(Registration):
+    """The driver of the aligners whose pass has entry points of its own (``GICP``, ``VGICP``, ``SymmetricICP``,
+    ``ColoredICP``): one GPU of one process, ``k`` neighbours for what they estimate.  A subclass supplies its pair of ``_capi``
+    entry points and ``_pass_params``, what they take between ``max_dist`` and the flags; it keeps its own ``set_target``,
+    scan preparation and ``calc_H_g_e2_no_parallel_ver``."""
+    KIND = None           # no kind of pcr_linearize
+    _capi_linearize = _capi_align = None
+
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, **kw):
+        if kw.get("devices") is not None or kw.get("comm") is not None:
+            raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
+        if not 1 <= int(k) <= 64:
+            raise ValueError("k must be in [1, 64]")
+        super().__init__(max_iter=max_iter, tol=tol, **kw)
+        self.max_dist = max_dist
+        self.k = int(k)
+
+    def _pass_params(self):
+        return ()
+
+    def _native_linearize(self, scan, cur_T):
+        return self._capi_linearize(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), self._flags)
+
+    def _native_align(self, scan, cur_T):
+        return self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
+                                self._flags, want_trace=True)
+
+    # -- out of scope ----------------------------------------------------------------------------
+    def _unsupported(self, what):
+        raise NotImplementedError(f"{type(self).__name__} does not support {what}")
+
+    def linearize(self, *a, **kw):
+        self._unsupported("linearize()")
+
+    def coreset(self, *a, **kw):
+        self._unsupported("coreset()")
+
+    def align_batch(self, *a, **kw):
+        self._unsupported("align_batch()")
+
+    def calc_H_g_e2_batch(self, *a, **kw):
+        self._unsupported("calc_H_g_e2_batch()")

@@ -15,25 +15,22 @@ import numpy as np
 from . import _capi
 from .gicp import _xform32
 from .kdtree import KDTree
-from .math_tools import plus, skew
-from .registration import Registration
+from .math_tools import skew
+from .registration import MatchPass
 
 
-class SymmetricICP(Registration):
-    KIND = None           # no kind of pcr_linearize: the pass has entry points of its own (pcr_symm_*)
+class SymmetricICP(MatchPass):
+    _capi_linearize, _capi_align = staticmethod(_capi.symm_linearize), staticmethod(_capi.symm_align)
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, min_normal_cos=0.0, **kw):
-        if kw.get("devices") is not None or kw.get("comm") is not None:
-            raise ValueError("SymmetricICP runs on one GPU of one process: not with comm= or devices=")
-        if not 1 <= int(k) <= 64:
-            raise ValueError("k must be in [1, 64]")
+        super().__init__(max_iter, max_dist, tol, k, **kw)
         if not 0.0 <= float(min_normal_cos) <= 1.0:             # (false for NaN)
             raise ValueError("min_normal_cos must be in [0, 1]")
-        super().__init__(max_iter=max_iter, tol=tol, **kw)
-        self.max_dist = max_dist
-        self.k = int(k)
         self.min_normal_cos = float(min_normal_cos)
         self._normal = None
+
+    def _pass_params(self):
+        return (self.min_normal_cos,)
 
     # -- target ----------------------------------------------------------------------------------
     def set_target(self, target, norm=None):
@@ -105,28 +102,7 @@ class SymmetricICP(Registration):
         return self._linearize(np.asarray(cur_T, dtype=np.float64), scan)
 
     def align(self, source, init_T=np.eye(4), verbose=False, source_normals=None):
-        if self.is_target_set() is False:
-            raise ValueError("Target is not set.")
-        scan = self._symm_scan(source, source_normals, fresh=True)
-        cur_T = np.array(init_T, dtype=np.float64)
-        if self._native_loop and not verbose:
-            T, iters, trace = _capi.symm_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
-                                               self.min_normal_cos, self._flags, want_trace=True)
-            self.last_iterations = iters
-            if iters:
-                self.last_correspondences = int(round(trace[iters - 1, 16 + 28]))
-            return T
-        it = 0
-        for it in range(self.max_iter):
-            H, g, e2 = self._linearize(cur_T, scan)
-            if verbose:
-                print(f"iter {it}, error {e2}")
-            dx = -np.linalg.solve(H, g)
-            if np.linalg.norm(dx) < self.tol:
-                break
-            cur_T = plus(cur_T, dx)
-        self.last_iterations = it + 1 if self.max_iter > 0 else 0
-        return cur_T
+        return self._align(self._symm_scan(source, source_normals, fresh=True), init_T, verbose)
 
     def calc_H_g_e2_no_parallel_ver(self, cur_T, source, source_normals=None):
         """Per-point loop of the same sums, for reading and for tests: host Python over the GPU's correspondences
@@ -152,27 +128,4 @@ class SymmetricICP(Registration):
             H += np.outer(J, J)
             g += J * r
             e2 += r * r
-        return H, g, e2
-
-    # -- out of scope ----------------------------------------------------------------------------
-    def linearize(self, *a, **kw):
-        self._unsupported("linearize()")
-
-    def coreset(self, *a, **kw):
-        self._unsupported("coreset()")
-
-    def align_batch(self, *a, **kw):
-        self._unsupported("align_batch()")
-
-    def calc_H_g_e2_batch(self, *a, **kw):
-        self._unsupported("calc_H_g_e2_batch()")
-
-    # -- internals -------------------------------------------------------------------------------
-    def _unsupported(self, what):
-        raise NotImplementedError(f"SymmetricICP does not support {what}")
-
-    def _linearize(self, cur_T, scan):
-        out = _capi.symm_linearize(self._target, scan, cur_T, self._max_dist(), self.min_normal_cos, self._flags)
-        H, g, e2, cnt = _capi.unpack29(out)
-        self.last_correspondences = cnt
         return H, g, e2

@@ -1,4 +1,4 @@
-"""Cases of the distribution pass behind GICP and VGICP (csrc/dist_pass.h), shared by tests/test_dist_cases.py and
+"""Cases of the distribution pass behind GICP and VGICP (csrc/match_pass.h), shared by tests/test_dist_cases.py and
 tests/test_gpu_dist_pass.py: the gate boundary and the pose space of tests/pass_cases.py with covariances on both sides, the
 det == 0 rule of the weight, and scans large enough for every slot of a lane and a second trip of its loop to carry live
 points.  Plain NumPy plus the CPU oracle, deterministic, no GPU; every cloud but the base scans comes from pass_cases.py.
@@ -115,7 +115,7 @@ def degenerate_pair(n_scan, n_target, which):
 
 # ----------------------------------------------------------------------------- live slots, second trip
 def stride_points(cus):
-    """Points one trip of dist_reduce hands to slot 0 of every lane: gridDim.x * 256 with gridDim.x = 8 * CUs, the cap of
+    """Points one trip of match_reduce hands to slot 0 of every lane: gridDim.x * 256 with gridDim.x = 8 * CUs, the cap of
     blocks_wanted (pass.hip), once the scan has that many points; the context's max_blocks = 16 * CUs does not bind."""
     return 8 * int(cus) * 256
 

@@ -96,6 +96,24 @@ def unit_normals(n, seed=0):
     return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
 
 
+CALL_MAX_DIST = 1.0
+
+
+def call_case(g2):
+    """The small pair of the "the call's parameter decides" tests: the first 300 scan points of g2 against its first 400
+    targets at g2's pose, correspondences by brute force in float32 as the kernels form them
+    -> (target, normals, scan, tp, j, mask).  216 pairs lie inside CALL_MAX_DIST, none within 1e-3 of it, and every nearest
+    neighbour leads its runner-up by more than 1e-4 of the squared distance, so masks and indices compare exactly."""
+    tgt, nq, src = (np.ascontiguousarray(g2[k][:n]) for k, n in (("target", 400), ("plane_normals", 400), ("source", 300)))
+    tp = xform32(g2["T"], src)
+    dd = tp[:, None, :] - tgt[None, :, :]                                       # float32
+    d2 = np.sort((dd[:, :, 0] * dd[:, :, 0] + dd[:, :, 1] * dd[:, :, 1]) + dd[:, :, 2] * dd[:, :, 2], axis=1)
+    dist = np.sqrt(d2[:, 0])
+    assert np.min(np.abs(dist - CALL_MAX_DIST)) > 1e-3 and np.min((d2[:, 1] - d2[:, 0]) / d2[:, 1]) > 1e-4
+    j = np.argmin(np.sum(dd.astype(np.float64) ** 2, axis=2), axis=1)
+    return tgt, nq, src, tp, j, dist < np.float32(CALL_MAX_DIST)
+
+
 def plane_case(g2):
     """The PlaneICP property on g2: scan normals float32(R^T n_q[nn_idx]) with every second one negated, so that R n_p = +-n_q
     up to float32 rounding and the pass is PlaneICP's -> (n_p, n_q of every target point)."""

@@ -554,7 +554,34 @@ def test_neighbours_undisturbed(capi, ctx, g2):
             assert g1[28] == o1[28] == s1[28] == c1[28] == 1823
 
 
-# ----------------------------------------------------------------------------- 12. device memory
+# ----------------------------------------------------------------------------- 12. the call's parameter decides
+def test_lambda_belongs_to_the_call(capi, ctx, g2):
+    """Three calls over ONE uploaded scan, lambda = 1, 0.5, 1: the first and the third return the same bits -- PlaneICP's sums
+    on the same pair, within the sum bound of test_lambda_one_is_plane_icp -- and the second other sums over the same pairs:
+    the weights are parameters of the call, nothing an earlier call leaves on the scan."""
+    import point_cloud_registration_amd as pcr
+    import symm_cases as sc
+    tgt, nq, src, tp, j, mask = sc.call_case(g2)
+    T, md = g2["T"], sc.CALL_MAX_DIST
+    I_q = cc.field(tgt)
+    G = (0.3 * np.random.default_rng(1).normal(size=(len(tgt), 3))).astype(np.float32)
+    I_p = np.random.default_rng(0).uniform(0, 1, len(src)).astype(np.float32)
+    s = capi.Scan(ctx, src, flags=capi.FLAG_KEEP_ORDER)
+    s.set_intensity(I_p)
+    t = colour_target(capi, ctx, tgt, nq, I_q, G)
+    first, second, third = (capi.color_linearize(t, s, T, md, lam) for lam in (1.0, 0.5, 1.0))
+    assert np.array_equal(first, third)
+    assert second[28] == first[28] == mask.sum() == 216 and not np.array_equal(second[:28], first[:28])
+    ref, bound, kept = cc.reference(cc.terms(T, src, tp, tgt[j], nq[j], I_q[j], G[j], I_p, mask, 1.0), mask)
+    plane = pcr.PlaneICP(max_dist=md)
+    plane.set_target(tgt, kdree=object(), norm=nq)
+    H, g, e2 = plane.calc_H_g_e2(T, src)
+    err = np.abs(np.concatenate([H[cc.TRIU], g, [e2]]) - first[:28])
+    print(f"lambda = 1 against PlaneICP: max err / bound {np.max(err / bound):.3e}")
+    assert plane.last_correspondences == kept == first[28] and np.all(err <= bound)
+
+
+# ----------------------------------------------------------------------------- 13. device memory
 def test_align_device_memory_is_stable(capi, ctx, case):
     import torch
     import point_cloud_registration_amd as pcr

@@ -1,4 +1,4 @@
-"""The distribution pass behind GICP and VGICP (csrc/dist_pass.h, gicp_weight.h) at the gate boundary, across the pose space,
+"""The distribution pass behind GICP and VGICP (csrc/match_pass.h, gicp_weight.h) at the gate boundary, across the pose space,
 on singular sums, and over scans of more than one stride (tests/dist_cases.py, the clouds of tests/pass_cases.py / g16).
 
   a  the exact lattices: probes ON the gate, gates one ulp either side in float32 and float64, gates whose float32 square

@@ -426,7 +426,27 @@ def test_neighbours_undisturbed(capi, ctx, g2):
             assert g1[28] == o1[28] == s1[28] == 1823
 
 
-# ----------------------------------------------------------------------------- 12. device memory
+# ----------------------------------------------------------------------------- 12. the call's parameter decides
+def test_min_cos_belongs_to_the_call(capi, ctx, g2):
+    """Three calls over ONE uploaded scan, min_cos = 0, 0.9, 0: the first and the third return the same bits, the second keeps
+    strictly fewer pairs -- the gate is a parameter of the call, nothing an earlier call leaves on the scan.  The counts are
+    the restatement's (symm_cases.kept over brute-force correspondences), no |c| within 1e-9 of the gate."""
+    tgt, nq, src, _, j, mask = sc.call_case(g2)
+    n_p = sc.unit_normals(len(src), seed=3)
+    T, md = g2["T"], sc.CALL_MAX_DIST
+    assert np.min(np.abs(np.abs(sc.dots(T, n_p, nq[j])[mask]) - 0.9)) > 1e-9
+    all_, few = (int(sc.kept(T, n_p, nq[j], mask, mc).sum()) for mc in (0.0, 0.9))
+    assert (all_, few) == (216, 21)
+    t = capi.Target.points(ctx, tgt)
+    t.set_normals(nq)
+    s = capi.Scan(ctx, src, flags=capi.FLAG_KEEP_ORDER)
+    s.set_normals(n_p)
+    first, second, third = (capi.symm_linearize(t, s, T, md, mc) for mc in (0.0, 0.9, 0.0))
+    assert np.array_equal(first, third)
+    assert first[28] == all_ and second[28] == few < first[28]
+
+
+# ----------------------------------------------------------------------------- 13. device memory
 def test_align_device_memory_is_stable(capi, ctx, case):
     import torch
     import point_cloud_registration_amd as pcr
