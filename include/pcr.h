@@ -691,6 +691,65 @@ PCR_API pcr_status pcr_ransac_poses(pcr_context *ctx, const float *src, const fl
                                     float *poses_or_null /* n_hyp x 12 */, int32_t *counts_or_null /* n_hyp */);
 PCR_API int pcr_pose_score_splits(int64_t m, int64_t b);
 
+/* ---- a pose from correspondences without hypotheses: fast global registration (no reference counterpart) ---------------
+ * Zhou, Park, Koltun (ECCV 2016), what Open3D's registration_fgr_based_on_feature_matching does after the matching: a few
+ * dozen Gauss-Newton steps over the matches themselves under a Geman-McClure line process whose scale mu is annealed from
+ * "everything is an inlier" down to the inlier distance.  Cost: iterations x matches; deterministic by construction.
+ * src, dst: m x 3 float32 host arrays, finite; row j is one match p -> q.  mult: m int32 >= 0, the multiplicity c_j of a
+ *   match (NULL: all 1).  The pose T is 16 doubles, row-major, and maps src into the frame of dst.
+ * One pass at (T, mu): float64 over the widened float32 points, no fma, every dot product (a*b + c*d) + e*f:
+ *     x = ((R00*px + R01*py) + R02*pz) + tx, likewise y and z;  r = x - q;  r2 = (r0*r0 + r1*r1) + r2*r2
+ *     l = mu / (mu + r2);  w = c_j * (l*l)
+ *     J = [I, -skew(x)]:  row 0 = [1 0 0  0  x2 -x1],  row 1 = [0 1 0  -x2 0 x0],  row 2 = [0 0 1  x1 -x0 0]
+ *     out[0..20] += w * triu(J^T J), out[21..26] += w * J^T r, out[27] += w * r2, out[28] += w
+ *   with the terms written out (each is w times the bracket; a leading minus negates the product, which is exact):
+ *     triu(J^T J), row by row:  1 0 0 0 x2 -x1 | 1 0 -x2 0 x0 | 1 x1 -x0 0 | (x1*x1 + x2*x2) -(x0*x1) -(x0*x2) |
+ *                               (x0*x0 + x2*x2) -(x1*x2) | (x0*x0 + x1*x1)
+ *     J^T r:  r0, r1, r2, (x1*r2 - x2*r1), (x2*r0 - x0*r2), (x0*r1 - x1*r0)
+ *   The weight handed out per match is l*l (without c_j): a fixed sequence of +, x and / in float64.
+ * Summation: the unit is the tile of PCR_FGR_TILE consecutive matches.  The terms of a tile are folded in a fixed order (wave
+ *   shuffles, then the four waves in wave order) into ONE row of sums, and the rows are added in ascending tile order.  Which
+ *   block folds which tile does not enter (a block takes PCR_FGR_WIDTH consecutive tiles per trip; pcr_fgr_blocks(m) is the
+ *   host-side rule for the grid, PCR_FGR_BLOCKS in the environment caps it): the sums do not depend on the grid, there are
+ *   no atomics, and the same call twice returns the same bits.
+ * Step: dx = -solve(H, g) (LU with partial pivoting, an exactly zero pivot = singular), |dx| = sqrt of the six squares added
+ *   in index order.  The update is LEFT-multiplied: T <- [exp(dx[3:]), dx[:3]; 0 1] * T (exp: first order below |w|^2 <= 1e-5,
+ *   Rodrigues above; every entry of the product the sum over k = 0 .. 3 in order).  The local aligners' J = [I, -R skew(p)]
+ *   with T <- T * dT is NOT used here: its translation block is right near R = I only, and this loop starts anywhere.
+ * Schedule: after iteration it (from 0), if (it + 1) % period == 0 and mu > mu_min: mu = max(mu / division, mu_min).
+ * Loop (pcr_fgr_pose), for it = 0 .. max_iter - 1: pass at (T, mu); trace row it = T (16), the 29 sums, mu (PCR_FGR_TRACE
+ *   doubles); a singular system ends it with status 2, T staying at the last good pose; when tol > 0, mu == mu_min and
+ *   |dx| < tol it ends with status 1 (the test precedes the update: T stays); else the update and the schedule.  Status 0:
+ *   max_iter passes were made.  *iterations = the passes made (trace rows written; the rest of the trace is 0), *mu_final =
+ *   mu after the last schedule step, weight = l*l of every match at (T_out, *mu_final).  The default form keeps pose, mu
+ *   and counter on the device and enqueues all passes back to back; PCR_FLAG_HOST_LOOP reads the 29 sums back and steps on
+ *   the host, per iteration: the same arithmetic, the same bits.
+ * pcr_fgr_tuples: Open3D's tuple test with RANSAC's sampler and validity rule above.  Tuple h = the three rows of hypothesis
+ *   h of `seed`; it is valid iff its three edges pass the edge-length rule with s = tuple_scale and e = min_edge and both
+ *   triangles are non-degenerate.  mult[j] = the number of valid tuples row j is in (an integer count: independent of order
+ *   and of the chunks, PCR_FGR_CHUNK tuples per launch, default 2^20), *n_valid = the valid tuples.  m < 3: all 0.
+ * PCR_ERR_INVALID: src or dst non-finite; mu, mu0 or mu_min not finite or not > 0; division <= 1; period < 1; max_iter < 0;
+ *   a negative mult; m > 2^24; n_tuples < 0 or > 2^26; tuple_scale outside [0, 1]; min_edge negative or non-finite -- the
+ *   outputs are then left untouched and the context stays usable.  m == 0 or max_iter == 0 return PCR_OK without a launch:
+ *   T_out = T_init, zero sums, 0 iterations, status 0, mu_final = mu0, weights 1.  One GPU of one process.               */
+#define PCR_FGR_TILE 256
+#define PCR_FGR_WIDTH 4
+#define PCR_FGR_TRACE 46
+PCR_API pcr_status pcr_fgr_linearize(pcr_context *ctx, const float *src, const float *dst, int64_t m, const int32_t *mult_or_null,
+                                     const double T[16], double mu, double out[29], double *weight_or_null /* m */);
+PCR_API pcr_status pcr_fgr_pose(pcr_context *ctx, const float *src, const float *dst, int64_t m, const int32_t *mult_or_null,
+                                const double T_init[16], double mu0, double mu_min, double division, int period, int max_iter,
+                                double tol, unsigned flags, double T_out[16], int *iterations,
+                                int *status /* 0 ran out, 1 converged, 2 singular */, double *mu_final,
+                                double *weight_or_null /* m */, double *trace_or_null /* max_iter x PCR_FGR_TRACE */);
+PCR_API pcr_status pcr_fgr_tuples(pcr_context *ctx, const float *src, const float *dst, int64_t m, int64_t n_tuples, uint64_t seed,
+                                  float tuple_scale, float min_edge, int32_t *mult /* m */, int64_t *n_valid);
+PCR_API int pcr_fgr_blocks(int64_t m);
+/* developer builds carry a single-block form of the loop for match lists that fit into the LDS of one workgroup (the same
+ * bits, measured slower; PCR_FGR_SOLO=1 in the environment selects it for every list that fits): *m_max = the largest list
+ * it serves on this device, 0 in a library without it                                                                   */
+PCR_API pcr_status pcr_fgr_solo_max(pcr_context *ctx, int64_t *m_max);
+
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the
  * context's stream; pcr_profile_read drains them (synchronises) and reports per-kernel

@@ -24,7 +24,7 @@ from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
 from .features import compute_fpfh, compute_fpfh_rows, match_features, select_matches
 from .keypoints import iss_keypoints
-from .global_registration import score_poses, fit_rigid, ransac_pose, register_global
+from .global_registration import score_poses, fit_rigid, ransac_pose, fgr_pose, register_global
 
 __all__ = [
     "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "SymmetricICP", "ColoredICP", "KDTree", "VoxelGrid", "voxel_filter",
@@ -32,5 +32,5 @@ __all__ = [
     "makeRt", "expSO3", "makeT", "skews", "huber_weight", "plus", "transform_points",
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
-    "score_poses", "fit_rigid", "ransac_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
+    "score_poses", "fit_rigid", "ransac_pose", "fgr_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
 ]

@@ -104,6 +104,14 @@ PROTOTYPES = {
     "pcr_ransac_poses": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float,
                                    C.POINTER(C.c_int64), _f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _vp, _vp, _vp]),
     "pcr_pose_score_splits": (C.c_int, [C.c_int64, C.c_int64]),
+    # fast global registration: the robust pass over a match list, its loop and the tuple test (include/pcr.h)
+    "pcr_fgr_linearize": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, _vp, _f64p, C.c_double, _f64p, _vp]),
+    "pcr_fgr_pose": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, _vp, _f64p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                               C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), _vp, _vp]),
+    "pcr_fgr_tuples": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float, _vp,
+                                 C.POINTER(C.c_int64)]),
+    "pcr_fgr_blocks": (C.c_int, [C.c_int64]),
+    "pcr_fgr_solo_max": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -1175,6 +1183,114 @@ def ransac_poses(ctx, src, dst, n_hyp, seed, max_dist, edge_similarity, min_edge
 def pose_score_splits(m, b):
     """pcr_pose_score_splits: how many row splits a pcr_pose_score call of b poses over m rows uses (a host-side rule)."""
     return int(lib().pcr_pose_score_splits(int(m), int(b)))
+
+
+FGR_TILE, FGR_WIDTH, FGR_TRACE = 256, 4, 46     # PCR_FGR_TILE, PCR_FGR_WIDTH, PCR_FGR_TRACE of include/pcr.h
+
+
+def check_mult(mult, m):
+    """Multiplicities as C-contiguous int32 (M,), every one >= 0, or None; else ValueError."""
+    if mult is None:
+        return None
+    mult = np.asarray(mult)
+    if mult.shape != (m,) or not np.issubdtype(mult.dtype, np.integer):
+        raise ValueError("mult must be M integers")
+    if m and (mult.min() < 0 or mult.max() >= 1 << 31):
+        raise ValueError("mult must be >= 0 and fit int32")
+    return np.ascontiguousarray(mult, dtype=np.int32)
+
+
+def _pose16(T, name):
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError(f"{name} must have shape (4, 4)")
+    return T
+
+
+def check_fgr(mu0, mu_min, division, period, max_iter):
+    """The schedule of pcr_fgr_pose as (float, float, float, int, int), the library's own rule, else ValueError."""
+    mu0, mu_min, division = float(mu0), float(mu_min), float(division)
+    if not (np.isfinite(mu0) and mu0 > 0 and np.isfinite(mu_min) and mu_min > 0):
+        raise ValueError("mu0 and mu_min must be finite and > 0")
+    if not (np.isfinite(division) and division > 1):
+        raise ValueError("division_factor must be finite and > 1")
+    if int(period) != period or not 1 <= int(period) < 1 << 31:
+        raise ValueError("period must be an integer >= 1")
+    if int(max_iter) != max_iter or not 0 <= int(max_iter) < 1 << 31:
+        raise ValueError("iterations must be an integer >= 0")
+    return mu0, mu_min, division, int(period), int(max_iter)
+
+
+def fgr_linearize(ctx, src, dst, T, mu, mult=None, want_weight=False):
+    """pcr_fgr_linearize: one robust pass over the matches at (T, mu) -> the 29 sums (and the weights l*l (M,) with
+    ``want_weight``).  ``ctx`` may be a callable, as for ``pose_score``."""
+    src, dst = check_pairs(src, dst)
+    m = len(src)
+    mult, T, mu = check_mult(mult, m), _pose16(T, "T"), float(mu)
+    if not (np.isfinite(mu) and mu > 0):
+        raise ValueError("mu must be finite and > 0")
+    out = np.zeros(29)
+    weight = np.ones(m) if want_weight else None
+    if m:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_fgr_linearize(ctx.handle, src, dst, m, _ptr(mult), T, mu, out, _ptr(weight)))
+    return (out, weight) if want_weight else out
+
+
+def fgr_pose(ctx, src, dst, T_init, mu0, mu_min, division, period, max_iter, tol=0.0, flags=0, mult=None, want_trace=False):
+    """pcr_fgr_pose -> dict(T (4, 4), iterations, status (0 ran out, 1 converged, 2 singular), mu, weights (M,)) and, with
+    ``want_trace``, trace (max_iter, 46): T before the step, the 29 sums, mu -- rows beyond ``iterations`` are 0."""
+    src, dst = check_pairs(src, dst)
+    m = len(src)
+    mult, T_init = check_mult(mult, m), _pose16(T_init, "T_init")
+    mu0, mu_min, division, period, max_iter = check_fgr(mu0, mu_min, division, period, max_iter)
+    T = T_init.copy()
+    weight = np.ones(m)
+    trace = np.zeros((max_iter, FGR_TRACE)) if want_trace else None
+    it, status, mu = C.c_int(0), C.c_int(0), C.c_double(mu0)
+    if m and max_iter:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_fgr_pose(ctx.handle, src, dst, m, _ptr(mult), T_init, mu0, mu_min, division, period, max_iter, float(tol),
+                                 int(flags), T, C.byref(it), C.byref(status), C.byref(mu), _ptr(weight), _ptr(trace)))
+    out = {"T": T, "iterations": it.value, "status": status.value, "mu": mu.value, "weights": weight}
+    if want_trace:
+        out["trace"] = trace
+    return out
+
+
+def fgr_tuples(ctx, src, dst, n_tuples, seed, tuple_scale, min_edge):
+    """pcr_fgr_tuples -> (mult (M,) int32, n_valid)."""
+    src, dst = check_pairs(src, dst)
+    n_tuples, seed = int(n_tuples), int(seed)
+    if not 0 <= n_tuples <= RANSAC_H_MAX:
+        raise ValueError("n_tuples must be in [0, 2^26]")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    min_edge = check_distance(min_edge, "min_edge")
+    tuple_scale = float(np.float32(tuple_scale))
+    if not 0 <= tuple_scale <= 1:
+        raise ValueError("tuple_scale must be in [0, 1]")
+    m = len(src)
+    mult, n_valid = np.zeros(m, np.int32), C.c_int64(0)
+    if m >= 3 and n_tuples:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_fgr_tuples(ctx.handle, src, dst, m, n_tuples, seed, tuple_scale, min_edge, _ptr(mult), C.byref(n_valid)))
+    return mult, n_valid.value
+
+
+def fgr_blocks(m):
+    """pcr_fgr_blocks: the grid of the robust pass over m matches (a host-side rule; PCR_FGR_BLOCKS caps it)."""
+    return int(lib().pcr_fgr_blocks(int(m)))
+
+
+def fgr_solo_max(ctx):
+    """pcr_fgr_solo_max: the largest match list the single-block form of the loop serves; 0 in a library without it."""
+    n = C.c_int64(0)
+    check(lib().pcr_fgr_solo_max(ctx.handle, C.byref(n)))
+    return n.value
 
 
 def gn_set(ctx, J, r):

@@ -120,6 +120,23 @@ PCR_HD static inline void gn_se3_plus(double T[16], const double dx[6]) {
     for (int i = 0; i < 16; ++i) T[i] = r[i];
 }
 
+// The LEFT update of fast global registration (include/pcr.h: pcr_fgr_pose): T <- [exp(w), v; 0 1] @ T, dx = (v, w).  It
+// belongs to J = [I, -skew(T p)], the perturbation of the TRANSFORMED point, and holds at any rotation; gn_se3_plus above
+// belongs to the local aligners' J = [I, -R skew(p)].  Every entry is the sum over k = 0 .. 3 in that order, starting from 0.
+PCR_HD static inline void gn_se3_lplus(double T[16], const double dx[6]) {
+    double dR[9];
+    gn_exp_so3(dx + 3, dR);
+    const double D[16] = {dR[0], dR[1], dR[2], dx[0], dR[3], dR[4], dR[5], dx[1], dR[6], dR[7], dR[8], dx[2], 0, 0, 0, 1};
+    double r[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double v = 0;
+            for (int k = 0; k < 4; ++k) v += D[4 * i + k] * T[4 * k + j];
+            r[4 * i + j] = v;
+        }
+    for (int i = 0; i < 16; ++i) T[i] = r[i];
+}
+
 // One Gauss-Newton step from the 29 sums (include/pcr.h layout).  Returns 0 = stepped (T updated),
 // 1 = converged (|dx| < tol: the test precedes the update, quirk Q4; T unchanged), 2 = singular.
 PCR_HD static inline int gn_step(double (*A)[7], const double o[29], double tol, double T[16]) {

@@ -18,6 +18,7 @@
 // smallest h -- by wave shuffles and one integer atomic maximum per wave: associative, so the winner does not depend on the
 // grid or on the chunks.
 #include "host_util.h"
+#include "ransac_device.h"     // rs_mix, rs_sample, RsV3, rs_edge_ok: shared with fgr.hip
 
 #define RS_TILE PCR_RANSAC_TILE      // rows per LDS tile
 #define RS_BLOCK 256                 // poses per block, one per lane
@@ -29,33 +30,7 @@
 typedef float rs_v2 __attribute__((ext_vector_type(2)));
 typedef float rs_v4 __attribute__((ext_vector_type(4)));
 
-// ---- sampling ---------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t rs_mix(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ void rs_sample(uint64_t s, uint64_t h, uint64_t m, uint32_t &c0, uint32_t &c1, uint32_t &c2) {
-    uint64_t a0 = __umul64hi(rs_mix(s ^ (4 * h + 0)), m);
-    uint64_t a1 = __umul64hi(rs_mix(s ^ (4 * h + 1)), m - 1);
-    uint64_t a2 = __umul64hi(rs_mix(s ^ (4 * h + 2)), m - 2);
-    a1 += (a1 >= a0);
-    const uint64_t lo = a0 < a1 ? a0 : a1, hi = a0 < a1 ? a1 : a0;
-    a2 += (a2 >= lo);
-    a2 += (a2 >= hi);
-    c0 = (uint32_t)a0; c1 = (uint32_t)a1; c2 = (uint32_t)a2;
-}
-
 // ---- the fit ----------------------------------------------------------------------------------------------------------------
-struct RsV3 { double x, y, z; };
-__device__ __forceinline__ RsV3 rs_ld(const float *__restrict__ a, uint32_t r) {
-    return RsV3{(double)a[3 * (size_t)r], (double)a[3 * (size_t)r + 1], (double)a[3 * (size_t)r + 2]};
-}
-__device__ __forceinline__ RsV3 rs_sub(RsV3 a, RsV3 b) { return RsV3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double rs_dot(RsV3 a, RsV3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ RsV3 rs_cross(RsV3 a, RsV3 b) { return RsV3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ RsV3 rs_div(RsV3 a, double s) { return RsV3{a.x / s, a.y / s, a.z / s}; }
 
 // the triad of (p0, p1, p2): u1 along e1, u3 along e1 x e2, u2 = u3 x u1; false when the triangle is degenerate
@@ -67,12 +42,6 @@ __device__ __forceinline__ bool rs_triad(RsV3 p0, RsV3 p1, RsV3 p2, RsV3 &u1, Rs
     u3 = rs_div(w, __builtin_sqrt(nw));
     u2 = rs_cross(u3, u1);
     return true;
-}
-
-__device__ __forceinline__ bool rs_edge_ok(RsV3 pi, RsV3 pj, RsV3 qi, RsV3 qj, double sim2, double e2min) {
-    const RsV3 dp = rs_sub(pi, pj), dq = rs_sub(qi, qj);
-    const double a2 = rs_dot(dp, dp), b2 = rs_dot(dq, dq);
-    return a2 >= sim2 * b2 && b2 >= sim2 * a2 && a2 >= e2min && b2 >= e2min;
 }
 
 // hypotheses h0 .. h0 + n - 1 -> poses[i * 12] (all NaN: invalid), samples[i * 3] when not NULL

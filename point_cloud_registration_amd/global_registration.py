@@ -3,7 +3,8 @@
 ``include/pcr.h``.  The reference has no counterpart.
 
 ``ransac_pose`` draws pose hypotheses from triples of matches, scores every one of them against every match on the GPU and
-refines the winner over its inliers; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose`` --
+refines the winner over its inliers; ``fgr_pose`` (fast global registration, ``csrc/fgr.hip``) runs a graduated robust
+Gauss-Newton loop over the matches instead; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose`` --
 over every point, or over keypoints (``keypoints.py``) with descriptors at those rows only.  The
 result is an ``init_T`` for ``align`` of any of the local aligners.  Everything is computed over the **float32 copy** of the
 points, and the same call twice returns the same bits.
@@ -162,6 +163,74 @@ def ransac_pose(source, target, ia, ib, max_dist, n_hypotheses=100_000, seed=0, 
                "n_valid": int(res["n_valid"])}
 
 
+def _bbox_diagonal(a):
+    return float(np.linalg.norm(a.max(axis=0).astype(np.float64) - a.min(axis=0).astype(np.float64))) if len(a) else 0.0
+
+
+def fgr_pose(source, target, ia, ib, max_dist, iterations=64, division_factor=1.4, period=4, mu0=None, tuple_scale=0.95, n_tuples=None,
+             min_edge=0.0, seed=0, init_T=None, refine_rounds=5, return_info=False, device=None):
+    """A pose from the correspondences ``source[ia] -> target[ib]`` by fast global registration (Zhou, Park, Koltun 2016;
+    Open3D's ``registration_fgr_based_on_feature_matching`` after the matching): no hypotheses, ``iterations`` Gauss-Newton
+    steps over the matches themselves under a Geman-McClure line process (``include/pcr.h``: ``pcr_fgr_pose``).  Its scale
+    ``mu`` starts at ``mu0`` -- ``None``: D^2, D the larger bounding-box diagonal of the two matched point sets, where every
+    match counts as an inlier -- and is divided by ``division_factor`` every ``period`` iterations down to ``max_dist``^2.
+
+    ``tuple_scale``: the tuple test first.  ``n_tuples`` (``None``: 100 per match, at most 2^26) triples of matches are drawn
+    by ``ransac_pose``'s generator from ``seed``; one whose edge lengths agree within the factor ``tuple_scale`` on both sides
+    (and are at least ``min_edge``) adds 1 to the multiplicity of its three matches, and a match then counts that often:
+    matches no valid triple contains drop out.  ``None`` skips the test.  Fewer than 3 matches left: ``ransac_pose``'s no-match
+    result, the identity and count 0.  The loop starts from ``init_T`` (identity) and ends as ``ransac_pose`` does: its pose
+    is scored at ``max_dist``, refined up to ``refine_rounds`` times over its inliers and returned with its rotation made
+    orthonormal.  Deterministic: the same call twice returns the same bits.
+
+    -> ``T`` (4, 4) float64; with ``return_info`` also a dict with ``pose``, ``inliers``, ``count``, ``fitness``, ``rmse`` as
+    for ``ransac_pose`` and ``iterations``, ``status`` (0 ran out, 1 converged, 2 singular), ``mu`` (the last scale),
+    ``weights`` (M,) float64 -- the line-process weights under the loop's own pose --, ``mult`` (M,) int32 and ``n_valid``."""
+    src, dst = _pairs(source, target, ia, ib)
+    m = len(src)
+    refine_rounds = int(refine_rounds)
+    if refine_rounds < 0:
+        raise ValueError("refine_rounds must be >= 0")
+    max_dist = _capi.check_distance(max_dist, "max_dist")
+    if not max_dist > 0:
+        raise ValueError("max_dist must be > 0")
+    if mu0 is None:
+        D = max(_bbox_diagonal(src), _bbox_diagonal(dst))
+        mu0 = D * D if D > 0 else max_dist * max_dist
+    mu0, mu_min, division, period, iterations = _capi.check_fgr(mu0, max_dist * max_dist, division_factor, period, iterations)
+    T0 = np.eye(4) if init_T is None else _capi._pose16(init_T, "init_T")
+    if n_tuples is None:
+        n_tuples = min(100 * m, _capi.RANSAC_H_MAX)
+    box = []
+
+    def ctx():
+        if not box:
+            box.append(_capi.get_context(device))
+        return box[0]
+    if tuple_scale is None:
+        mult, n_valid, live = np.ones(m, np.int32), 0, m
+    else:
+        mult, n_valid = _capi.fgr_tuples(ctx, src, dst, n_tuples, seed, tuple_scale, min_edge)
+        live = int(np.count_nonzero(mult))
+    T, count, mask, rmse = np.eye(4), 0, np.zeros(m, bool), np.inf
+    pose = _poses12(T)[0][0]
+    res = {"iterations": 0, "status": 0, "mu": mu0, "weights": np.ones(m)}
+    if live >= 3:
+        res = _capi.fgr_pose(ctx, src, dst, T0, mu0, mu_min, division, period, iterations, mult=None if tuple_scale is None else mult)
+
+        def score(Tc):
+            c, k = _capi.pose_score(ctx, src, dst, _poses12(Tc)[0], max_dist, want_mask=True)
+            return int(c[0]), k[0]
+        T, count, mask, rmse = refine_pose(score, src, dst, res["T"], refine_rounds)
+        pose = _poses12(T)[0][0]
+        T = _proper(T)
+    if not return_info:
+        return T
+    return T, {"pose": pose, "inliers": mask, "count": int(count), "fitness": count / m if m else 0.0, "rmse": rmse,
+               "iterations": res["iterations"], "status": res["status"], "mu": res["mu"], "weights": res["weights"], "mult": mult,
+               "n_valid": int(n_valid)}
+
+
 def _keypoint_rows(rows, n, name):
     rows = np.asarray(rows)
     if rows.ndim != 1 or (len(rows) and not np.issubdtype(rows.dtype, np.integer)):
@@ -175,16 +244,20 @@ def _keypoint_rows(rows, n, name):
 
 
 def register_global(source, target, feature_radius, max_dist, normals=None, mutual=True, ratio=None, device=None, keypoints=None,
-                    keypoint_args=None, **ransac):
+                    keypoint_args=None, method="ransac", **ransac):
     """Global registration end to end: ``compute_fpfh`` on both clouds at ``feature_radius``, ``match_features`` (source
     against target, ``mutual`` / ``ratio``), then ``ransac_pose`` with the remaining keywords.  ``normals``: ``None`` to
-    estimate them, or a pair ``(source_normals, target_normals)``.
+    estimate them, or a pair ``(source_normals, target_normals)``.  ``method="fgr"`` hands the matches and the remaining
+    keywords to ``fgr_pose`` instead.
 
     ``keypoints``: ``None`` describes and matches every point; ``"iss"`` detects ISS keypoints on both clouds
     (``iss_keypoints(cloud, **keypoint_args)``); a pair ``(source_rows, target_rows)`` uses the caller's own.  Descriptors are
     then computed at those rows only (``compute_fpfh_rows``), a few thousand rows are matched instead of every point, and the
     matches are mapped back to rows of ``source`` and ``target`` before ``ransac_pose``.  Fewer than 3 keypoints on either side
     give no matches: ``ransac_pose``'s no-match result."""
+    if method not in ("ransac", "fgr"):
+        raise ValueError('method must be "ransac" or "fgr"')
+    pose_from_matches = ransac_pose if method == "ransac" else fgr_pose
     ns, nt = (None, None) if normals is None else normals
     if keypoints is None:
         if keypoint_args is not None:
@@ -192,7 +265,7 @@ def register_global(source, target, feature_radius, max_dist, normals=None, mutu
         fs = compute_fpfh(source, ns, radius=feature_radius, device=device)
         ft = compute_fpfh(target, nt, radius=feature_radius, device=device)
         ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
-        return ransac_pose(source, target, ia, ib, max_dist, device=device, **ransac)
+        return pose_from_matches(source, target, ia, ib, max_dist, device=device, **ransac)
     if isinstance(keypoints, str):
         if keypoints != "iss":
             raise ValueError('keypoints must be None, "iss" or a pair (source_rows, target_rows)')
@@ -216,4 +289,4 @@ def register_global(source, target, feature_radius, max_dist, normals=None, mutu
         ft = compute_fpfh_rows(target, kt, nt, radius=feature_radius, device=device)
         ia, ib, _ = match_features(fs, ft, mutual=mutual, ratio=ratio, device=device)
         ia, ib = ks[ia], kt[ib]
-    return ransac_pose(source, target, ia, ib, max_dist, device=device, **ransac)
+    return pose_from_matches(source, target, ia, ib, max_dist, device=device, **ransac)
