@@ -493,6 +493,77 @@ PCR_API pcr_status pcr_color_align(pcr_target *t, pcr_scan *s, const double T_in
                                    double lambda_geometric, unsigned flags, double T_out[16], int *iterations,
                                    double *trace_or_null);
 
+/* ---- robust kernels inside the pass of GICP, VGICP, SymmetricICP and ColoredICP ----------------
+ * No reference counterpart (what Open3D's RobustKernel, PCL and small_gicp offer): a correspondence inside the gate is weighed
+ * by w(s), s its squared residual, so that wrong ones -- moving objects, vegetation, partial overlap -- pull less.  New entry
+ * points only; the plain ones above keep their kernels and their bits.
+ * A kernel is a function of s and a scale c > 0, with c2 = c * c taken ONCE on the host.  Float64, nothing contracted, each a
+ * fixed sequence of compare, +, -, x, / and sqrt:
+ *   PCR_ROBUST_HUBER    w = s <= c2 ? 1 : c / sqrt(s)
+ *   PCR_ROBUST_CAUCHY   w = 1 / (1 + s / c2)
+ *   PCR_ROBUST_TUKEY    u = 1 - s / c2;  w = s <= c2 ? u u : 0
+ *   PCR_ROBUST_GM       l = c2 / (c2 + s);  w = l l            (Geman-McClure: pcr_fgr_linearize's line process with mu = c2)
+ *   PCR_ROBUST_NONE     the plain pass: rb == NULL or this kind run the plain kernel and return its bits; the scale is not read
+ * Every w lies in [0, 1]; w(0) = 1; every kernel is continuous at s = c2.
+ * What s is:
+ *   pcr_symm_*    s = r r of the one row
+ *   pcr_color_*   each of the two rows has its own s and its own weight (Open3D's convention): s_G = (a_G r_G)(a_G r_G),
+ *                 s_C = (a_C r_C)(a_C r_C), the row's residual after the sqrt(lambda) / sqrt(1 - lambda) factor
+ *   pcr_gicp_*, pcr_vgicp_*   s = d^T M d with M the 3 x 3 weight the plain pass forms and d the residual, widened:
+ *                 Md_i = (M_i0 d_0 + M_i1 d_1) + M_i2 d_2,  s = (d_0 Md_0 + d_1 Md_1) + d_2 Md_2
+ * The sums are the IRLS ones, H = sum w J^T J, g = sum w J^T r, e2 = sum w r r:
+ *   rows (symm, color):  Jw = w J and rw = w r, one product each, then the plain accumulation with them on the left:
+ *                 H_ij = fma(Jw_i, J_j, H_ij), g_i = fma(Jw_i, r, g_i), e2 = fma(rw, r, e2)
+ *   gicp, vgicp:  every entry of M times w, one product each, then the plain accumulation with w M in the place of M
+ * out[28] stays the NUMBER of correspondences inside the gate (for symm: through the normal gate too), whatever their weights.
+ * Search, distance gate, normal gate and the det == 0 rule are the plain pass's; so are the reduce's three phases, its fold
+ * (plain stores, no atomics) and its grid, which depends on the scan size and the device only: two calls return the same bits.
+ * pcr_*_linearize_robust: the refusals of the plain call, and PCR_ERR_INVALID for a kind that is none of the above, or (kind
+ *   not NONE) a scale that is not finite, not > 0, or whose square is not finite or not > 0 (1e200; 1e-200).  The outputs
+ *   are then untouched.
+ * pcr_*_align_robust: the host-driven loop of the plain *_align over the robust pass: same step, same stop rule, same trace
+ *   rows (16 + 29 doubles: the sums of pcr_*_linearize_robust at the row's pose), PCR_ERR_SINGULAR as there -- which a Tukey
+ *   scale below every residual returns, every weight being 0.  A refusal leaves T_out untouched.
+ * pcr_*_residuals: s of every scan point at pose T -- what a caller picks a scale from (a median, say) -- as (n) doubles, for
+ *   pcr_color_residuals (n, 2) = s_G, s_C, in the CALLER's order: the scan must know that order (PCR_FLAG_KEEP_ORDER or
+ *   PCR_FLAG_NO_SCAN_SORT, else PCR_ERR_INVALID).  +inf (every value of the point) where the point has no correspondence or
+ *   a gate drops it.  Refusals of the plain linearize otherwise; s_out is untouched then.                              */
+#define PCR_ROBUST_NONE 0
+#define PCR_ROBUST_HUBER 1
+#define PCR_ROBUST_CAUCHY 2
+#define PCR_ROBUST_TUKEY 3
+#define PCR_ROBUST_GM 4
+typedef struct {
+    int kind;      /* PCR_ROBUST_* */
+    double scale;  /* c */
+} pcr_robust;
+PCR_API pcr_status pcr_gicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
+                                             unsigned flags, double out[29]);
+PCR_API pcr_status pcr_gicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                         const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
+                                         double *trace_or_null);
+PCR_API pcr_status pcr_gicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out);
+PCR_API pcr_status pcr_vgicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
+                                              unsigned flags, double out[29]);
+PCR_API pcr_status pcr_vgicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                          const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
+                                          double *trace_or_null);
+PCR_API pcr_status pcr_vgicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out);
+PCR_API pcr_status pcr_symm_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos,
+                                             const pcr_robust *rb, unsigned flags, double out[29]);
+PCR_API pcr_status pcr_symm_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                         double min_cos, const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
+                                         double *trace_or_null);
+PCR_API pcr_status pcr_symm_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
+                                      double *s_out);
+PCR_API pcr_status pcr_color_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                              const pcr_robust *rb, unsigned flags, double out[29]);
+PCR_API pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                          double lambda_geometric, const pcr_robust *rb, unsigned flags, double T_out[16],
+                                          int *iterations, double *trace_or_null);
+PCR_API pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                       unsigned flags, double *s_out);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

@@ -179,6 +179,22 @@ PROTOTYPES = {
     "pcr_target_voxels_get_covariances": (C.c_int, [_vp, _f64p]),
     "pcr_vgicp_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _f64p]),
     "pcr_vgicp_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    # robust kernels inside the pass of the four match-list aligners, and the squared residuals a scale is chosen from
+    # (include/pcr.h); rb: a pcr_robust by pointer, or NULL
+    "pcr_gicp_linearize_robust": (C.c_int, [_vp, _vp, _f64p, C.c_double, _vp, C.c_uint, _f64p]),
+    "pcr_gicp_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, _vp, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    "pcr_gicp_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _vp]),
+    "pcr_vgicp_linearize_robust": (C.c_int, [_vp, _vp, _f64p, C.c_double, _vp, C.c_uint, _f64p]),
+    "pcr_vgicp_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, _vp, C.c_uint, _f64p, C.POINTER(C.c_int), _vp]),
+    "pcr_vgicp_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_uint, _vp]),
+    "pcr_symm_linearize_robust": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, _vp, C.c_uint, _f64p]),
+    "pcr_symm_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
+                                        C.POINTER(C.c_int), _vp]),
+    "pcr_symm_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _vp]),
+    "pcr_color_linearize_robust": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, _vp, C.c_uint, _f64p]),
+    "pcr_color_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
+                                         C.POINTER(C.c_int), _vp]),
+    "pcr_color_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _vp]),
     # batches: many scans / start poses against one target in one launch (include/pcr.h)
     "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
     "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -1426,6 +1442,93 @@ def color_align(target, scan, T_init, max_iter, tol, max_dist, lambda_geometric=
     """pcr_color_align: the host-driven Gauss-Newton loop over pcr_color_linearize, behind the boundary."""
     entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_color_align(t, s, T0, it, tol, md, float(lambda_geometric), *rest)
     return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
+
+
+# ---- robust kernels inside the pass of the four match-list aligners (include/pcr.h) ----------------------------------
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_GM = 0, 1, 2, 3, 4
+ROBUST_KINDS = {None: ROBUST_NONE, "huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY, "gm": ROBUST_GM}
+
+
+class Robust(C.Structure):
+    """pcr_robust: a kind (ROBUST_*) and its scale c."""
+    _fields_ = [("kind", C.c_int), ("scale", C.c_double)]
+
+
+def check_robust(robust, scale):
+    """``robust`` (None, "huber", "cauchy", "tukey", "gm") and ``scale`` as (kind, float), the library's own rule, else
+    ValueError: the scale finite and > 0, and so its square (not read when ``robust`` is None)."""
+    if robust not in ROBUST_KINDS:
+        raise ValueError('robust must be None, "huber", "cauchy", "tukey" or "gm"')
+    scale = float(scale)
+    if robust is not None and not (0.0 < scale < np.inf and 0.0 < scale * scale < np.inf):      # (false for NaN)
+        raise ValueError("robust_scale must be finite and > 0, and so must its square")
+    return ROBUST_KINDS[robust], scale
+
+
+def _rb(robust):
+    """None or (kind, scale) -> the pointer argument of a *_robust entry point (and the object that keeps it alive)."""
+    if robust is None:
+        return None, None
+    rb = Robust(int(robust[0]), float(robust[1]))
+    return C.cast(C.pointer(rb), _vp), rb
+
+
+def _extras(args, extra):
+    if len(args) != extra:
+        raise TypeError(f"expected {extra} pass parameter(s) after max_dist, got {len(args)}")
+    return tuple(float(v) for v in args)
+
+
+def _robust_pair(name, extra):
+    """(linearize, align) over pcr_<name>_linearize_robust / _align_robust; ``extra``: the doubles between max_dist and rb."""
+    def linearize(target, scan, T, max_dist, *args, robust=None, flags=0):
+        p, keep = _rb(robust)
+        ex = _extras(args, extra)
+        entry = lambda t, s, T, md, fl, out: getattr(lib(), f"pcr_{name}_linearize_robust")(t, s, T, md, *ex, p, fl, out)
+        return _linearize29(entry, target, scan, T, max_dist, flags)
+
+    def align(target, scan, T_init, max_iter, tol, max_dist, *args, robust=None, flags=0, want_trace=False):
+        p, keep = _rb(robust)
+        ex = _extras(args, extra)
+        entry = lambda t, s, T0, it, tol, md, *rest: getattr(lib(), f"pcr_{name}_align_robust")(t, s, T0, it, tol, md, *ex, p, *rest)
+        return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
+    return linearize, align
+
+
+# (target, scan, T, max_dist[, min_cos | lambda_geometric], robust=(kind, scale) or None, flags=0) -> the 29 sums;
+# (target, scan, T_init, max_iter, tol, max_dist[, ...], robust=, flags=0, want_trace=False) -> as the plain *_align
+gicp_linearize_robust, gicp_align_robust = _robust_pair("gicp", 0)
+vgicp_linearize_robust, vgicp_align_robust = _robust_pair("vgicp", 0)
+symm_linearize_robust, symm_align_robust = _robust_pair("symm", 1)
+color_linearize_robust, color_align_robust = _robust_pair("color", 1)
+
+
+def _residuals(name, m, target, scan, T, max_dist, extra, flags):
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty((scan.n, m) if m > 1 else (scan.n,))
+    check(getattr(lib(), f"pcr_{name}_residuals")(target.handle, scan.handle, T, float(max_dist), *map(float, extra), int(flags), _ptr(out)))
+    return out
+
+
+def gicp_residuals(target, scan, T, max_dist, flags=0):
+    """pcr_gicp_residuals -> d^T M d (N,) float64 in the caller's order, inf where a point has no correspondence."""
+    return _residuals("gicp", 1, target, scan, T, max_dist, (), flags)
+
+
+def vgicp_residuals(target, scan, T, max_dist, flags=0):
+    """pcr_vgicp_residuals -> d^T M d (N,) float64 in the caller's order, inf where a point has no correspondence."""
+    return _residuals("vgicp", 1, target, scan, T, max_dist, (), flags)
+
+
+def symm_residuals(target, scan, T, max_dist, min_cos=0.0, flags=0):
+    """pcr_symm_residuals -> r r (N,) float64 in the caller's order, inf where a point has no correspondence."""
+    return _residuals("symm", 1, target, scan, T, max_dist, (min_cos,), flags)
+
+
+def color_residuals(target, scan, T, max_dist, lambda_geometric=0.968, flags=0):
+    """pcr_color_residuals -> the squared residuals of both rows (N, 2) float64 in the caller's order, inf where a point has no
+    correspondence."""
+    return _residuals("color", 2, target, scan, T, max_dist, (lambda_geometric,), flags)
 
 
 _linearize_fast = None

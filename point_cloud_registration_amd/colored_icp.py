@@ -33,6 +33,8 @@ def as_intensity(values, n, name):
 
 class ColoredICP(MatchPass):
     _capi_linearize, _capi_align = staticmethod(_capi.color_linearize), staticmethod(_capi.color_align)
+    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.color_linearize_robust), staticmethod(_capi.color_align_robust)
+    _capi_residuals = staticmethod(_capi.color_residuals)
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, lambda_geometric=0.968, **kw):
         super().__init__(max_iter, max_dist, tol, k, **kw)
@@ -116,6 +118,9 @@ class ColoredICP(MatchPass):
             scan.set_intensity(inten)
             scan._color_int = tag
         return scan
+
+    def _pass_scan(self, source, source_intensity=None):
+        return self._color_scan(source, source_intensity)
 
     # -- passes ----------------------------------------------------------------------------------
     def calc_H_g_e2(self, cur_T, source, source_intensity=None, weights=None):

@@ -15,6 +15,9 @@
 //   k_color_reduce         sits where k_symm_reduce sits: behind a full search (pass.hip: pcr_rows_search, ICP's) into a match
 //   k_color_fold           buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold,
 //                          match_pass) with ColorArgs as its SIDE, COLOR_W points per lane in flight.
+//   k_color_robust         the same pass with each of the two rows weighed by a robust kernel of its own r r
+//                          (RobustSide<ColorArgs>, COLOR_ROBUST_W points per lane in flight), folded by k_color_fold
+//   k_color_residuals      both rows' r r of every scan point in the caller's order (match_residuals)
 //
 // Scan side: pcr_scan::inten, one float per point in device order.  Target side: the PtN records PlaneICP gathers and the
 // 16-byte colour records, 48 bytes per match from two arrays.
@@ -204,8 +207,8 @@ extern "C" pcr_status pcr_scan_get_intensity(pcr_scan *s, float *intensity) {
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------
 // A SIDE of match_pass.h.  Phase A carries the intensity of a scan point, phase B the PtN record of the match (two 16-byte
-// loads of one sector) and its colour record (one 16-byte load); add is the arithmetic of include/pcr.h: two rows per
-// correspondence, one count
+// loads of one sector) and its colour record (one 16-byte load); each is the arithmetic of include/pcr.h up to the two rows
+// (J, r) of a correspondence, add their plain accumulation: two rows, one count
 struct ColorArgs {
     const float *sint;       // scan intensities, device order
     const float4 *col;       // the target's colour records, cell-sorted
@@ -220,8 +223,14 @@ struct ColorArgs {
         m.q = rec[0]; m.nq = rec[1];
         m.cq = col[j];
     }
-    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
-                                        const Scan &ip, const Match &m) const {
+    typedef RowsPlain Plain;
+    typedef RowsWeighted Weighted;
+    typedef RowsResid Resid;
+    static constexpr int M = 2;
+    // the ONE statement of a correspondence: the gate, then f on the geometric row and on the colour row
+    template <typename F>
+    __device__ __forceinline__ void each(const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                         const Scan &ip, const Match &m, const F &f) const {
         float dx, dy, dz;
         if (!residual_f32<true>(a, m.q, tx, ty, tz, dx, dy, dz)) return;
         const double n0 = m.nq.x, n1 = m.nq.y, n2 = m.nq.z;
@@ -233,16 +242,18 @@ struct ColorArgs {
         double r = plane_row(P, px, py, pz, n0, n1, n2, d0, d1, d2, J);
 #pragma unroll
         for (int i = 0; i < 6; ++i) J[i] *= ag;
-        acc_rank1(acc, J, ag * r);
+        f(0, J, ag * r);
         // the colour row: the gradient's tangent part in the place of the normal, times sqrt(1 - lambda)
         const double gn = (g0 * n0 + g1 * n1) + g2 * n2;
         const double m0 = g0 - gn * n0, m1 = g1 - gn * n1, m2 = g2 - gn * n2;
         r = ((double)m.cq.x - (double)ip) + plane_row(P, px, py, pz, m0, m1, m2, d0, d1, d2, J);
 #pragma unroll
         for (int i = 0; i < 6; ++i) J[i] *= ac;
-        const double count = acc[28];                                // (acc_rank1 counts rows; out[28] counts correspondences)
-        acc_rank1(acc, J, ac * r);
-        acc[28] = count;
+        f(1, J, ac * r);                                             // (a second row does not count: out[28] counts correspondences)
+    }
+    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                        const Scan &ip, const Match &m) const {
+        each(a, P, x, y, z, tx, ty, tz, ip, m, Plain(acc, P, x, y, z));
     }
 };
 
@@ -255,16 +266,46 @@ struct ColorArgs {
 __global__ void __launch_bounds__(256) k_color_reduce(const LinArgs a, const ColorArgs ca) { match_reduce<COLOR_W>(a, ca); }
 __global__ void __launch_bounds__(64) k_color_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-// search + the coloured pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
-// too); params: two doubles, lambda_pair's sqrt(lambda) and sqrt(1 - lambda) of the call
-static pcr_status pcr_run_color(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
+// the pass under a robust weight per row (include/pcr.h: "robust kernels"): the same three phases, fold and grid; for its
+// registers and COLOR_ROBUST_W see docs/EXPERIMENTS.md
+#ifndef COLOR_ROBUST_W
+#define COLOR_ROBUST_W 2
+#endif
+__global__ void __launch_bounds__(256) k_color_robust(const LinArgs a, const RobustSide<ColorArgs> ca) { match_reduce<COLOR_ROBUST_W>(a, ca); }
+// the squared residuals of both rows of every scan point in the caller's order, +inf where there is no correspondence
+__global__ void __launch_bounds__(256) k_color_residuals(const LinArgs a, const ColorArgs ca, const uint32_t *order, double *out) {
+    match_residuals(a, ca, order, out);
+}
+
+static pcr_status check_color_payloads(const pcr_target *t, const pcr_scan *s) {
     if (t->is_voxel) { pcr_set_error("ColoredICP needs a point target"); return PCR_ERR_NO_TARGET; }
     if (!t->pn) { pcr_set_error("ColoredICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
     if (!t->col) { pcr_set_error("ColoredICP target has no colour records (pcr_target_set_intensity; replacing the normals frees them)"); return PCR_ERR_NO_TARGET; }
     if (!s->inten) { pcr_set_error("ColoredICP scan has no intensities (pcr_scan_set_intensity)"); return PCR_ERR_NO_TARGET; }
+    return PCR_OK;
+}
+
+// search + the coloured pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
+// too); params: two doubles, lambda_pair's sqrt(lambda) and sqrt(1 - lambda) of the call
+static pcr_status pcr_run_color(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
+    PCR_TRY(check_color_payloads(t, s));
     const double *w = (const double *)params;
     const ColorArgs ca{s->inten, t->col, w[0], w[1], nullptr};
     return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_reduce", k_color_reduce, k_color_fold, ca, out);
+}
+
+// the same under a robust weight; params: the two factors and the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
+struct ColorRobustParams {
+    double w[2];
+    RobustK rb;
+};
+static pcr_status pcr_run_color_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
+                                       double out[29]) {
+    const ColorRobustParams *p = (const ColorRobustParams *)params;
+    if (p->rb.kind == PCR_ROBUST_NONE) return pcr_run_color(t, s, kind, T, max_dist, flags, p->w, out);
+    PCR_TRY(check_color_payloads(t, s));
+    const RobustSide<ColorArgs> ca{{s->inten, t->col, p->w[0], p->w[1], nullptr}, p->rb};
+    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_robust", k_color_robust, k_color_fold, ca, out);
 }
 
 // sqrt(lambda) and sqrt(1 - lambda), once, in double
@@ -292,4 +333,38 @@ extern "C" pcr_status pcr_color_align(pcr_target *t, pcr_scan *s, const double T
     PCR_TRY(lambda_pair(lambda_geometric, w));
     CtxScope scope(t->ctx);
     return pcr_align_host_loop(pcr_run_color, t, s, PCR_ICP, w, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
+extern "C" pcr_status pcr_color_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                                 const pcr_robust *rb, unsigned flags, double out[29]) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    ColorRobustParams p;
+    PCR_TRY(lambda_pair(lambda_geometric, p.w));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return pcr_run_color_robust(t, s, PCR_ICP, T, max_dist, flags, &p, out);
+}
+
+extern "C" pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             double lambda_geometric, const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
+                                             double *trace_or_null) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    ColorRobustParams p;
+    PCR_TRY(lambda_pair(lambda_geometric, p.w));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(pcr_run_color_robust, t, s, PCR_ICP, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+extern "C" pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                          unsigned flags, double *s_out) {
+    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
+    double w[2];
+    PCR_TRY(lambda_pair(lambda_geometric, w));
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
+    CtxScope scope(t->ctx);
+    PCR_TRY(check_color_payloads(t, s));
+    const ColorArgs ca{s->inten, t->col, w[0], w[1], nullptr};
+    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_residuals", k_color_residuals, ca, s_out);
 }

@@ -13,6 +13,9 @@
 //                     per lane in flight.  The correspondence is ICP's (xform, the matched PtF, residual_f32<true>), the sums
 //                     are acc_ndt's with M6 from icov_closed_form: nothing is restated here.
 //   k_gicp_scov_perm  the scan's covariances between caller and device order: ScanPayload<6> (scan_payload.h)
+//   k_gicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<GicpArgs>, GICP_ROBUST_W
+//                     points per lane in flight), folded by k_gicp_fold
+//   k_gicp_residuals  d^T M d of every scan point in the caller's order (match_residuals)
 //
 // Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
 // correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line); its
@@ -233,10 +236,26 @@ struct GicpArgs : DistSide<GicpArgs> {
 __global__ void __launch_bounds__(256) k_gicp_reduce(const LinArgs a, const GicpArgs ga) { match_reduce<GICP_W>(a, ga); }
 __global__ void __launch_bounds__(64) k_gicp_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-// search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is ICP's
-static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
+// the pass under a robust weight (include/pcr.h: "robust kernels"): the same three phases, fold and grid; for its registers
+// and GICP_ROBUST_W see docs/EXPERIMENTS.md
+#ifndef GICP_ROBUST_W
+#define GICP_ROBUST_W GICP_W
+#endif
+__global__ void __launch_bounds__(256) k_gicp_robust(const LinArgs a, const RobustSide<GicpArgs> ga) { match_reduce<GICP_ROBUST_W>(a, ga); }
+// d^T M d of every scan point in the caller's order, +inf where there is no correspondence
+__global__ void __launch_bounds__(256) k_gicp_residuals(const LinArgs a, const GicpArgs ga, const uint32_t *order, double *out) {
+    match_residuals(a, ga, order, out);
+}
+
+static pcr_status check_gicp_payloads(const pcr_target *t, const pcr_scan *s) {
     if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+    return PCR_OK;
+}
+
+// search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is ICP's
+static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
+    PCR_TRY(check_gicp_payloads(t, s));
     const GicpArgs ga{{s->cov}, (const GicpRec *)t->gcov, nullptr};
     return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_reduce", k_gicp_reduce, k_gicp_fold, ga, out);
 }
@@ -253,4 +272,42 @@ extern "C" pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
     return pcr_align_host_loop(pcr_run_gicp, t, s, PCR_ICP, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
+// params of the robust pcr_pass_fn: the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
+static pcr_status pcr_run_gicp_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
+                                      double out[29]) {
+    const RobustK *rb = (const RobustK *)params;
+    if (rb->kind == PCR_ROBUST_NONE) return pcr_run_gicp(t, s, kind, T, max_dist, flags, nullptr, out);
+    PCR_TRY(check_gicp_payloads(t, s));
+    const RobustSide<GicpArgs> ga{{{s->cov}, (const GicpRec *)t->gcov, nullptr}, *rb};
+    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_robust", k_gicp_robust, k_gicp_fold, ga, out);
+}
+
+extern "C" pcr_status pcr_gicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
+                                                unsigned flags, double out[29]) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    RobustK k;
+    PCR_TRY(robust_args(rb, &k));
+    CtxScope scope(t->ctx);
+    return pcr_run_gicp_robust(t, s, PCR_ICP, T, max_dist, flags, &k, out);
+}
+
+extern "C" pcr_status pcr_gicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                            const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    RobustK k;
+    PCR_TRY(robust_args(rb, &k));
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(pcr_run_gicp_robust, t, s, PCR_ICP, &k, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+extern "C" pcr_status pcr_gicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
+    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
+    CtxScope scope(t->ctx);
+    PCR_TRY(check_gicp_payloads(t, s));
+    const GicpArgs ga{{s->cov}, (const GicpRec *)t->gcov, nullptr};
+    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_residuals", k_gicp_residuals, ga, s_out);
 }

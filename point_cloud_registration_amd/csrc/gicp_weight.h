@@ -4,7 +4,7 @@
 #pragma once
 
 #include "eigen3.h"
-#include "pass_device.h"
+#include "match_pass.h"
 
 // the plane regulariser C = I - (1 - eps) n n^T as xx xy xz yy yz zz: eigenvalues (eps, 1, 1); the sign of n cancels
 __device__ __forceinline__ void plane_cov6(const double n[3], double eps, double c[6]) {
@@ -39,8 +39,53 @@ __device__ __forceinline__ void gicp_weight(const PoseK &P, const float cp[6], c
     m6[0] = o[0]; m6[1] = o[1]; m6[2] = o[2]; m6[3] = o[4]; m6[4] = o[5]; m6[5] = o[8];
 }
 
+// s = d^T M d of include/pcr.h: Md_i = (M_i0 d_0 + M_i1 d_1) + M_i2 d_2, s = (d_0 Md_0 + d_1 Md_1) + d_2 Md_2
+__device__ __forceinline__ double dist_s(const double m6[6], double d0, double d1, double d2) {
+    const double c0 = (m6[0] * d0 + m6[1] * d1) + m6[2] * d2;
+    const double c1 = (m6[1] * d0 + m6[3] * d1) + m6[4] * d2;
+    const double c2 = (m6[2] * d0 + m6[4] * d1) + m6[5] * d2;
+    return (d0 * c0 + d1 * c1) + d2 * c2;
+}
+
+// The three f of a distribution SIDE (match_pass.h): f(M6, d).  Plain: acc_ndt.  Weighted: acc_ndt with w M in the place of M,
+// w = robust_weight(d^T M d), one product per entry.  Resid: d^T M d
+struct DistPlain {
+    double *acc;
+    const PoseK &P;
+    float x, y, z;
+    __device__ __forceinline__ DistPlain(double *acc_, const PoseK &P_, float x_, float y_, float z_) : acc(acc_), P(P_), x(x_), y(y_), z(z_) {}
+    template <typename RES>                          // (the residual is widened where acc_ndt takes it, as the coordinates are)
+    __device__ __forceinline__ void operator()(const double m6[6], RES d0, RES d1, RES d2) const {
+        acc_ndt(acc, P, (double)x, (double)y, (double)z, m6, (double)d0, (double)d1, (double)d2);
+    }
+};
+struct DistWeighted {
+    double *acc;
+    const PoseK &P;
+    float x, y, z;
+    const RobustK &rb;
+    __device__ __forceinline__ DistWeighted(double *acc_, const PoseK &P_, float x_, float y_, float z_, const RobustK &rb_)
+        : acc(acc_), P(P_), x(x_), y(y_), z(z_), rb(rb_) {}
+    template <typename RES>
+    __device__ __forceinline__ void operator()(const double m6[6], RES r0, RES r1, RES r2) const {
+        const double d0 = r0, d1 = r1, d2 = r2;
+        const double w = robust_weight(rb, dist_s(m6, d0, d1, d2));
+        double wm[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) wm[k] = w * m6[k];
+        acc_ndt(acc, P, (double)x, (double)y, (double)z, wm, d0, d1, d2);
+    }
+};
+struct DistResid {
+    double *s;
+    __device__ __forceinline__ DistResid(double *s_, const PoseK &, float, float, float) : s(s_) {}
+    template <typename RES>
+    __device__ __forceinline__ void operator()(const double m6[6], RES d0, RES d1, RES d2) const { s[0] = dist_s(m6, (double)d0, (double)d1, (double)d2); }
+};
+
 // What the two SIDEs of match_pass.h with a covariance on the scan share: the scan covariance through phase A as three
-// float2, and residual -> weight -> acc_ndt (with M6).  D (GicpArgs, VgicpArgs) adds the target side:
+// float2, and the ONE statement of a correspondence, each: residual -> weight -> f(M6, d).  D (GicpArgs, VgicpArgs) adds the
+// target side:
 //   Match, gather             (match_pass.h)
 //   Res                       the type of the residual (float / double)
 //   residual(a, m, t.., d..)  residual_f32<true> / residual_f64<true> on the gathered match: residual and gate
@@ -54,16 +99,25 @@ struct DistSide {
         const float2 *c = reinterpret_cast<const float2 *>(scov + 6 * i);
         s.c[0] = c[0]; s.c[1] = c[1]; s.c[2] = c[2];
     }
-    template <typename MATCH>
-    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
-                                        const Scan &s, const MATCH &m) const {
+    typedef DistPlain Plain;
+    typedef DistWeighted Weighted;
+    typedef DistResid Resid;
+    static constexpr int M = 1;
+    template <typename MATCH, typename F>
+    __device__ __forceinline__ void each(const LinArgs &a, const PoseK &P, float, float, float, float tx, float ty, float tz,
+                                         const Scan &s, const MATCH &m, const F &f) const {
         const D &d = static_cast<const D &>(*this);
         typename D::Res dx, dy, dz;
         if (!d.residual(a, m, tx, ty, tz, dx, dy, dz)) return;
         const float cpv[6] = {s.c[0].x, s.c[0].y, s.c[1].x, s.c[1].y, s.c[2].x, s.c[2].y};
         double m6[6];
         d.weight(P, cpv, m, m6);
-        acc_ndt(acc, P, (double)x, (double)y, (double)z, m6, (double)dx, (double)dy, (double)dz);
+        f(m6, dx, dy, dz);
+    }
+    template <typename MATCH>
+    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                        const Scan &s, const MATCH &m) const {
+        each(a, P, x, y, z, tx, ty, tz, s, m, Plain(acc, P, x, y, z));
     }
 };
 

@@ -7,12 +7,89 @@
 //   load(i, Scan&)            the loads of scan point i (device order); nothing else
 //   Match                     what phase B carries per correspondence
 //   gather(a, j, Match&)      the loads of one match at cell-sorted index j; nothing else
+//   each(a, P, x, y, z, tx, ty, tz, scan, match, f)
+//                             what ONE correspondence yields, stated once: residual and gates, then f on its row(s) (J, r) or on
+//                             (M, d); nothing is handed to f when a gate drops the correspondence; (tx, ty, tz) = xform(P, x, y, z)
+//   Plain, Weighted, Resid    the three f: the sums of the plain pass, the sums under a robust weight, the squared residual(s)
+//   M                         squared residuals per correspondence (1; ColoredICP 2)
 //   add(acc, a, P, x, y, z, tx, ty, tz, scan, match)
-//                             residual, gate and sums of one correspondence; (tx, ty, tz) = xform(P, x, y, z)
+//                             each with Plain.  RobustSide<SIDE> is the SIDE whose add is each with Weighted
 #pragma once
+
+#include <math.h>
 
 #include "host_util.h"
 #include "pass_device.h"
+
+// ---- robust weights (include/pcr.h: "robust kernels") ---------------------------------------------------------------------
+// kind, c and c2 = c * c (taken once on the host) travel by value
+struct RobustK {
+    int kind;
+    double c, c2;
+};
+
+// w(s): float64, nothing contracted.  The switch is wave-uniform: kind is a kernel argument
+__device__ __forceinline__ double robust_weight(const RobustK &rb, double s) {
+    switch (rb.kind) {
+    case PCR_ROBUST_HUBER: return s <= rb.c2 ? 1.0 : rb.c / __builtin_sqrt(s);
+    case PCR_ROBUST_CAUCHY: return 1.0 / (1.0 + s / rb.c2);
+    case PCR_ROBUST_TUKEY: { const double u = 1.0 - s / rb.c2; return s <= rb.c2 ? u * u : 0.0; }
+    default: { const double l = rb.c2 / (rb.c2 + s); return l * l; }                  // PCR_ROBUST_GM
+    }
+}
+
+// acc_rank1 under a weight: Jw = w J and rw = w r, one product each, then acc_rank1's fmas with them on the left
+__device__ __forceinline__ void acc_rank1_w(double *acc, const double J[6], double r, double w) {
+    double Jw[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Jw[i] = w * J[i];
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) { acc[p] = fma(Jw[i], J[j], acc[p]); ++p; }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] = fma(Jw[i], r, acc[21 + i]);
+    acc[27] = fma(w * r, r, acc[27]);
+    acc[28] += 1.0;
+}
+
+// The three f of a SIDE of rows (symm.hip, color.hip): f(row, J, r), rows in order.  acc_rank1 counts rows and out[28] counts
+// correspondences: a row past the first puts the count back
+struct RowsPlain {
+    double *acc;
+    __device__ __forceinline__ RowsPlain(double *acc_, const PoseK &, float, float, float) : acc(acc_) {}
+    __device__ __forceinline__ void operator()(int row, const double J[6], double r) const {
+        const double count = acc[28];
+        acc_rank1(acc, J, r);
+        if (row > 0) acc[28] = count;
+    }
+};
+struct RowsWeighted {
+    double *acc;
+    const RobustK &rb;
+    __device__ __forceinline__ RowsWeighted(double *acc_, const PoseK &, float, float, float, const RobustK &rb_) : acc(acc_), rb(rb_) {}
+    __device__ __forceinline__ void operator()(int row, const double J[6], double r) const {
+        const double count = acc[28];
+        acc_rank1_w(acc, J, r, robust_weight(rb, r * r));
+        if (row > 0) acc[28] = count;
+    }
+};
+struct RowsResid {
+    double *s;
+    __device__ __forceinline__ RowsResid(double *s_, const PoseK &, float, float, float) : s(s_) {}
+    __device__ __forceinline__ void operator()(int row, const double *, double r) const { s[row] = r * r; }
+};
+
+// the SIDE whose add weighs every correspondence
+template <typename SIDE>
+struct RobustSide : SIDE {
+    RobustK rb;
+    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                        const typename SIDE::Scan &s, const typename SIDE::Match &m) const {
+        this->each(a, P, x, y, z, tx, ty, tz, s, m, typename SIDE::Weighted(acc, P, x, y, z, rb));
+    }
+};
 
 // W points per lane in flight, the phases of reduce_stream (pass_device.h):
 //   phase A  index, coordinates and Scan of all W points.  A point past the end reads the lane's first point.
@@ -76,6 +153,34 @@ __device__ __forceinline__ void match_fold(const double *__restrict__ rows, int 
     out[e] = s;
 }
 
+// The sibling of match_reduce that writes instead of accumulating: SIDE::M squared residuals per scan point, +inf where the
+// point has no match or a gate drops it, at the point's CALLER index through `order` (pcr_scan::order; NULL: the device order
+// is the caller's), as k_rows scatters.  One point per lane and trip: nothing is folded, nothing depends on the grid
+template <typename SIDE>
+__device__ __forceinline__ void match_residuals(const LinArgs &a, const SIDE &sd, const uint32_t *__restrict__ order, double *__restrict__ out) {
+    const PoseK &P = a.hp;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += stride) {
+        double s[SIDE::M];
+#pragma unroll
+        for (int k = 0; k < SIDE::M; ++k) s[k] = (double)INFINITY;
+        const uint32_t j = a.nn_j[i];
+        if (j != PCR_NONE) {
+            const float x = a.sx[i], y = a.sy[i], z = a.sz[i];
+            typename SIDE::Scan sc;
+            typename SIDE::Match m;
+            sd.load(i, sc);
+            sd.gather(a, j, m);
+            float tx, ty, tz;
+            xform(P, x, y, z, tx, ty, tz);
+            sd.each(a, P, x, y, z, tx, ty, tz, sc, m, typename SIDE::Resid(s, P, x, y, z));
+        }
+        const int64_t dest = order ? (int64_t)order[i] : i;
+#pragma unroll
+        for (int k = 0; k < SIDE::M; ++k) out[SIDE::M * dest + k] = s[k];
+    }
+}
+
 // reduce + fold + 29 doubles back behind a search into `a`: one stream synchronisation, device blocks from the context's
 // block cache.  sd comes with everything but rows set.
 template <typename SIDE>
@@ -108,4 +213,39 @@ static pcr_status match_pass(pcr_target *t, pcr_scan *s, int kind, const double 
     for (int i = 0; i < 29; ++i) out[i] = 0.0;
     if (s->n == 0) return PCR_OK;
     return match_launch(t->ctx, range_name, reduce, fold, a, sd, s->n, out);
+}
+
+// ---- robust passes and residuals: the host side the four units share --------------------------------------------------------
+// the caller's pcr_robust -> RobustK.  NULL or PCR_ROBUST_NONE: the plain pass (kind 0; the scale is not read)
+static inline pcr_status robust_args(const pcr_robust *rb, RobustK *k) {
+    k->kind = PCR_ROBUST_NONE; k->c = 1.0; k->c2 = 1.0;
+    if (!rb || rb->kind == PCR_ROBUST_NONE) return PCR_OK;
+    PCR_REQUIRE(rb->kind >= PCR_ROBUST_HUBER && rb->kind <= PCR_ROBUST_GM, "robust kind must be one of PCR_ROBUST_*");
+    const double c = rb->scale, c2 = c * c;
+    PCR_REQUIRE(c > 0.0 && isfinite(c) && c2 > 0.0 && isfinite(c2), "robust scale must be finite and > 0, and so must its square");   // (false for NaN)
+    k->kind = rb->kind; k->c = c; k->c2 = c2;
+    return PCR_OK;
+}
+
+// What a *_residuals entry point does once the unit has checked its payloads: kind's full search, as match_pass, and the
+// residual kernel into SIDE::M doubles per scan point in the caller's order
+template <typename SIDE>
+static pcr_status match_residuals_run(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
+                                      const char *range_name, void (*resid)(const LinArgs, const SIDE, const uint32_t *, double *),
+                                      const SIDE &sd, double *s_out) {
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, kind, T, max_dist, flags, true));
+    if (s->n == 0) return PCR_OK;
+    pcr_context *ctx = t->ctx;
+    DevBuf<double> d;
+    HIP_TRY(d.alloc(SIDE::M * (size_t)s->n));
+    {
+        RoctxRange range(range_name);
+        hipLaunchKernelGGL(resid, dim3((unsigned)choose_blocks(ctx, s->n)), dim3(256), 0, ctx->stream, a, sd, (const uint32_t *)s->order, d.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s_out, d.p, SIDE::M * (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
 }

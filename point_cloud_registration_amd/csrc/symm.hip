@@ -11,6 +11,9 @@
 //   k_symm_reduce        sits where k_gicp_reduce sits: behind a full search (pass.hip: pcr_rows_search, ICP's) into a match
 //   k_symm_fold          buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold, match_pass)
 //                        with SymmArgs as its SIDE, SYMM_W points per lane in flight.
+//   k_symm_robust        the same pass with every correspondence weighed by a robust kernel of r r (RobustSide<SymmArgs>,
+//                        SYMM_ROBUST_W points per lane in flight), folded by k_symm_fold
+//   k_symm_residuals     r r of every scan point in the caller's order (match_residuals)
 //
 // Scan side: pcr_scan::nrm, three floats per point in device order (12 bytes beside the 16 of index and coordinates).  Target
 // side: the PtN records PlaneICP gathers -- point and normal in one 32-byte sector.
@@ -81,7 +84,7 @@ extern "C" pcr_status pcr_scan_get_normals(pcr_scan *s, float *normals) {
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------
 // A SIDE of match_pass.h.  Phase A carries the three normal floats of a scan point, phase B the PtN record of the match (two
-// 16-byte loads of one sector); add is the arithmetic of include/pcr.h
+// 16-byte loads of one sector); each is the arithmetic of include/pcr.h up to the row (J, r), add its plain accumulation
 struct SymmArgs {
     const float *snrm;       // scan normals, device order, 3 floats per point
     double min_cos;          // normal gate: kept iff |n_q . R n_p| >= min_cos
@@ -97,8 +100,14 @@ struct SymmArgs {
         const float4 *rec = reinterpret_cast<const float4 *>(a.pn + j);
         m.q = rec[0]; m.nq = rec[1];
     }
-    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
-                                        const Scan &s, const Match &m) const {
+    typedef RowsPlain Plain;
+    typedef RowsWeighted Weighted;
+    typedef RowsResid Resid;
+    static constexpr int M = 1;
+    // the ONE statement of a correspondence: both gates, then f on its row
+    template <typename F>
+    __device__ __forceinline__ void each(const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                         const Scan &s, const Match &m, const F &f) const {
         float dx, dy, dz;
         if (!residual_f32<true>(a, m.q, tx, ty, tz, dx, dy, dz)) return;
         const double px = s.nx, py = s.ny, pz = s.nz;
@@ -112,7 +121,11 @@ struct SymmArgs {
         const double m0 = 0.5 * (q0 + sg * v0), m1 = 0.5 * (q1 + sg * v1), m2 = 0.5 * (q2 + sg * v2);
         double J[6];
         const double r = plane_row(P, (double)x, (double)y, (double)z, m0, m1, m2, (double)dx, (double)dy, (double)dz, J);
-        acc_rank1(acc, J, r);
+        f(0, J, r);
+    }
+    __device__ __forceinline__ void add(double *acc, const LinArgs &a, const PoseK &P, float x, float y, float z, float tx, float ty, float tz,
+                                        const Scan &s, const Match &m) const {
+        each(a, P, x, y, z, tx, ty, tz, s, m, Plain(acc, P, x, y, z));
     }
 };
 
@@ -125,19 +138,51 @@ struct SymmArgs {
 __global__ void __launch_bounds__(256) k_symm_reduce(const LinArgs a, const SymmArgs sa) { match_reduce<SYMM_W>(a, sa); }
 __global__ void __launch_bounds__(64) k_symm_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
+// the pass under a robust weight (include/pcr.h: "robust kernels"): the same three phases, fold and grid.  The weight (a
+// float64 divide and square root, w J beside J) does not fit beside the 32 sums within the 128 registers of four waves per
+// SIMD at any width -- forced there it spills -- so the kernel runs at three waves, where k_gicp_reduce runs: 2 points in
+// flight need 162 registers, 3 need 174 and would drop to two waves (docs/EXPERIMENTS.md)
+#ifndef SYMM_ROBUST_W
+#define SYMM_ROBUST_W 2
+#endif
+__global__ void __launch_bounds__(256) k_symm_robust(const LinArgs a, const RobustSide<SymmArgs> sa) { match_reduce<SYMM_ROBUST_W>(a, sa); }
+// r * r of every scan point in the caller's order, +inf where there is no correspondence
+__global__ void __launch_bounds__(256) k_symm_residuals(const LinArgs a, const SymmArgs sa, const uint32_t *order, double *out) {
+    match_residuals(a, sa, order, out);
+}
+
 static pcr_status check_min_cos(double min_cos) {
     PCR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must be in [0, 1]");      // (false for NaN)
+    return PCR_OK;
+}
+
+static pcr_status check_symm_payloads(const pcr_target *t, const pcr_scan *s) {
+    if (t->is_voxel) { pcr_set_error("SymmetricICP needs a point target"); return PCR_ERR_NO_TARGET; }
+    if (!t->pn) { pcr_set_error("SymmetricICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
+    if (!s->nrm) { pcr_set_error("SymmetricICP scan has no normals (pcr_scan_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
     return PCR_OK;
 }
 
 // search + the symmetric pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
 // too: pass.hip, pass_fill_lin); params: one double, the normal gate min_cos of the call
 static pcr_status pcr_run_symm(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
-    if (t->is_voxel) { pcr_set_error("SymmetricICP needs a point target"); return PCR_ERR_NO_TARGET; }
-    if (!t->pn) { pcr_set_error("SymmetricICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
-    if (!s->nrm) { pcr_set_error("SymmetricICP scan has no normals (pcr_scan_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
+    PCR_TRY(check_symm_payloads(t, s));
     const SymmArgs sa{s->nrm, *(const double *)params, nullptr};
     return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_reduce", k_symm_reduce, k_symm_fold, sa, out);
+}
+
+// the same under a robust weight; params: min_cos and the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
+struct SymmRobustParams {
+    double min_cos;
+    RobustK rb;
+};
+static pcr_status pcr_run_symm_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
+                                      double out[29]) {
+    const SymmRobustParams *p = (const SymmRobustParams *)params;
+    if (p->rb.kind == PCR_ROBUST_NONE) return pcr_run_symm(t, s, kind, T, max_dist, flags, &p->min_cos, out);
+    PCR_TRY(check_symm_payloads(t, s));
+    const RobustSide<SymmArgs> sa{{s->nrm, p->min_cos, nullptr}, p->rb};
+    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_robust", k_symm_robust, k_symm_fold, sa, out);
 }
 
 extern "C" pcr_status pcr_symm_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
@@ -155,4 +200,37 @@ extern "C" pcr_status pcr_symm_align(pcr_target *t, pcr_scan *s, const double T_
     PCR_TRY(check_min_cos(min_cos));
     CtxScope scope(t->ctx);
     return pcr_align_host_loop(pcr_run_symm, t, s, PCR_ICP, &min_cos, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
+extern "C" pcr_status pcr_symm_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos,
+                                                const pcr_robust *rb, unsigned flags, double out[29]) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    SymmRobustParams p{min_cos, {}};
+    PCR_TRY(check_min_cos(min_cos));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return pcr_run_symm_robust(t, s, PCR_ICP, T, max_dist, flags, &p, out);
+}
+
+extern "C" pcr_status pcr_symm_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                            double min_cos, const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
+                                            double *trace_or_null) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    SymmRobustParams p{min_cos, {}};
+    PCR_TRY(check_min_cos(min_cos));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(pcr_run_symm_robust, t, s, PCR_ICP, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+extern "C" pcr_status pcr_symm_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
+                                         double *s_out) {
+    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
+    PCR_TRY(check_min_cos(min_cos));
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
+    CtxScope scope(t->ctx);
+    PCR_TRY(check_symm_payloads(t, s));
+    const SymmArgs sa{s->nrm, min_cos, nullptr};
+    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_residuals", k_symm_residuals, sa, s_out);
 }

@@ -12,6 +12,9 @@
 //                      list of match_pass.h (match_reduce, match_fold, match_pass) with VgicpArgs as its SIDE -- the scan side
 //                      and the sums are DistSide's (gicp_weight.h), shared with gicp.hip -- VGICP_W points per lane in flight:
 //                      residual_f64<true> on the gathered centroid, gicp_weight, acc_ndt -- nothing is restated here.
+//   k_vgicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<VgicpArgs>,
+//   k_vgicp_residuals  VGICP_ROBUST_W points per lane in flight), folded by k_vgicp_fold; d^T M d of every scan point in the
+//                      caller's order (match_residuals)
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -129,11 +132,27 @@ struct VgicpArgs : DistSide<VgicpArgs> {
 __global__ void __launch_bounds__(256) k_vgicp_reduce(const LinArgs a, const VgicpArgs va) { match_reduce<VGICP_W>(a, va); }
 __global__ void __launch_bounds__(64) k_vgicp_fold(const double *__restrict__ rows, int nb, double *out) { match_fold(rows, nb, out); }
 
-// centroid search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is VPlaneICP's
-static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
+// the pass under a robust weight (include/pcr.h: "robust kernels"): the same three phases, fold and grid; for its registers
+// and VGICP_ROBUST_W see docs/EXPERIMENTS.md
+#ifndef VGICP_ROBUST_W
+#define VGICP_ROBUST_W VGICP_W
+#endif
+__global__ void __launch_bounds__(256) k_vgicp_robust(const LinArgs a, const RobustSide<VgicpArgs> va) { match_reduce<VGICP_ROBUST_W>(a, va); }
+// d^T M d of every scan point in the caller's order, +inf where there is no correspondence
+__global__ void __launch_bounds__(256) k_vgicp_residuals(const LinArgs a, const VgicpArgs va, const uint32_t *order, double *out) {
+    match_residuals(a, va, order, out);
+}
+
+static pcr_status check_vgicp_payloads(const pcr_target *t, const pcr_scan *s) {
     if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
     if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
     if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+    return PCR_OK;
+}
+
+// centroid search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is VPlaneICP's
+static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
+    PCR_TRY(check_vgicp_payloads(t, s));
     pcr_context *ctx = t->ctx;
     for (int i = 0; i < 29; ++i) out[i] = 0.0;
     if (t->n == 0) {                                 // no kept voxel: no match (and no voxel 0 for the select of phase B)
@@ -158,4 +177,48 @@ extern "C" pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T
     PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
     CtxScope scope(t->ctx);
     return pcr_align_host_loop(pcr_run_vgicp, t, s, PCR_VPLANE, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
+// params of the robust pcr_pass_fn: the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
+static pcr_status pcr_run_vgicp_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
+                                       double out[29]) {
+    const RobustK *rb = (const RobustK *)params;
+    if (rb->kind == PCR_ROBUST_NONE || t->n == 0) return pcr_run_vgicp(t, s, kind, T, max_dist, flags, nullptr, out);   // (no kept voxel: zeros)
+    PCR_TRY(check_vgicp_payloads(t, s));
+    const RobustSide<VgicpArgs> va{{{s->cov}, t->vcov, nullptr}, *rb};
+    return match_pass(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_robust", k_vgicp_robust, k_vgicp_fold, va, out);
+}
+
+extern "C" pcr_status pcr_vgicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
+                                                 unsigned flags, double out[29]) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    RobustK k;
+    PCR_TRY(robust_args(rb, &k));
+    CtxScope scope(t->ctx);
+    return pcr_run_vgicp_robust(t, s, PCR_VPLANE, T, max_dist, flags, &k, out);
+}
+
+extern "C" pcr_status pcr_vgicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    RobustK k;
+    PCR_TRY(robust_args(rb, &k));
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(pcr_run_vgicp_robust, t, s, PCR_VPLANE, &k, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+extern "C" pcr_status pcr_vgicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
+    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
+    CtxScope scope(t->ctx);
+    PCR_TRY(check_vgicp_payloads(t, s));
+    if (t->n == 0) {                                 // no kept voxel: no match, once the plain pass's checks have passed
+        double zeros[29];
+        PCR_TRY(pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, nullptr, zeros));
+        for (int64_t i = 0; i < s->n; ++i) s_out[i] = (double)INFINITY;
+        return PCR_OK;
+    }
+    const VgicpArgs va{{s->cov}, t->vcov, nullptr};
+    return match_residuals_run(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_residuals", k_vgicp_residuals, va, s_out);
 }

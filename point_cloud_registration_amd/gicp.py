@@ -65,6 +65,9 @@ class DistributionPass(ScanCovariances, MatchPass):
         self.regularization = regularization
         self._covariance = None
 
+    def _pass_scan(self, source, source_cov=None):
+        return self._gicp_scan(source, source_cov)
+
     # -- passes ----------------------------------------------------------------------------------
     def calc_H_g_e2(self, cur_T, source, source_cov=None, weights=None):
         """Hessian (6x6), gradient (6) and squared (Mahalanobis) error at ``cur_T``.  ``source_cov``: (N, 6) or (N, 3, 3) in
@@ -103,6 +106,8 @@ class DistributionPass(ScanCovariances, MatchPass):
 
 class GICP(DistributionPass):
     _capi_linearize, _capi_align = staticmethod(_capi.gicp_linearize), staticmethod(_capi.gicp_align)
+    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.gicp_linearize_robust), staticmethod(_capi.gicp_align_robust)
+    _capi_residuals = staticmethod(_capi.gicp_residuals)
 
     # -- target ----------------------------------------------------------------------------------
     def set_target(self, target, kdree=None, cov=None):

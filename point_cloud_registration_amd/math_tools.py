@@ -24,6 +24,35 @@ def huber_weight(r, d=1.0):
     return w
 
 
+def robust_weight(kind, s, scale):
+    """The weight of a robust kernel at the squared residual(s) ``s``, the NumPy statement of ``include/pcr.h``: float64,
+    with ``c2 = scale * scale`` taken once.
+
+    ``"huber"``: ``1`` where ``s <= c2`` else ``c / sqrt(s)``;  ``"cauchy"``: ``1 / (1 + s / c2)``;
+    ``"tukey"``: ``(1 - s / c2)^2`` where ``s <= c2`` else ``0``;  ``"gm"`` (Geman-McClure): ``(c2 / (c2 + s))^2``;
+    ``None``: ones.  ``s = inf`` (no correspondence: ``MatchPass.residuals``) gives 0 -- ``None`` included, so the result
+    can go straight into ``weights=``.  ``scale`` must be finite and > 0, and so must its square."""
+    s = np.asarray(s, dtype=np.float64)
+    if kind is None:
+        return np.where(np.isinf(s), 0.0, 1.0)
+    c = float(scale)
+    c2 = c * c
+    if not (0.0 < c < np.inf and 0.0 < c2 < np.inf):
+        raise ValueError("scale must be finite and > 0, and so must its square")
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        if kind == "huber":
+            return np.where(s <= c2, 1.0, c / np.sqrt(s))
+        if kind == "cauchy":
+            return 1.0 / (1.0 + s / c2)
+        if kind == "tukey":
+            u = 1.0 - s / c2
+            return np.where(s <= c2, u * u, 0.0)
+        if kind == "gm":
+            l = c2 / (c2 + s)
+            return l * l
+    raise ValueError('kind must be None, "huber", "cauchy", "tukey" or "gm"')
+
+
 def skew(vector):
     """3x3 cross-product matrix of one vector (reference ``math_tools.py:61-64``)."""
     x, y, z = vector[0], vector[1], vector[2]

@@ -366,28 +366,58 @@ class MatchPass(Registration):
     """The driver of the aligners whose pass has entry points of its own (``GICP``, ``VGICP``, ``SymmetricICP``,
     ``ColoredICP``): one GPU of one process, ``k`` neighbours for what they estimate.  A subclass supplies its pair of ``_capi``
     entry points and ``_pass_params``, what they take between ``max_dist`` and the flags; it keeps its own ``set_target``,
-    scan preparation and ``calc_H_g_e2_no_parallel_ver``."""
+    scan preparation (``_pass_scan``) and ``calc_H_g_e2_no_parallel_ver``.
+
+    ``robust`` (``None``, ``"huber"``, ``"cauchy"``, ``"tukey"``, ``"gm"``) with ``robust_scale`` = c weighs every
+    correspondence inside the gate by a robust kernel of its squared residual (``math_tools.robust_weight``; ``include/pcr.h``
+    says what the squared residual of each class is), inside the pass: ``calc_H_g_e2`` and ``align`` then return the IRLS sums
+    and pose.  ``None`` calls exactly what the class called before there were kernels.  ``residuals`` returns the squared
+    residuals a scale can be chosen from."""
     KIND = None           # no kind of pcr_linearize
     _capi_linearize = _capi_align = None
+    _capi_linearize_robust = _capi_align_robust = _capi_residuals = None
 
-    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, **kw):
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, **kw):
         if kw.get("devices") is not None or kw.get("comm") is not None:
             raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
         if not 1 <= int(k) <= 64:
             raise ValueError("k must be in [1, 64]")
+        kind, scale = _capi.check_robust(robust, robust_scale)
         super().__init__(max_iter=max_iter, tol=tol, **kw)
         self.max_dist = max_dist
         self.k = int(k)
+        self.robust, self.robust_scale = robust, scale
+        self._robust = None if robust is None else (kind, scale)
 
     def _pass_params(self):
         return ()
 
+    def _pass_scan(self, source, *extras, **kw):
+        """The device copy of ``source`` with what the class's pass needs on it (``source_cov``, ``source_normals``, ...)."""
+        raise NotImplementedError
+
+    # (the kernel is an argument of the call, as min_cos and lambda are: nothing of it stays on the scan, which aligners share)
     def _native_linearize(self, scan, cur_T):
-        return self._capi_linearize(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), self._flags)
+        if self._robust is None:
+            return self._capi_linearize(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), self._flags)
+        return self._capi_linearize_robust(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), robust=self._robust,
+                                           flags=self._flags)
 
     def _native_align(self, scan, cur_T):
-        return self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
-                                self._flags, want_trace=True)
+        if self._robust is None:
+            return self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
+                                    self._flags, want_trace=True)
+        return self._capi_align_robust(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
+                                       robust=self._robust, flags=self._flags, want_trace=True)
+
+    def residuals(self, cur_T, source, *extras, **kw):
+        """The squared residual of every point of ``source`` at ``cur_T``, in its order, ``inf`` where the point has no
+        correspondence inside the gates: (N,) float64 -- ``ColoredICP``: (N, 2), the geometric and the colour row.  What
+        ``robust`` weighs, whatever this object's own kernel; a scale can be chosen from it (its median, say).  The per-class
+        extras (``source_cov``, ``source_normals``, ``source_intensity``) are taken exactly as ``calc_H_g_e2`` takes them."""
+        scan = self._pass_scan(source, *extras, **kw)
+        return self._capi_residuals(self._target, scan, np.asarray(cur_T, dtype=np.float64), self._max_dist(), *self._pass_params(),
+                                    flags=self._flags)
 
     # -- out of scope ----------------------------------------------------------------------------
     def _unsupported(self, what):

@@ -21,6 +21,8 @@ from .registration import MatchPass
 
 class SymmetricICP(MatchPass):
     _capi_linearize, _capi_align = staticmethod(_capi.symm_linearize), staticmethod(_capi.symm_align)
+    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.symm_linearize_robust), staticmethod(_capi.symm_align_robust)
+    _capi_residuals = staticmethod(_capi.symm_residuals)
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, min_normal_cos=0.0, **kw):
         super().__init__(max_iter, max_dist, tol, k, **kw)
@@ -91,6 +93,9 @@ class SymmetricICP(MatchPass):
                 scan.estimate_normals(self.k, want=False)
                 scan._symm_nrm = tag
         return scan
+
+    def _pass_scan(self, source, source_normals=None):
+        return self._symm_scan(source, source_normals)
 
     # -- passes ----------------------------------------------------------------------------------
     def calc_H_g_e2(self, cur_T, source, source_normals=None, weights=None):
