@@ -1379,69 +1379,17 @@ def cov6_f64(cov):
     return cov6(cov, np.float64)
 
 
-def _linearize29(entry, target, scan, T, max_dist, flags):
-    """entry(target, scan, T, max_dist, flags, out) -> the 29 sums of one pass (see include/pcr.h)."""
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-    out = np.empty(29)
-    check(entry(target.handle, scan.handle, T, float(max_dist), int(flags), out))
-    return out
-
-
-def _align(entry, head, T_init, max_iter, tol, max_dist, flags, want_trace):
-    """entry(*head, T_init, max_iter, tol, max_dist, flags, T_out, &iterations, trace) -> (T, iterations[, trace rows])."""
+def _align(entry, head, T_init, max_iter, tol, max_dist, flags, want_trace, mid=()):
+    """entry(*head, T_init, max_iter, tol, max_dist, *mid, flags, T_out, &iterations, trace) -> (T, iterations[, trace rows])."""
     T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
     T = np.zeros(16)
     iters = C.c_int(0)
     trace = np.zeros((max(int(max_iter), 1), 45)) if want_trace else None
-    check(entry(*head, T0, int(max_iter), float(tol), float(max_dist), int(flags), T, C.byref(iters), _ptr(trace)))
+    check(entry(*head, T0, int(max_iter), float(tol), float(max_dist), *mid, int(flags), T, C.byref(iters), _ptr(trace)))
     T = T.reshape(4, 4)
     if want_trace:
         return T, iters.value, trace[:iters.value]
     return T, iters.value
-
-
-def gicp_linearize(target, scan, T, max_dist, flags=0):
-    """pcr_gicp_linearize -> the 29 sums of one GICP pass."""
-    return _linearize29(lib().pcr_gicp_linearize, target, scan, T, max_dist, flags)
-
-
-def gicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
-    """pcr_gicp_align: the host-driven Gauss-Newton loop over pcr_gicp_linearize, behind the boundary."""
-    return _align(lib().pcr_gicp_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
-
-
-def vgicp_linearize(target, scan, T, max_dist, flags=0):
-    """pcr_vgicp_linearize -> the 29 sums of one VGICP pass."""
-    return _linearize29(lib().pcr_vgicp_linearize, target, scan, T, max_dist, flags)
-
-
-def vgicp_align(target, scan, T_init, max_iter, tol, max_dist, flags=0, want_trace=False):
-    """pcr_vgicp_align: the host-driven Gauss-Newton loop over pcr_vgicp_linearize, behind the boundary."""
-    return _align(lib().pcr_vgicp_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
-
-
-def symm_linearize(target, scan, T, max_dist, min_cos=0.0, flags=0):
-    """pcr_symm_linearize -> the 29 sums of one symmetric point-to-plane pass."""
-    entry = lambda t, s, T, md, fl, out: lib().pcr_symm_linearize(t, s, T, md, float(min_cos), fl, out)
-    return _linearize29(entry, target, scan, T, max_dist, flags)
-
-
-def symm_align(target, scan, T_init, max_iter, tol, max_dist, min_cos=0.0, flags=0, want_trace=False):
-    """pcr_symm_align: the host-driven Gauss-Newton loop over pcr_symm_linearize, behind the boundary."""
-    entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_symm_align(t, s, T0, it, tol, md, float(min_cos), *rest)
-    return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
-
-
-def color_linearize(target, scan, T, max_dist, lambda_geometric=0.968, flags=0):
-    """pcr_color_linearize -> the 29 sums of one coloured pass (two rows per correspondence, out[28] counts correspondences)."""
-    entry = lambda t, s, T, md, fl, out: lib().pcr_color_linearize(t, s, T, md, float(lambda_geometric), fl, out)
-    return _linearize29(entry, target, scan, T, max_dist, flags)
-
-
-def color_align(target, scan, T_init, max_iter, tol, max_dist, lambda_geometric=0.968, flags=0, want_trace=False):
-    """pcr_color_align: the host-driven Gauss-Newton loop over pcr_color_linearize, behind the boundary."""
-    entry = lambda t, s, T0, it, tol, md, *rest: lib().pcr_color_align(t, s, T0, it, tol, md, float(lambda_geometric), *rest)
-    return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
 
 
 # ---- robust kernels inside the pass of the four match-list aligners (include/pcr.h) ----------------------------------
@@ -1473,62 +1421,88 @@ def _rb(robust):
     return C.cast(C.pointer(rb), _vp), rb
 
 
-def _extras(args, extra):
-    if len(args) != extra:
-        raise TypeError(f"expected {extra} pass parameter(s) after max_dist, got {len(args)}")
-    return tuple(float(v) for v in args)
+# ---- the entry points of the four match-list aligners (include/pcr.h): one table, five wrappers per unit -----------------
+# unit -> (its pass parameter between max_dist and rb / the flags: () or ((name, default),); squared residuals per point)
+MATCH_UNITS = {
+    "gicp": ((), 1),
+    "vgicp": ((), 1),
+    "symm": ((("min_cos", 0.0),), 1),
+    "color": ((("lambda_geometric", 0.968),), 2),
+}
 
 
-def _robust_pair(name, extra):
-    """(linearize, align) over pcr_<name>_linearize_robust / _align_robust; ``extra``: the doubles between max_dist and rb."""
-    def linearize(target, scan, T, max_dist, *args, robust=None, flags=0):
-        p, keep = _rb(robust)
-        ex = _extras(args, extra)
-        entry = lambda t, s, T, md, fl, out: getattr(lib(), f"pcr_{name}_linearize_robust")(t, s, T, md, *ex, p, fl, out)
-        return _linearize29(entry, target, scan, T, max_dist, flags)
-
-    def align(target, scan, T_init, max_iter, tol, max_dist, *args, robust=None, flags=0, want_trace=False):
-        p, keep = _rb(robust)
-        ex = _extras(args, extra)
-        entry = lambda t, s, T0, it, tol, md, *rest: getattr(lib(), f"pcr_{name}_align_robust")(t, s, T0, it, tol, md, *ex, p, *rest)
-        return _align(entry, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace)
-    return linearize, align
+def _trailing(*params):
+    """(name, default) pairs -> bind(args, kw): the values of these trailing parameters of a wrapper, given by position or
+    by keyword, in order, else TypeError.  (By hand, 0.5 us a call: these wrappers sit inside passes of well under a millisecond.)"""
+    def bind(args, kw):
+        if len(args) > len(params):
+            raise TypeError(f"at most {len(params)} trailing argument(s) ({', '.join(n for n, _ in params)}), got {len(args)}")
+        vals = list(args) + [kw.pop(n, d) for n, d in params[len(args):]]
+        if kw:
+            raise TypeError(f"unexpected keyword argument(s): {', '.join(sorted(kw))}")
+        return vals
+    return bind
 
 
-# (target, scan, T, max_dist[, min_cos | lambda_geometric], robust=(kind, scale) or None, flags=0) -> the 29 sums;
-# (target, scan, T_init, max_iter, tol, max_dist[, ...], robust=, flags=0, want_trace=False) -> as the plain *_align
-gicp_linearize_robust, gicp_align_robust = _robust_pair("gicp", 0)
-vgicp_linearize_robust, vgicp_align_robust = _robust_pair("vgicp", 0)
-symm_linearize_robust, symm_align_robust = _robust_pair("symm", 1)
-color_linearize_robust, color_align_robust = _robust_pair("color", 1)
+def _match_unit(unit):
+    """The five wrappers of ``unit``, with P its pass parameter (``min_cos=0.0`` / ``lambda_geometric=0.968``; none for gicp, vgicp):
+      linearize(target, scan, T, max_dist[, P], flags=0) -> the 29 sums of one pass (pcr_<unit>_linearize)
+      align(target, scan, T_init, max_iter, tol, max_dist[, P], flags=0, want_trace=False) -> (T, iterations[, trace rows]):
+          the host-driven Gauss-Newton loop over the pass, behind the boundary (pcr_<unit>_align)
+      linearize_robust(target, scan, T, max_dist[, P], robust=None, flags=0), align_robust(..., max_dist[, P], robust=None, flags=0,
+          want_trace=False): the same through pcr_<unit>_*_robust; ``robust``: (kind, scale), or None -> NULL.  P has no default
+      residuals(target, scan, T, max_dist[, P], flags=0) -> the squared residuals in the caller's order, (N,) float64 -- color:
+          (N, 2), both rows -- inf where a point has no correspondence (pcr_<unit>_residuals)"""
+    extra, m = MATCH_UNITS[unit]
+    pass_tail, align_tail = _trailing(*extra, ("flags", 0)), _trailing(*extra, ("flags", 0), ("want_trace", False))
+
+    def entry(what):
+        return getattr(lib(), f"pcr_{unit}_{what}")
+
+    def floats(args):
+        if len(args) != len(extra):
+            raise TypeError(f"expected {len(extra)} pass parameter(s) after max_dist, got {len(args)}")
+        return tuple(float(v) for v in args)
+
+    def call(what, target, scan, T, max_dist, mid, flags, out):
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        check(entry(what)(target.handle, scan.handle, T, float(max_dist), *mid, int(flags), out))
+
+    def sums(what, *args):
+        out = np.empty(29)
+        call(what, *args, out)
+        return out
+
+    def loop(what, target, scan, head, mid, flags, want_trace):
+        return _align(entry(what), (target.handle, scan.handle), *head, flags, want_trace, mid=mid)
+
+    def linearize(target, scan, T, max_dist, *args, **kw):
+        *p, flags = pass_tail(args, kw)
+        return sums("linearize", target, scan, T, max_dist, floats(p), flags)
+
+    def align(target, scan, T_init, max_iter, tol, max_dist, *args, **kw):
+        *p, flags, want_trace = align_tail(args, kw)
+        return loop("align", target, scan, (T_init, max_iter, tol, max_dist), floats(p), flags, want_trace)
+
+    def linearize_robust(target, scan, T, max_dist, *args, robust=None, flags=0):
+        rb, keep = _rb(robust)
+        return sums("linearize_robust", target, scan, T, max_dist, floats(args) + (rb,), flags)
+
+    def align_robust(target, scan, T_init, max_iter, tol, max_dist, *args, robust=None, flags=0, want_trace=False):
+        rb, keep = _rb(robust)
+        return loop("align_robust", target, scan, (T_init, max_iter, tol, max_dist), floats(args) + (rb,), flags, want_trace)
+
+    def residuals(target, scan, T, max_dist, *args, **kw):
+        *p, flags = pass_tail(args, kw)
+        out = np.empty((scan.n, m) if m > 1 else (scan.n,))
+        call("residuals", target, scan, T, max_dist, floats(p), flags, _ptr(out))
+        return out
+
+    return {f"{unit}_{f.__name__}": f for f in (linearize, align, linearize_robust, align_robust, residuals)}
 
 
-def _residuals(name, m, target, scan, T, max_dist, extra, flags):
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-    out = np.empty((scan.n, m) if m > 1 else (scan.n,))
-    check(getattr(lib(), f"pcr_{name}_residuals")(target.handle, scan.handle, T, float(max_dist), *map(float, extra), int(flags), _ptr(out)))
-    return out
-
-
-def gicp_residuals(target, scan, T, max_dist, flags=0):
-    """pcr_gicp_residuals -> d^T M d (N,) float64 in the caller's order, inf where a point has no correspondence."""
-    return _residuals("gicp", 1, target, scan, T, max_dist, (), flags)
-
-
-def vgicp_residuals(target, scan, T, max_dist, flags=0):
-    """pcr_vgicp_residuals -> d^T M d (N,) float64 in the caller's order, inf where a point has no correspondence."""
-    return _residuals("vgicp", 1, target, scan, T, max_dist, (), flags)
-
-
-def symm_residuals(target, scan, T, max_dist, min_cos=0.0, flags=0):
-    """pcr_symm_residuals -> r r (N,) float64 in the caller's order, inf where a point has no correspondence."""
-    return _residuals("symm", 1, target, scan, T, max_dist, (min_cos,), flags)
-
-
-def color_residuals(target, scan, T, max_dist, lambda_geometric=0.968, flags=0):
-    """pcr_color_residuals -> the squared residuals of both rows (N, 2) float64 in the caller's order, inf where a point has no
-    correspondence."""
-    return _residuals("color", 2, target, scan, T, max_dist, (lambda_geometric,), flags)
+for _unit in MATCH_UNITS:
+    globals().update(_match_unit(_unit))
 
 
 _linearize_fast = None

@@ -32,9 +32,7 @@ def as_intensity(values, n, name):
 
 
 class ColoredICP(MatchPass):
-    _capi_linearize, _capi_align = staticmethod(_capi.color_linearize), staticmethod(_capi.color_align)
-    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.color_linearize_robust), staticmethod(_capi.color_align_robust)
-    _capi_residuals = staticmethod(_capi.color_residuals)
+    _UNIT = "color"
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, lambda_geometric=0.968, **kw):
         super().__init__(max_iter, max_dist, tol, k, **kw)
@@ -104,20 +102,13 @@ class ColoredICP(MatchPass):
 
     # -- scan ------------------------------------------------------------------------------------
     def _color_scan(self, source, source_intensity, fresh=False):
-        """The device copy of ``source`` with its intensities on it.  They belong to the ``_capi.Scan``: uploaded once per
-        uploaded scan and intensity array (by digest), gone with it."""
+        """The device copy of ``source`` with its intensities on it (``MatchPass._payload_scan``; nothing to estimate)."""
         if not self._is_target_set:
             raise ValueError("Target is not set.")
         if source_intensity is None:
             raise ValueError("ColoredICP needs the scan's intensities")
-        # the caller's order is kept (4 bytes per point): the intensities cross the boundary in it
-        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
-        inten = as_intensity(source_intensity, scan.n, "source_intensity")
-        tag = self._digest(inten)
-        if getattr(scan, "_color_int", None) != tag:
-            scan.set_intensity(inten)
-            scan._color_int = tag
-        return scan
+        return self._payload_scan(source, fresh, "_color_int", lambda n: as_intensity(source_intensity, n, "source_intensity"),
+                                  _capi.Scan.set_intensity)
 
     def _pass_scan(self, source, source_intensity=None):
         return self._color_scan(source, source_intensity)

@@ -18,6 +18,8 @@
 //   k_color_robust         the same pass with each of the two rows weighed by a robust kernel of its own r r
 //                          (RobustSide<ColorArgs>, COLOR_ROBUST_W points per lane in flight), folded by k_color_fold
 //   k_color_residuals      both rows' r r of every scan point in the caller's order (match_residuals)
+//   ColorUnit              what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                          match_align, match_residuals_entry)
 //
 // Scan side: pcr_scan::inten, one float per point in device order.  Target side: the PtN records PlaneICP gathers and the
 // 16-byte colour records, 48 bytes per match from two arrays.
@@ -277,94 +279,52 @@ __global__ void __launch_bounds__(256) k_color_residuals(const LinArgs a, const 
     match_residuals(a, ca, order, out);
 }
 
-static pcr_status check_color_payloads(const pcr_target *t, const pcr_scan *s) {
-    if (t->is_voxel) { pcr_set_error("ColoredICP needs a point target"); return PCR_ERR_NO_TARGET; }
-    if (!t->pn) { pcr_set_error("ColoredICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
-    if (!t->col) { pcr_set_error("ColoredICP target has no colour records (pcr_target_set_intensity; replacing the normals frees them)"); return PCR_ERR_NO_TARGET; }
-    if (!s->inten) { pcr_set_error("ColoredICP scan has no intensities (pcr_scan_set_intensity)"); return PCR_ERR_NO_TARGET; }
-    return PCR_OK;
-}
-
-// search + the coloured pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
-// too); params: two doubles, lambda_pair's sqrt(lambda) and sqrt(1 - lambda) of the call
-static pcr_status pcr_run_color(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
-    PCR_TRY(check_color_payloads(t, s));
-    const double *w = (const double *)params;
-    const ColorArgs ca{s->inten, t->col, w[0], w[1], nullptr};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_reduce", k_color_reduce, k_color_fold, ca, out);
-}
-
-// the same under a robust weight; params: the two factors and the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
-struct ColorRobustParams {
-    double w[2];
-    RobustK rb;
+// ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
+// The search is ICP's (its LinArgs carries the PtN records too); the parameter of a call is lambda_geometric, taken through
+// the pass as sqrt(lambda) and sqrt(1 - lambda): once, in double
+struct ColorUnit : MatchUnit {
+    typedef ColorArgs Side;
+    struct Params { double ag, ac; };
+    static pcr_status check(Params *p, double lambda) {
+        PCR_REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda_geometric must be in [0, 1]");      // (false for NaN)
+        p->ag = sqrt(lambda);
+        p->ac = sqrt(1.0 - lambda);
+        return PCR_OK;
+    }
+    static constexpr int kind = PCR_ICP;
+    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
+        if (t->is_voxel) { pcr_set_error("ColoredICP needs a point target"); return PCR_ERR_NO_TARGET; }
+        if (!t->pn) { pcr_set_error("ColoredICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
+        if (!t->col) { pcr_set_error("ColoredICP target has no colour records (pcr_target_set_intensity; replacing the normals frees them)"); return PCR_ERR_NO_TARGET; }
+        if (!s->inten) { pcr_set_error("ColoredICP scan has no intensities (pcr_scan_set_intensity)"); return PCR_ERR_NO_TARGET; }
+        return PCR_OK;
+    }
+    static Side side(const pcr_target *t, const pcr_scan *s, const Params &p) { return {s->inten, t->col, p.ag, p.ac, nullptr}; }
+    static constexpr auto reduce = k_color_reduce;
+    static constexpr auto robust = k_color_robust;
+    static constexpr auto fold = k_color_fold;
+    static constexpr auto residuals = k_color_residuals;
+    static constexpr const char *reduce_range = "pcr:color_reduce", *robust_range = "pcr:color_robust", *residuals_range = "pcr:color_residuals";
 };
-static pcr_status pcr_run_color_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
-                                       double out[29]) {
-    const ColorRobustParams *p = (const ColorRobustParams *)params;
-    if (p->rb.kind == PCR_ROBUST_NONE) return pcr_run_color(t, s, kind, T, max_dist, flags, p->w, out);
-    PCR_TRY(check_color_payloads(t, s));
-    const RobustSide<ColorArgs> ca{{s->inten, t->col, p->w[0], p->w[1], nullptr}, p->rb};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_robust", k_color_robust, k_color_fold, ca, out);
-}
-
-// sqrt(lambda) and sqrt(1 - lambda), once, in double
-static pcr_status lambda_pair(double lambda, double w[2]) {
-    PCR_REQUIRE(lambda >= 0.0 && lambda <= 1.0, "lambda_geometric must be in [0, 1]");      // (false for NaN)
-    w[0] = sqrt(lambda);
-    w[1] = sqrt(1.0 - lambda);
-    return PCR_OK;
-}
 
 extern "C" pcr_status pcr_color_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                           unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    double w[2];
-    PCR_TRY(lambda_pair(lambda_geometric, w));
-    CtxScope scope(t->ctx);
-    return pcr_run_color(t, s, PCR_ICP, T, max_dist, flags, w, out);
+    return match_linearize<ColorUnit>(t, s, T, max_dist, nullptr, flags, out, lambda_geometric);
 }
-
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_color_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                       double lambda_geometric, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    double w[2];
-    PCR_TRY(lambda_pair(lambda_geometric, w));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_color, t, s, PCR_ICP, w, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<ColorUnit>(t, s, T_init, max_iter, tol, max_dist, nullptr, flags, T_out, iterations, trace_or_null, lambda_geometric);
 }
-
-// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
 extern "C" pcr_status pcr_color_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                                  const pcr_robust *rb, unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    ColorRobustParams p;
-    PCR_TRY(lambda_pair(lambda_geometric, p.w));
-    PCR_TRY(robust_args(rb, &p.rb));
-    CtxScope scope(t->ctx);
-    return pcr_run_color_robust(t, s, PCR_ICP, T, max_dist, flags, &p, out);
+    return match_linearize<ColorUnit>(t, s, T, max_dist, rb, flags, out, lambda_geometric);
 }
-
 extern "C" pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                              double lambda_geometric, const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
                                              double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    ColorRobustParams p;
-    PCR_TRY(lambda_pair(lambda_geometric, p.w));
-    PCR_TRY(robust_args(rb, &p.rb));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_color_robust, t, s, PCR_ICP, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<ColorUnit>(t, s, T_init, max_iter, tol, max_dist, rb, flags, T_out, iterations, trace_or_null, lambda_geometric);
 }
-
 extern "C" pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                           unsigned flags, double *s_out) {
-    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
-    double w[2];
-    PCR_TRY(lambda_pair(lambda_geometric, w));
-    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
-    PCR_TRY(check_color_payloads(t, s));
-    const ColorArgs ca{s->inten, t->col, w[0], w[1], nullptr};
-    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:color_residuals", k_color_residuals, ca, s_out);
+    return match_residuals_entry<ColorUnit>(t, s, T, max_dist, flags, s_out, lambda_geometric);
 }

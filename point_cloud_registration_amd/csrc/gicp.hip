@@ -16,6 +16,8 @@
 //   k_gicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<GicpArgs>, GICP_ROBUST_W
 //                     points per lane in flight), folded by k_gicp_fold
 //   k_gicp_residuals  d^T M d of every scan point in the caller's order (match_residuals)
+//   GicpUnit          what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                     match_align, match_residuals_entry)
 //
 // Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
 // correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line); its
@@ -247,67 +249,39 @@ __global__ void __launch_bounds__(256) k_gicp_residuals(const LinArgs a, const G
     match_residuals(a, ga, order, out);
 }
 
-static pcr_status check_gicp_payloads(const pcr_target *t, const pcr_scan *s) {
-    if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-    if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-    return PCR_OK;
-}
-
-// search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is ICP's
-static pcr_status pcr_run_gicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
-    PCR_TRY(check_gicp_payloads(t, s));
-    const GicpArgs ga{{s->cov}, (const GicpRec *)t->gcov, nullptr};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_reduce", k_gicp_reduce, k_gicp_fold, ga, out);
-}
+// ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
+// The search is ICP's; a call has no parameter of the unit's own
+struct GicpUnit : MatchUnit {
+    typedef GicpArgs Side;
+    static constexpr int kind = PCR_ICP;
+    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
+        if (t->is_voxel || !t->gcov) { pcr_set_error("GICP target has no covariances (pcr_target_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+        if (!s->cov) { pcr_set_error("GICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
+        return PCR_OK;
+    }
+    static Side side(const pcr_target *t, const pcr_scan *s, const Params &) { return {{s->cov}, (const GicpRec *)t->gcov, nullptr}; }
+    static constexpr auto reduce = k_gicp_reduce;
+    static constexpr auto robust = k_gicp_robust;
+    static constexpr auto fold = k_gicp_fold;
+    static constexpr auto residuals = k_gicp_residuals;
+    static constexpr const char *reduce_range = "pcr:gicp_reduce", *robust_range = "pcr:gicp_robust", *residuals_range = "pcr:gicp_residuals";
+};
 
 extern "C" pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    CtxScope scope(t->ctx);
-    return pcr_run_gicp(t, s, PCR_ICP, T, max_dist, flags, nullptr, out);
+    return match_linearize<GicpUnit>(t, s, T, max_dist, nullptr, flags, out);
 }
-
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_gicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                      unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_gicp, t, s, PCR_ICP, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<GicpUnit>(t, s, T_init, max_iter, tol, max_dist, nullptr, flags, T_out, iterations, trace_or_null);
 }
-
-// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
-// params of the robust pcr_pass_fn: the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
-static pcr_status pcr_run_gicp_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
-                                      double out[29]) {
-    const RobustK *rb = (const RobustK *)params;
-    if (rb->kind == PCR_ROBUST_NONE) return pcr_run_gicp(t, s, kind, T, max_dist, flags, nullptr, out);
-    PCR_TRY(check_gicp_payloads(t, s));
-    const RobustSide<GicpArgs> ga{{{s->cov}, (const GicpRec *)t->gcov, nullptr}, *rb};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_robust", k_gicp_robust, k_gicp_fold, ga, out);
-}
-
 extern "C" pcr_status pcr_gicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
                                                 unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    RobustK k;
-    PCR_TRY(robust_args(rb, &k));
-    CtxScope scope(t->ctx);
-    return pcr_run_gicp_robust(t, s, PCR_ICP, T, max_dist, flags, &k, out);
+    return match_linearize<GicpUnit>(t, s, T, max_dist, rb, flags, out);
 }
-
 extern "C" pcr_status pcr_gicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                             const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    RobustK k;
-    PCR_TRY(robust_args(rb, &k));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_gicp_robust, t, s, PCR_ICP, &k, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<GicpUnit>(t, s, T_init, max_iter, tol, max_dist, rb, flags, T_out, iterations, trace_or_null);
 }
-
 extern "C" pcr_status pcr_gicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
-    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
-    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
-    PCR_TRY(check_gicp_payloads(t, s));
-    const GicpArgs ga{{s->cov}, (const GicpRec *)t->gcov, nullptr};
-    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:gicp_residuals", k_gicp_residuals, ga, s_out);
+    return match_residuals_entry<GicpUnit>(t, s, T, max_dist, flags, s_out);
 }

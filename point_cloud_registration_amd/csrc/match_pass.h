@@ -1,6 +1,18 @@
-// A pass over a match list, stated once: the three-phase reduce loop, the fold, the host driver of the two launches and the
-// scaffold of a pcr_pass_fn around them.  Behind GICP, VGICP, SymmetricICP and ColoredICP (gicp.hip, vgicp.hip, symm.hip,
-// color.hip); each keeps its own __global__ one-liners (k_gicp_* / k_vgicp_* / k_symm_* / k_color_*) and its *_W.
+// A pass over a match list, stated once: the three-phase reduce loop, the fold, the host driver of the two launches, the
+// pcr_pass_fn around them and the entry points in front of it.  Behind GICP, VGICP, SymmetricICP and ColoredICP (gicp.hip,
+// vgicp.hip, symm.hip, color.hip).  A unit is a SIDE and a UNIT; it keeps its own __global__ one-liners (k_gicp_* / k_vgicp_* /
+// k_symm_* / k_color_*), its *_W and its twenty-odd lines of extern "C" names, each ONE call of a template here.
+//
+// A UNIT (GicpUnit, VgicpUnit, SymmUnit, ColorUnit) names what the five entry points of a unit differ in -- and nothing else:
+//   Side                      its SIDE
+//   Params, check(&p, raw...) the checked per-call parameter block, for plain and robust calls alike, and the check that fills
+//                             it from the caller's own parameter (MatchUnit: none; symm.hip: min_cos; color.hip: the two roots)
+//   kind                      the search: PCR_ICP, or PCR_VPLANE
+//   payloads(t, s)            PCR_ERR_NO_TARGET and its message where target or scan lack what the pass reads
+//   side(t, s, p)             the SIDE of a call, everything but rows
+//   reduce, robust, fold, residuals                 the four __global__ one-liners
+//   reduce_range, robust_range, residuals_range     their roctx range names
+//   no_match(t, s, max_dist, &none)                 MatchUnit: never; vgicp.hip: a target with no kept voxel
 //
 // A SIDE is a unit's kernel-argument struct (GicpArgs, VgicpArgs, SymmArgs, ColorArgs): its arrays, its parameters, rows -- and
 //   Scan                      what phase A carries per scan point beside index and coordinates
@@ -201,21 +213,15 @@ static pcr_status match_launch(pcr_context *ctx, const char *range_name, void (*
     return PCR_OK;
 }
 
-// What a pcr_pass_fn does once the unit has checked its payloads: kind's full search (pass.hip: pcr_rows_search) into a match
-// buffer of the call, 29 zeros, and -- for a scan with points -- match_launch
-template <typename SIDE>
-static pcr_status match_pass(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const char *range_name,
-                             void (*reduce)(const LinArgs, const SIDE), void (*fold)(const double *, int, double *), const SIDE &sd,
-                             double out[29]) {
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, kind, T, max_dist, flags, false));
-    for (int i = 0; i < 29; ++i) out[i] = 0.0;
-    if (s->n == 0) return PCR_OK;
-    return match_launch(t->ctx, range_name, reduce, fold, a, sd, s->n, out);
-}
+// ---- the entry points, stated once: a UNIT and the templates over it ------------------------------------------------------
+// What a UNIT leaves unsaid (it derives from this): no parameter of its own between max_dist and the flags, and no target
+// without a match
+struct MatchUnit {
+    struct Params {};
+    static pcr_status check(Params *) { return PCR_OK; }
+    static pcr_status no_match(const pcr_target *, const pcr_scan *, double, bool *none) { *none = false; return PCR_OK; }
+};
 
-// ---- robust passes and residuals: the host side the four units share --------------------------------------------------------
 // the caller's pcr_robust -> RobustK.  NULL or PCR_ROBUST_NONE: the plain pass (kind 0; the scale is not read)
 static inline pcr_status robust_args(const pcr_robust *rb, RobustK *k) {
     k->kind = PCR_ROBUST_NONE; k->c = 1.0; k->c2 = 1.0;
@@ -227,25 +233,105 @@ static inline pcr_status robust_args(const pcr_robust *rb, RobustK *k) {
     return PCR_OK;
 }
 
-// What a *_residuals entry point does once the unit has checked its payloads: kind's full search, as match_pass, and the
-// residual kernel into SIDE::M doubles per scan point in the caller's order
-template <typename SIDE>
-static pcr_status match_residuals_run(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
-                                      const char *range_name, void (*resid)(const LinArgs, const SIDE, const uint32_t *, double *),
-                                      const SIDE &sd, double *s_out) {
+// U's full search (pass.hip: pcr_rows_search) into a match buffer of the call, 29 zeros, and -- for a scan with points --
+// match_launch of `reduce` over sd
+template <typename U, typename SIDE>
+static pcr_status match_pass(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, const char *range_name,
+                             void (*reduce)(const LinArgs, const SIDE), const SIDE &sd, double out[29]) {
     LinArgs a;
     DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, kind, T, max_dist, flags, true));
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    if (s->n == 0) return PCR_OK;
+    return match_launch(t->ctx, range_name, reduce, U::fold, a, sd, s->n, out);
+}
+
+// The pcr_pass_fn of a unit (`kind` is not read: the search is U::kind's).  params: what U::check made of the caller's own
+// parameter, and the checked kernel of the call -- PCR_ROBUST_NONE: the plain kernel, the plain bits
+template <typename U>
+struct MatchParams {
+    typename U::Params unit;
+    RobustK rb;
+};
+template <typename U>
+static pcr_status match_run(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
+    const MatchParams<U> *p = (const MatchParams<U> *)params;
+    PCR_TRY(U::payloads(t, s));
+    bool none;
+    PCR_TRY(U::no_match(t, s, max_dist, &none));
+    if (none) {
+        for (int i = 0; i < 29; ++i) out[i] = 0.0;
+        return PCR_OK;
+    }
+    const typename U::Side sd = U::side(t, s, p->unit);
+    if (p->rb.kind == PCR_ROBUST_NONE) return match_pass<U>(t, s, T, max_dist, flags, U::reduce_range, U::reduce, sd, out);
+    return match_pass<U>(t, s, T, max_dist, flags, U::robust_range, U::robust, RobustSide<typename U::Side>{sd, p->rb}, out);
+}
+
+// The three entry points of a unit behind its five extern "C" names: rb is NULL from the plain ones, raw is the caller's own
+// parameter of the unit (none, min_cos, lambda_geometric).  The order of refusals, the same for every unit: NULL arguments,
+// the unit's parameter, the kernel, (residuals) a scan that knows the caller's order, the payloads, what the search refuses.
+// A refused call writes nothing
+template <typename U, typename... Raw>
+static pcr_status match_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb, unsigned flags,
+                                  double out[29], Raw... raw) {
+    PCR_REQUIRE(t && s && T && out, "NULL argument");
+    MatchParams<U> p;
+    PCR_TRY(U::check(&p.unit, raw...));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return match_run<U>(t, s, U::kind, T, max_dist, flags, &p, out);
+}
+
+// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
+template <typename U, typename... Raw>
+static pcr_status match_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist, const pcr_robust *rb,
+                              unsigned flags, double T_out[16], int *iterations, double *trace_or_null, Raw... raw) {
+    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
+    MatchParams<U> p;
+    PCR_TRY(U::check(&p.unit, raw...));
+    PCR_TRY(robust_args(rb, &p.rb));
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(match_run<U>, t, s, U::kind, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}
+
+// U's full search, as match_pass, and the residual kernel into Side::M doubles per scan point in the caller's order
+template <typename U>
+static pcr_status match_residuals_run(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, const typename U::Side &sd,
+                                      double *s_out) {
+    const size_t m = U::Side::M;
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, true));
     if (s->n == 0) return PCR_OK;
     pcr_context *ctx = t->ctx;
     DevBuf<double> d;
-    HIP_TRY(d.alloc(SIDE::M * (size_t)s->n));
+    HIP_TRY(d.alloc(m * (size_t)s->n));
     {
-        RoctxRange range(range_name);
-        hipLaunchKernelGGL(resid, dim3((unsigned)choose_blocks(ctx, s->n)), dim3(256), 0, ctx->stream, a, sd, (const uint32_t *)s->order, d.p);
+        RoctxRange range(U::residuals_range);
+        hipLaunchKernelGGL(U::residuals, dim3((unsigned)choose_blocks(ctx, s->n)), dim3(256), 0, ctx->stream, a, sd, (const uint32_t *)s->order, d.p);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s_out, d.p, SIDE::M * (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s_out, d.p, m * (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PCR_OK;
 }
+
+// +inf for every point of a target without a match, whatever else: the squared residuals of match_residuals_run
+template <typename U, typename... Raw>
+static pcr_status match_residuals_entry(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out, Raw... raw) {
+    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
+    typename U::Params p;
+    PCR_TRY(U::check(&p, raw...));
+    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
+    CtxScope scope(t->ctx);
+    PCR_TRY(U::payloads(t, s));
+    bool none;
+    PCR_TRY(U::no_match(t, s, max_dist, &none));
+    if (none) {
+        for (int64_t i = 0; i < U::Side::M * s->n; ++i) s_out[i] = (double)INFINITY;
+        return PCR_OK;
+    }
+    return match_residuals_run<U>(t, s, T, max_dist, flags, U::side(t, s, p), s_out);
+}
+

@@ -452,8 +452,8 @@ struct LinArgs;
 pcr_status pcr_rows_search(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
                            unsigned flags, bool caller_order);
 // ---- api.hip: the host-driven Gauss-Newton loop (align_host_loop of pcr_align) over a pass of the caller's choice.  `params`:
-// what the pass takes beside the common arguments (symm.hip: min_cos; color.hip: the two weights; else NULL), handed through
-// to every iteration: a parameter of the call travels with the call
+// what the pass takes beside the common arguments (match_pass.h: a MatchParams<UNIT>, the unit's own block and the robust
+// kernel; pcr_align: NULL), handed through to every iteration: a parameter of the call travels with the call
 typedef pcr_status (*pcr_pass_fn)(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags,
                                   const void *params, double out[29]);
 pcr_status pcr_align_host_loop(pcr_pass_fn pass, pcr_target *t, pcr_scan *s, int kind, const void *params, const double T_init[16],

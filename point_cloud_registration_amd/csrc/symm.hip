@@ -14,6 +14,8 @@
 //   k_symm_robust        the same pass with every correspondence weighed by a robust kernel of r r (RobustSide<SymmArgs>,
 //                        SYMM_ROBUST_W points per lane in flight), folded by k_symm_fold
 //   k_symm_residuals     r r of every scan point in the caller's order (match_residuals)
+//   SymmUnit             what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                        match_align, match_residuals_entry)
 //
 // Scan side: pcr_scan::nrm, three floats per point in device order (12 bytes beside the 16 of index and coordinates).  Target
 // side: the PtN records PlaneICP gathers -- point and normal in one 32-byte sector.
@@ -151,86 +153,50 @@ __global__ void __launch_bounds__(256) k_symm_residuals(const LinArgs a, const S
     match_residuals(a, sa, order, out);
 }
 
-static pcr_status check_min_cos(double min_cos) {
-    PCR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must be in [0, 1]");      // (false for NaN)
-    return PCR_OK;
-}
-
-static pcr_status check_symm_payloads(const pcr_target *t, const pcr_scan *s) {
-    if (t->is_voxel) { pcr_set_error("SymmetricICP needs a point target"); return PCR_ERR_NO_TARGET; }
-    if (!t->pn) { pcr_set_error("SymmetricICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
-    if (!s->nrm) { pcr_set_error("SymmetricICP scan has no normals (pcr_scan_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
-    return PCR_OK;
-}
-
-// search + the symmetric pass.  A pcr_pass_fn: `kind` is not read, the search is ICP's (its LinArgs carries the PtN records
-// too: pass.hip, pass_fill_lin); params: one double, the normal gate min_cos of the call
-static pcr_status pcr_run_symm(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
-    PCR_TRY(check_symm_payloads(t, s));
-    const SymmArgs sa{s->nrm, *(const double *)params, nullptr};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_reduce", k_symm_reduce, k_symm_fold, sa, out);
-}
-
-// the same under a robust weight; params: min_cos and the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
-struct SymmRobustParams {
-    double min_cos;
-    RobustK rb;
+// ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
+// The search is ICP's (its LinArgs carries the PtN records too: pass.hip, pass_fill_lin); the parameter of a call is the normal
+// gate min_cos
+struct SymmUnit : MatchUnit {
+    typedef SymmArgs Side;
+    typedef double Params;
+    static pcr_status check(Params *p, double min_cos) {
+        PCR_REQUIRE(min_cos >= 0.0 && min_cos <= 1.0, "min_cos must be in [0, 1]");      // (false for NaN)
+        *p = min_cos;
+        return PCR_OK;
+    }
+    static constexpr int kind = PCR_ICP;
+    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
+        if (t->is_voxel) { pcr_set_error("SymmetricICP needs a point target"); return PCR_ERR_NO_TARGET; }
+        if (!t->pn) { pcr_set_error("SymmetricICP target has no normals (pcr_target_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
+        if (!s->nrm) { pcr_set_error("SymmetricICP scan has no normals (pcr_scan_estimate_normals / _set_normals)"); return PCR_ERR_NO_TARGET; }
+        return PCR_OK;
+    }
+    static Side side(const pcr_target *, const pcr_scan *s, const Params &min_cos) { return {s->nrm, min_cos, nullptr}; }
+    static constexpr auto reduce = k_symm_reduce;
+    static constexpr auto robust = k_symm_robust;
+    static constexpr auto fold = k_symm_fold;
+    static constexpr auto residuals = k_symm_residuals;
+    static constexpr const char *reduce_range = "pcr:symm_reduce", *robust_range = "pcr:symm_robust", *residuals_range = "pcr:symm_residuals";
 };
-static pcr_status pcr_run_symm_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
-                                      double out[29]) {
-    const SymmRobustParams *p = (const SymmRobustParams *)params;
-    if (p->rb.kind == PCR_ROBUST_NONE) return pcr_run_symm(t, s, kind, T, max_dist, flags, &p->min_cos, out);
-    PCR_TRY(check_symm_payloads(t, s));
-    const RobustSide<SymmArgs> sa{{s->nrm, p->min_cos, nullptr}, p->rb};
-    return match_pass(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_robust", k_symm_robust, k_symm_fold, sa, out);
-}
 
 extern "C" pcr_status pcr_symm_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
                                          double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    PCR_TRY(check_min_cos(min_cos));
-    CtxScope scope(t->ctx);
-    return pcr_run_symm(t, s, PCR_ICP, T, max_dist, flags, &min_cos, out);
+    return match_linearize<SymmUnit>(t, s, T, max_dist, nullptr, flags, out, min_cos);
 }
-
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_symm_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                      double min_cos, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    PCR_TRY(check_min_cos(min_cos));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_symm, t, s, PCR_ICP, &min_cos, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<SymmUnit>(t, s, T_init, max_iter, tol, max_dist, nullptr, flags, T_out, iterations, trace_or_null, min_cos);
 }
-
-// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
 extern "C" pcr_status pcr_symm_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos,
                                                 const pcr_robust *rb, unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    SymmRobustParams p{min_cos, {}};
-    PCR_TRY(check_min_cos(min_cos));
-    PCR_TRY(robust_args(rb, &p.rb));
-    CtxScope scope(t->ctx);
-    return pcr_run_symm_robust(t, s, PCR_ICP, T, max_dist, flags, &p, out);
+    return match_linearize<SymmUnit>(t, s, T, max_dist, rb, flags, out, min_cos);
 }
-
 extern "C" pcr_status pcr_symm_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                             double min_cos, const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations,
                                             double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    SymmRobustParams p{min_cos, {}};
-    PCR_TRY(check_min_cos(min_cos));
-    PCR_TRY(robust_args(rb, &p.rb));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_symm_robust, t, s, PCR_ICP, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<SymmUnit>(t, s, T_init, max_iter, tol, max_dist, rb, flags, T_out, iterations, trace_or_null, min_cos);
 }
-
 extern "C" pcr_status pcr_symm_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
                                          double *s_out) {
-    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
-    PCR_TRY(check_min_cos(min_cos));
-    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
-    PCR_TRY(check_symm_payloads(t, s));
-    const SymmArgs sa{s->nrm, min_cos, nullptr};
-    return match_residuals_run(t, s, PCR_ICP, T, max_dist, flags, "pcr:symm_residuals", k_symm_residuals, sa, s_out);
+    return match_residuals_entry<SymmUnit>(t, s, T, max_dist, flags, s_out, min_cos);
 }

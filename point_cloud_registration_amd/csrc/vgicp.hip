@@ -15,6 +15,8 @@
 //   k_vgicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<VgicpArgs>,
 //   k_vgicp_residuals  VGICP_ROBUST_W points per lane in flight), folded by k_vgicp_fold; d^T M d of every scan point in the
 //                      caller's order (match_residuals)
+//   VgicpUnit          what the five entry points differ in -- the target with no kept voxel among it; the rest of them is
+//                      match_pass.h's (match_run, match_linearize, match_align, match_residuals_entry)
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -143,82 +145,49 @@ __global__ void __launch_bounds__(256) k_vgicp_residuals(const LinArgs a, const 
     match_residuals(a, va, order, out);
 }
 
-static pcr_status check_vgicp_payloads(const pcr_target *t, const pcr_scan *s) {
-    if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
-    if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
-    if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-    return PCR_OK;
-}
-
-// centroid search + the distribution pass.  A pcr_pass_fn: `kind` and `params` are not read, the search is VPlaneICP's
-static pcr_status pcr_run_vgicp(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *, double out[29]) {
-    PCR_TRY(check_vgicp_payloads(t, s));
-    pcr_context *ctx = t->ctx;
-    for (int i = 0; i < 29; ++i) out[i] = 0.0;
-    if (t->n == 0) {                                 // no kept voxel: no match (and no voxel 0 for the select of phase B)
-        PCR_REQUIRE(s->ctx == ctx, "scan and target belong to different contexts");
-        PCR_REQUIRE(max_dist > 0, "max_dist must be positive");
-        if (ctx->comm != nullptr) { pcr_set_error("VGICP passes are not available on a context with a communicator attached"); return PCR_ERR_UNSUPPORTED; }
+// ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
+// The search is VPlaneICP's, over the centroids; a call has no parameter of the unit's own
+struct VgicpUnit : MatchUnit {
+    typedef VgicpArgs Side;
+    static constexpr int kind = PCR_VPLANE;
+    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
+        if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
+        if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
+        if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
         return PCR_OK;
     }
-    const VgicpArgs va{{s->cov}, t->vcov, nullptr};
-    return match_pass(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_reduce", k_vgicp_reduce, k_vgicp_fold, va, out);
-}
+    // no kept voxel: no match (and no voxel 0 for the select of phase B) -- once what the search refuses has been refused here
+    static pcr_status no_match(const pcr_target *t, const pcr_scan *s, double max_dist, bool *none) {
+        *none = t->n == 0;
+        if (!*none) return PCR_OK;
+        PCR_REQUIRE(s->ctx == t->ctx, "scan and target belong to different contexts");
+        PCR_REQUIRE(max_dist > 0, "max_dist must be positive");
+        if (t->ctx->comm != nullptr) { pcr_set_error("VGICP passes are not available on a context with a communicator attached"); return PCR_ERR_UNSUPPORTED; }
+        return PCR_OK;
+    }
+    static Side side(const pcr_target *t, const pcr_scan *s, const Params &) { return {{s->cov}, t->vcov, nullptr}; }
+    static constexpr auto reduce = k_vgicp_reduce;
+    static constexpr auto robust = k_vgicp_robust;
+    static constexpr auto fold = k_vgicp_fold;
+    static constexpr auto residuals = k_vgicp_residuals;
+    static constexpr const char *reduce_range = "pcr:vgicp_reduce", *robust_range = "pcr:vgicp_robust", *residuals_range = "pcr:vgicp_residuals";
+};
 
 extern "C" pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    CtxScope scope(t->ctx);
-    return pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, nullptr, out);
+    return match_linearize<VgicpUnit>(t, s, T, max_dist, nullptr, flags, out);
 }
-
-// the host-driven Gauss-Newton loop of pcr_align (api.hip: pcr_align_host_loop) over the pass: same gn_step, same trace rows
 extern "C" pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                       unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_vgicp, t, s, PCR_VPLANE, nullptr, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<VgicpUnit>(t, s, T_init, max_iter, tol, max_dist, nullptr, flags, T_out, iterations, trace_or_null);
 }
-
-// ---- robust kernels and residuals (include/pcr.h) -----------------------------------------------------------------------
-// params of the robust pcr_pass_fn: the checked kernel of the call.  PCR_ROBUST_NONE: the plain pass
-static pcr_status pcr_run_vgicp_robust(pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist, unsigned flags, const void *params,
-                                       double out[29]) {
-    const RobustK *rb = (const RobustK *)params;
-    if (rb->kind == PCR_ROBUST_NONE || t->n == 0) return pcr_run_vgicp(t, s, kind, T, max_dist, flags, nullptr, out);   // (no kept voxel: zeros)
-    PCR_TRY(check_vgicp_payloads(t, s));
-    const RobustSide<VgicpArgs> va{{{s->cov}, t->vcov, nullptr}, *rb};
-    return match_pass(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_robust", k_vgicp_robust, k_vgicp_fold, va, out);
-}
-
 extern "C" pcr_status pcr_vgicp_linearize_robust(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_robust *rb,
                                                  unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    RobustK k;
-    PCR_TRY(robust_args(rb, &k));
-    CtxScope scope(t->ctx);
-    return pcr_run_vgicp_robust(t, s, PCR_VPLANE, T, max_dist, flags, &k, out);
+    return match_linearize<VgicpUnit>(t, s, T, max_dist, rb, flags, out);
 }
-
 extern "C" pcr_status pcr_vgicp_align_robust(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                              const pcr_robust *rb, unsigned flags, double T_out[16], int *iterations, double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    RobustK k;
-    PCR_TRY(robust_args(rb, &k));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(pcr_run_vgicp_robust, t, s, PCR_VPLANE, &k, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    return match_align<VgicpUnit>(t, s, T_init, max_iter, tol, max_dist, rb, flags, T_out, iterations, trace_or_null);
 }
-
 extern "C" pcr_status pcr_vgicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
-    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
-    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
-    PCR_TRY(check_vgicp_payloads(t, s));
-    if (t->n == 0) {                                 // no kept voxel: no match, once the plain pass's checks have passed
-        double zeros[29];
-        PCR_TRY(pcr_run_vgicp(t, s, PCR_VPLANE, T, max_dist, flags, nullptr, zeros));
-        for (int64_t i = 0; i < s->n; ++i) s_out[i] = (double)INFINITY;
-        return PCR_OK;
-    }
-    const VgicpArgs va{{s->cov}, t->vcov, nullptr};
-    return match_residuals_run(t, s, PCR_VPLANE, T, max_dist, flags, "pcr:vgicp_residuals", k_vgicp_residuals, va, s_out);
+    return match_residuals_entry<VgicpUnit>(t, s, T, max_dist, flags, s_out);
 }

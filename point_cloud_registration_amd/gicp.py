@@ -31,31 +31,20 @@ class ScanCovariances:
         return self._gicp_scan(source, None).get_covariances()
 
     def _gicp_scan(self, source, source_cov, fresh=False):
-        """The device copy of ``source`` with covariances on it.  They belong to the ``_capi.Scan``: estimated (or uploaded)
-        once per uploaded scan, gone with it."""
-        if not self._is_target_set:
-            raise ValueError("Target is not set.")
-        # the caller's order is kept (4 bytes per point): given covariances and source_covariance() cross the boundary in it
-        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
-        if source_cov is not None:
+        """The device copy of ``source`` with covariances on it (``MatchPass._payload_scan``)."""
+        def given(n):
             c = _capi.cov6(source_cov)
-            if c.shape != (scan.n, 6):
+            if c.shape != (n, 6):
                 raise ValueError("source_cov must have shape (N, 6) or (N, 3, 3)")
-            tag = ("given", self._digest(c))
-            if getattr(scan, "_gicp_cov", None) != tag:
-                scan.set_covariances(c)
-                scan._gicp_cov = tag
-        else:
-            tag = ("estimated", self.k, self.regularization, self.eps)
-            if getattr(scan, "_gicp_cov", None) != tag:
-                scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
-                scan._gicp_cov = tag
-        return scan
+            return c
+        return self._payload_scan(source, fresh, "_gicp_cov", given if source_cov is not None else None, _capi.Scan.set_covariances,
+                                  ("estimated", self.k, self.regularization, self.eps),
+                                  lambda scan: scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False))
 
 
 class DistributionPass(ScanCovariances, MatchPass):
     """The distribution-to-distribution pass behind ``GICP`` and ``VGICP``.  A subclass supplies the target side:
-    ``set_target``, ``covariance``, its pair of ``_capi`` entry points and ``_match`` for the per-point loop."""
+    ``set_target``, ``covariance``, its ``_UNIT`` and ``_match`` for the per-point loop."""
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
         super().__init__(max_iter, max_dist, tol, k, **kw)
@@ -105,9 +94,7 @@ class DistributionPass(ScanCovariances, MatchPass):
 
 
 class GICP(DistributionPass):
-    _capi_linearize, _capi_align = staticmethod(_capi.gicp_linearize), staticmethod(_capi.gicp_align)
-    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.gicp_linearize_robust), staticmethod(_capi.gicp_align_robust)
-    _capi_residuals = staticmethod(_capi.gicp_residuals)
+    _UNIT = "gicp"
 
     # -- target ----------------------------------------------------------------------------------
     def set_target(self, target, kdree=None, cov=None):

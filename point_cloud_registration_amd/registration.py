@@ -364,18 +364,17 @@ class Registration:
 
 class MatchPass(Registration):
     """The driver of the aligners whose pass has entry points of its own (``GICP``, ``VGICP``, ``SymmetricICP``,
-    ``ColoredICP``): one GPU of one process, ``k`` neighbours for what they estimate.  A subclass supplies its pair of ``_capi``
-    entry points and ``_pass_params``, what they take between ``max_dist`` and the flags; it keeps its own ``set_target``,
-    scan preparation (``_pass_scan``) and ``calc_H_g_e2_no_parallel_ver``.
+    ``ColoredICP``): one GPU of one process, ``k`` neighbours for what they estimate.  A subclass names its unit (``_UNIT``,
+    a row of ``_capi.MATCH_UNITS``) and supplies ``_pass_params``, what the unit's entry points take between ``max_dist`` and
+    the flags; it keeps its own ``set_target``, scan preparation (``_pass_scan``) and ``calc_H_g_e2_no_parallel_ver``.
 
     ``robust`` (``None``, ``"huber"``, ``"cauchy"``, ``"tukey"``, ``"gm"``) with ``robust_scale`` = c weighs every
     correspondence inside the gate by a robust kernel of its squared residual (``math_tools.robust_weight``; ``include/pcr.h``
     says what the squared residual of each class is), inside the pass: ``calc_H_g_e2`` and ``align`` then return the IRLS sums
-    and pose.  ``None`` calls exactly what the class called before there were kernels.  ``residuals`` returns the squared
-    residuals a scale can be chosen from."""
+    and pose.  ``None`` passes no kernel, which the library defines as the plain pass: the bits the class returned before
+    there were kernels.  ``residuals`` returns the squared residuals a scale can be chosen from."""
     KIND = None           # no kind of pcr_linearize
-    _capi_linearize = _capi_align = None
-    _capi_linearize_robust = _capi_align_robust = _capi_residuals = None
+    _UNIT = None          # "gicp", "vgicp", "symm", "color"
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, **kw):
         if kw.get("devices") is not None or kw.get("comm") is not None:
@@ -396,19 +395,37 @@ class MatchPass(Registration):
         """The device copy of ``source`` with what the class's pass needs on it (``source_cov``, ``source_normals``, ...)."""
         raise NotImplementedError
 
+    def _payload_scan(self, source, fresh, attr, given, set_payload, estimated=None, estimate=None):
+        """The device copy of ``source`` with a per-point payload of the class on it (covariances, normals, intensities).  It
+        belongs to the ``_capi.Scan``: uploaded or estimated once per uploaded scan, gone with it.  ``given(n)``: the caller's
+        array, checked for ``n`` points, put there by ``set_payload(scan, array)``; ``None``: ``estimate(scan)``, whose
+        parameters are ``estimated``.  What the scan carries is remembered on it as ``attr``: ``("given", digest)`` or
+        ``estimated``."""
+        if not self._is_target_set:
+            raise ValueError("Target is not set.")
+        # the caller's order is kept (4 bytes per point): payloads cross the boundary in it
+        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
+        if given is not None:
+            array = given(scan.n)
+            tag, put = ("given", self._digest(array)), lambda: set_payload(scan, array)
+        else:
+            tag, put = estimated, lambda: estimate(scan)
+        if getattr(scan, attr, None) != tag:
+            put()
+            setattr(scan, attr, tag)
+        return scan
+
     # (the kernel is an argument of the call, as min_cos and lambda are: nothing of it stays on the scan, which aligners share)
+    def _entry(self, what):
+        return getattr(_capi, f"{self._UNIT}_{what}")
+
     def _native_linearize(self, scan, cur_T):
-        if self._robust is None:
-            return self._capi_linearize(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), self._flags)
-        return self._capi_linearize_robust(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), robust=self._robust,
-                                           flags=self._flags)
+        return self._entry("linearize_robust")(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), robust=self._robust,
+                                               flags=self._flags)
 
     def _native_align(self, scan, cur_T):
-        if self._robust is None:
-            return self._capi_align(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
-                                    self._flags, want_trace=True)
-        return self._capi_align_robust(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
-                                       robust=self._robust, flags=self._flags, want_trace=True)
+        return self._entry("align_robust")(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
+                                           robust=self._robust, flags=self._flags, want_trace=True)
 
     def residuals(self, cur_T, source, *extras, **kw):
         """The squared residual of every point of ``source`` at ``cur_T``, in its order, ``inf`` where the point has no
@@ -416,8 +433,8 @@ class MatchPass(Registration):
         ``robust`` weighs, whatever this object's own kernel; a scale can be chosen from it (its median, say).  The per-class
         extras (``source_cov``, ``source_normals``, ``source_intensity``) are taken exactly as ``calc_H_g_e2`` takes them."""
         scan = self._pass_scan(source, *extras, **kw)
-        return self._capi_residuals(self._target, scan, np.asarray(cur_T, dtype=np.float64), self._max_dist(), *self._pass_params(),
-                                    flags=self._flags)
+        return self._entry("residuals")(self._target, scan, np.asarray(cur_T, dtype=np.float64), self._max_dist(), *self._pass_params(),
+                                        flags=self._flags)
 
     # -- out of scope ----------------------------------------------------------------------------
     def _unsupported(self, what):

@@ -20,9 +20,7 @@ from .registration import MatchPass
 
 
 class SymmetricICP(MatchPass):
-    _capi_linearize, _capi_align = staticmethod(_capi.symm_linearize), staticmethod(_capi.symm_align)
-    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.symm_linearize_robust), staticmethod(_capi.symm_align_robust)
-    _capi_residuals = staticmethod(_capi.symm_residuals)
+    _UNIT = "symm"
 
     def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, min_normal_cos=0.0, **kw):
         super().__init__(max_iter, max_dist, tol, k, **kw)
@@ -73,26 +71,14 @@ class SymmetricICP(MatchPass):
         return scan.get_normals()
 
     def _symm_scan(self, source, source_normals, fresh=False):
-        """The device copy of ``source`` with normals on it.  They belong to the ``_capi.Scan``: estimated (or uploaded)
-        once per uploaded scan, gone with it."""
-        if not self._is_target_set:
-            raise ValueError("Target is not set.")
-        # the caller's order is kept (4 bytes per point): given normals and source_normals() cross the boundary in it
-        scan = self._scan_for(source, fresh=fresh, flags=_capi.FLAG_KEEP_ORDER)
-        if source_normals is not None:
-            n = np.ascontiguousarray(source_normals, dtype=np.float32)
-            if n.shape != (scan.n, 3):
+        """The device copy of ``source`` with normals on it (``MatchPass._payload_scan``)."""
+        def given(n):
+            nrm = np.ascontiguousarray(source_normals, dtype=np.float32)
+            if nrm.shape != (n, 3):
                 raise ValueError("source_normals must have shape (N, 3)")
-            tag = ("given", self._digest(n))
-            if getattr(scan, "_symm_nrm", None) != tag:
-                scan.set_normals(n)
-                scan._symm_nrm = tag
-        else:
-            tag = ("estimated", self.k)
-            if getattr(scan, "_symm_nrm", None) != tag:
-                scan.estimate_normals(self.k, want=False)
-                scan._symm_nrm = tag
-        return scan
+            return nrm
+        return self._payload_scan(source, fresh, "_symm_nrm", given if source_normals is not None else None, _capi.Scan.set_normals,
+                                  ("estimated", self.k), lambda scan: scan.estimate_normals(self.k, want=False))
 
     def _pass_scan(self, source, source_normals=None):
         return self._symm_scan(source, source_normals)

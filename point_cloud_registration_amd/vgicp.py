@@ -12,15 +12,12 @@ determinant of exactly 0 is replaced by 1e6, the rule of ``calc_icov``.
 
 import numpy as np
 
-from . import _capi
 from .gicp import _MODES, DistributionPass
 from .voxel import VoxelGrid
 
 
 class VGICP(DistributionPass):
-    _capi_linearize, _capi_align = staticmethod(_capi.vgicp_linearize), staticmethod(_capi.vgicp_align)
-    _capi_linearize_robust, _capi_align_robust = staticmethod(_capi.vgicp_linearize_robust), staticmethod(_capi.vgicp_align_robust)
-    _capi_residuals = staticmethod(_capi.vgicp_residuals)
+    _UNIT = "vgicp"
 
     def __init__(self, voxel_size=1.0, max_iter=30, max_dist=2, tol=1e-3, k=10, eps=1e-3, regularization="plane", **kw):
         super().__init__(max_iter, max_dist, tol, k, eps, regularization, **kw)

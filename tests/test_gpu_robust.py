@@ -409,6 +409,79 @@ def test_refusals(sides, name):
         getattr(capi, f"{name}_align_robust")(side.tgt, s, side.T, 5, 1e-3, side.md, *side.extra, robust=(3, tiny))
 
 
+@pytest.mark.parametrize("name, word", [("symm", "min_cos"), ("color", "lambda_geometric")])
+def test_unit_parameter_is_refused_first(sides, name, word):
+    """min_cos / lambda_geometric outside [0, 1] or NaN: PCR_ERR_INVALID from all five entry points with every output
+    untouched, and the message names the parameter -- also under a kernel that would itself be refused (the parameter is
+    checked before the kernel) and on a scan without its payload (before PCR_ERR_NO_TARGET)."""
+    import ctypes
+    side, capi = sides[name], sides[name].capi
+    L = capi.lib()
+    T = np.ascontiguousarray(side.T, dtype=np.float64).reshape(16)
+    with_payload = side.upload(np.arange(257))
+    bare = capi.Scan(side.ctx, np.ascontiguousarray(side.scan[:257]), flags=capi.FLAG_KEEP_ORDER)
+    entry = lambda what: getattr(L, f"pcr_{name}_{what}")
+    good, keep_good = capi._rb((1, 1.0))
+    bad, keep_bad = capi._rb((5, 1.0))
+
+    def refused(st, what):
+        msg = L.pcr_last_error().decode()
+        assert st == capi.PCR_ERR_INVALID and word in msg and "robust" not in msg, (what, st, msg)
+
+    for s in (with_payload, bare):
+        t, h = side.tgt.handle, s.handle
+        for v in (1.5, -0.1, float("nan")):
+            for mid in ((v,), (v, good), (v, bad)):
+                rob = "_robust" if len(mid) == 2 else ""
+                out = np.full(29, 7.25)
+                refused(entry("linearize" + rob)(t, h, T, side.md, *mid, 0, out), ("linearize" + rob, v))
+                assert np.all(out == 7.25)
+                T_out, iters, trace = np.full(16, 7.25), ctypes.c_int(-3), np.full((2, 45), 7.25)
+                refused(entry("align" + rob)(t, h, T, 2, 1e-3, side.md, *mid, 0, T_out, ctypes.byref(iters),
+                                             trace.ctypes.data_as(ctypes.c_void_p)), ("align" + rob, v))
+                assert np.all(T_out == 7.25) and np.all(trace == 7.25) and iters.value == -3
+            s_out = np.full((257, side.m), 7.25)
+            refused(entry("residuals")(t, h, T, side.md, v, 0, s_out.ctypes.data_as(ctypes.c_void_p)), ("residuals", v))
+            assert np.all(s_out == 7.25)
+    # (the same calls with a parameter inside [0, 1]: the bad kernel and the missing payload are what is refused)
+    out = np.full(29, 7.25)
+    assert entry("linearize_robust")(side.tgt.handle, with_payload.handle, T, side.md, *side.extra, bad, 0, out) == capi.PCR_ERR_INVALID
+    assert "robust" in L.pcr_last_error().decode() and np.all(out == 7.25)
+    assert entry("linearize_robust")(side.tgt.handle, bare.handle, T, side.md, *side.extra, good, 0, out) == capi.PCR_ERR_NO_TARGET
+    assert np.all(out == 7.25)
+
+
+def test_empty_voxel_target_under_a_kernel(g2):
+    """The five-point target of test_gpu_vgicp.test_target_with_no_kept_voxel, where set_target accepts it: no voxel, so no
+    match whatever the kernel -- 29 zeros from a pass, inf for every point from residuals, and align ends as it ends with
+    robust=None."""
+    import point_cloud_registration_amd as pcr
+    pts, src = np.ascontiguousarray(g2["target"][:5]), g2["source"]
+
+    def ending(reg):
+        try:
+            return "pose", reg.align(src).tobytes()
+        except Exception as exc:                             # noqa: BLE001
+            return type(exc).__name__, None
+
+    accepted, ends = [], {}
+    for kind in (None,) + rc.KINDS:
+        reg = pcr.VGICP(voxel_size=1.0, robust=kind, robust_scale=1.0)
+        try:
+            reg.set_target(pts)
+        except Exception:                                    # noqa: BLE001
+            continue
+        accepted.append(kind)
+        H, g, e2 = reg.calc_H_g_e2(np.eye(4), src)
+        assert not H.any() and not g.any() and e2 == 0.0 and reg.last_correspondences == 0, kind
+        s = reg.residuals(np.eye(4), src)
+        assert s.shape == (len(src),) and np.all(np.isposinf(s)), kind
+        ends[kind] = ending(reg)
+    print(f"accepted under {accepted}: align ends {ends}")
+    assert len(accepted) in (0, 5)
+    assert all(e == ends[None] for e in ends.values())
+
+
 # ----------------------------------------------------------------------------- 6. align on the end-to-end case
 def _e2e_reg(name, capi, ctx, case, **kw):
     """(aligner with the case's target and GIVEN payloads on it, keyword arguments of its calc_H_g_e2 / align)."""
