@@ -564,6 +564,69 @@ PCR_API pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const doub
 PCR_API pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                        unsigned flags, double *s_out);
 
+/* ---- adaptive pass: trimmed ICP and robust scales taken from each pass's own residuals ---------
+ * No reference counterpart (Chetverikov et al.: "The Trimmed Iterative Closest Point Algorithm", ICPR 2002; what PCL offers as
+ * CorrespondenceRejectorTrimmed / CorrespondenceRejectorMedianDistance and libpointmatcher as TrimmedDistOutlierFilter /
+ * MedianDistOutlierFilter): the threshold of a trim, or the scale c of a robust kernel, is an order statistic of the pass's OWN
+ * squared residuals, found on the device between the search and the reduce -- no host round trip, the one stream
+ * synchronisation of a pass.  New entry points only; the plain and the robust ones above keep their kernels and their bits.
+ * One pass at pose T:
+ *   search and gates   the search, the distance gate, the unit's own gate and the det == 0 rule are the plain pass's
+ *   key     every scan point gets a key in device order (no caller order is needed: PCR_FLAG_KEEP_ORDER is not required): the
+ *           squared residual s that pcr_*_residuals defines; for pcr_color_* s_G + s_C, one addition, geometric row first;
+ *           +inf where the point has no correspondence or a gate drops it
+ *   rank    m = the number of keys < +inf = the plain pass's out[28], and out[28] here;  k = max(1, floor(quantile * m)), the
+ *           product taken once in float64.  m = 0: all 29 sums are zero and stats = (+inf, 0, 0, 0)
+ *   tau     the k-th smallest key (1-based), exact, by pcr_order_statistic's selection on the device
+ *   PCR_ROBUST_TRIM    a correspondence is kept iff its STORED key <= tau (not a recomputation: the kept count is n_le by
+ *           construction); ties at tau are all kept, so there is no index tie-break and n_le >= k.  Kept terms enter with weight
+ *           exactly 1 through the robust pass's weighted accumulation (a product with 1 is exact), a dropped one with weight 0.
+ *           factor is not read
+ *   PCR_ROBUST_HUBER .. PCR_ROBUST_GM    c = factor * sqrt(tau) and c2 = c * c, both taken once on the device, in float64, by
+ *           the selection's last kernel; the robust reduce of the unit then runs with that kernel read from device memory: the
+ *           same points per lane, the same order of operations, a weight per row for pcr_color_*, exactly as
+ *           pcr_*_linearize_robust with scale = c -- whose 29 values it returns bit for bit.  If c2 is not > 0 (tau = 0: a scan
+ *           that is a subset of the target at the true pose; underflow) every kernel takes its limit for c -> 0:
+ *           w = (s == 0 ? 1 : 0)
+ *   stats   (tau, c, n_le, k): n_le the number of keys <= tau; c = 0 under PCR_ROBUST_TRIM
+ * The selection never rounds, orders keys as float64 `<` does and does not depend on its grid: two calls return the same bits.
+ * pcr_*_linearize_adaptive: the refusals of the plain call in their order (NULL arguments, the unit's own parameter first),
+ *   then PCR_ERR_INVALID for a kind outside 1 .. 5, a quantile outside (0, 1] or NaN, or (M-estimators only) a factor that is
+ *   not finite and > 0.  out and stats are then untouched.  pcr_*_linearize_robust / _align_robust keep refusing kind 5.
+ * pcr_*_align_adaptive: the host-driven loop of *_align over this pass: same step, same stop rule, same trace rows (16 + 29
+ *   doubles), PCR_ERR_SINGULAR as there; stats_or_null takes 4 doubles per iteration.  A refusal leaves every output untouched.
+ * pcr_order_statistic: the selection on its own, over n host keys: *value = the k-th smallest (1-based) of the keys < +inf,
+ *   *n_le = the number of keys <= *value.  Exact; the order is that of float64 `<` (negative keys, -0.0 == +0.0 -- returned as
+ *   +0.0 --, denormals); a NaN key counts as outside, as +inf does.  PCR_ERR_INVALID with untouched outputs for NULL arguments,
+ *   n < 1, k < 1 or k above the number of keys < +inf.                                                                      */
+#define PCR_ROBUST_TRIM 5 /* valid in pcr_adaptive only */
+typedef struct {
+    int kind;        /* PCR_ROBUST_HUBER .. PCR_ROBUST_GM, or PCR_ROBUST_TRIM */
+    double quantile; /* in (0, 1] */
+    double factor;   /* c = factor * sqrt(tau); not read under PCR_ROBUST_TRIM */
+} pcr_adaptive;
+PCR_API pcr_status pcr_order_statistic(pcr_context *ctx, const double *keys, int64_t n, int64_t k, double *value, int64_t *n_le);
+PCR_API pcr_status pcr_gicp_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_adaptive *ad,
+                                               unsigned flags, double out[29], double stats[4]);
+PCR_API pcr_status pcr_gicp_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                           const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                           double *trace_or_null, double *stats_or_null);
+PCR_API pcr_status pcr_vgicp_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_adaptive *ad,
+                                                unsigned flags, double out[29], double stats[4]);
+PCR_API pcr_status pcr_vgicp_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                            const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                            double *trace_or_null, double *stats_or_null);
+PCR_API pcr_status pcr_symm_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos,
+                                               const pcr_adaptive *ad, unsigned flags, double out[29], double stats[4]);
+PCR_API pcr_status pcr_symm_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                           double min_cos, const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                           double *trace_or_null, double *stats_or_null);
+PCR_API pcr_status pcr_color_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
+                                                const pcr_adaptive *ad, unsigned flags, double out[29], double stats[4]);
+PCR_API pcr_status pcr_color_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                            double lambda_geometric, const pcr_adaptive *ad, unsigned flags, double T_out[16],
+                                            int *iterations, double *trace_or_null, double *stats_or_null);
+
 /* ---- batches: many scans and / or start poses against ONE target in one launch -----------
  * No reference counterpart (Registration.align takes one scan, registration.py:71).  A scan of the sizes people register
  * (up to ~260 k points) runs as ONE fused kernel per Gauss-Newton iteration and is latency-bound: it fills a fraction of the

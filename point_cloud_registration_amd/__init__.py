@@ -8,7 +8,7 @@ a C ABI (include/pcr.h); there is no CPU fallback.
 
 from .registration import Registration
 from .math_tools import (makeRt, expSO3, makeT, skews, huber_weight, plus, transform_points,
-                         skew_time_vector, skew, skew2, robust_weight)
+                         skew_time_vector, skew, skew2, robust_weight, trim_threshold)
 from .voxelized_plane_icp import VPlaneICP
 from .plane_icp import PlaneICP
 from .icp import ICP
@@ -33,5 +33,5 @@ __all__ = [
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
     "score_poses", "fit_rigid", "ransac_pose", "fgr_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
-    "robust_weight",
+    "robust_weight", "trim_threshold",
 ]

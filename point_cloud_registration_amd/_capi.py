@@ -195,6 +195,19 @@ PROTOTYPES = {
     "pcr_color_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
                                          C.POINTER(C.c_int), _vp]),
     "pcr_color_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _vp]),
+    # the adaptive pass of the same four: a trim or a robust scale from each pass's own residuals, and the exact order statistic
+    # behind it (include/pcr.h); ad: a pcr_adaptive by pointer; stats: 4 doubles (per iteration)
+    "pcr_order_statistic": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "pcr_gicp_linearize_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_double, _vp, C.c_uint, _f64p, _f64p]),
+    "pcr_gicp_align_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, _vp, C.c_uint, _f64p, C.POINTER(C.c_int), _vp, _vp]),
+    "pcr_vgicp_linearize_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_double, _vp, C.c_uint, _f64p, _f64p]),
+    "pcr_vgicp_align_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, _vp, C.c_uint, _f64p, C.POINTER(C.c_int), _vp, _vp]),
+    "pcr_symm_linearize_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, _vp, C.c_uint, _f64p, _f64p]),
+    "pcr_symm_align_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
+                                          C.POINTER(C.c_int), _vp, _vp]),
+    "pcr_color_linearize_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, _vp, C.c_uint, _f64p, _f64p]),
+    "pcr_color_align_adaptive": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
+                                           C.POINTER(C.c_int), _vp, _vp]),
     # batches: many scans / start poses against one target in one launch (include/pcr.h)
     "pcr_scan_batch_create": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_uint, C.POINTER(_vp)]),
     "pcr_scan_batch_size": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
@@ -1421,7 +1434,45 @@ def _rb(robust):
     return C.cast(C.pointer(rb), _vp), rb
 
 
-# ---- the entry points of the four match-list aligners (include/pcr.h): one table, five wrappers per unit -----------------
+# ---- the adaptive pass of the same four, and the exact order statistic behind it (include/pcr.h) ----------------------
+ROBUST_TRIM = 5
+ADAPTIVE_KINDS = {"huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY, "gm": ROBUST_GM, "trim": ROBUST_TRIM}
+
+
+class Adaptive(C.Structure):
+    """pcr_adaptive: a kind (ROBUST_HUBER .. ROBUST_TRIM), the quantile and the factor of c = factor * sqrt(tau)."""
+    _fields_ = [("kind", C.c_int), ("quantile", C.c_double), ("factor", C.c_double)]
+
+
+def check_adaptive(kind, quantile, factor=1.0):
+    """``kind`` ("huber", "cauchy", "tukey", "gm", "trim"), ``quantile`` and ``factor`` as (kind, quantile, factor), the library's
+    own rule, else ValueError: the quantile in (0, 1], the factor finite and > 0 (not read under "trim")."""
+    if kind not in ADAPTIVE_KINDS:
+        raise ValueError('adaptive kind must be "huber", "cauchy", "tukey", "gm" or "trim"')
+    quantile, factor = float(quantile), float(factor)
+    if not 0.0 < quantile <= 1.0:                                                                 # (false for NaN)
+        raise ValueError("the quantile (the trim ratio) must be in (0, 1]")
+    if kind != "trim" and not 0.0 < factor < np.inf:
+        raise ValueError("the factor of an adaptive robust scale must be finite and > 0")
+    return ADAPTIVE_KINDS[kind], quantile, factor
+
+
+def _ad(adaptive):
+    """(kind, quantile, factor) -> the pointer argument of a *_adaptive entry point (and the object that keeps it alive)."""
+    ad = Adaptive(int(adaptive[0]), float(adaptive[1]), float(adaptive[2]))
+    return C.cast(C.pointer(ad), _vp), ad
+
+
+def order_statistic(ctx, keys, k):
+    """pcr_order_statistic: the k-th smallest (1-based) of the float64 ``keys`` that are < +inf, found on the device, and the
+    number of keys <= it -> (value, n_le).  Exact: ``value == np.sort(keys)[k - 1]``."""
+    keys = np.ascontiguousarray(keys, dtype=np.float64).ravel()
+    value, n_le = C.c_double(0.0), C.c_int64(0)
+    check(lib().pcr_order_statistic(ctx.handle, _ptr(keys), keys.size, int(k), C.byref(value), C.byref(n_le)))
+    return value.value, n_le.value
+
+
+# ---- the entry points of the four match-list aligners (include/pcr.h): one table, seven wrappers per unit ----------------
 # unit -> (its pass parameter between max_dist and rb / the flags: () or ((name, default),); squared residuals per point)
 MATCH_UNITS = {
     "gicp": ((), 1),
@@ -1445,14 +1496,18 @@ def _trailing(*params):
 
 
 def _match_unit(unit):
-    """The five wrappers of ``unit``, with P its pass parameter (``min_cos=0.0`` / ``lambda_geometric=0.968``; none for gicp, vgicp):
+    """The seven wrappers of ``unit``, with P its pass parameter (``min_cos=0.0`` / ``lambda_geometric=0.968``; none for gicp, vgicp):
       linearize(target, scan, T, max_dist[, P], flags=0) -> the 29 sums of one pass (pcr_<unit>_linearize)
       align(target, scan, T_init, max_iter, tol, max_dist[, P], flags=0, want_trace=False) -> (T, iterations[, trace rows]):
           the host-driven Gauss-Newton loop over the pass, behind the boundary (pcr_<unit>_align)
       linearize_robust(target, scan, T, max_dist[, P], robust=None, flags=0), align_robust(..., max_dist[, P], robust=None, flags=0,
           want_trace=False): the same through pcr_<unit>_*_robust; ``robust``: (kind, scale), or None -> NULL.  P has no default
       residuals(target, scan, T, max_dist[, P], flags=0) -> the squared residuals in the caller's order, (N,) float64 -- color:
-          (N, 2), both rows -- inf where a point has no correspondence (pcr_<unit>_residuals)"""
+          (N, 2), both rows -- inf where a point has no correspondence (pcr_<unit>_residuals)
+      linearize_adaptive(target, scan, T, max_dist[, P], adaptive=(kind, quantile, factor), flags=0) -> (the 29 sums, stats (4,)
+          = tau, c, n_le, k) (pcr_<unit>_linearize_adaptive)
+      align_adaptive(..., max_dist[, P], adaptive=..., flags=0, want_trace=False) -> (T, iterations, stats rows (iterations, 4)
+          [, trace rows]) (pcr_<unit>_align_adaptive)"""
     extra, m = MATCH_UNITS[unit]
     pass_tail, align_tail = _trailing(*extra, ("flags", 0)), _trailing(*extra, ("flags", 0), ("want_trace", False))
 
@@ -1464,9 +1519,9 @@ def _match_unit(unit):
             raise TypeError(f"expected {len(extra)} pass parameter(s) after max_dist, got {len(args)}")
         return tuple(float(v) for v in args)
 
-    def call(what, target, scan, T, max_dist, mid, flags, out):
+    def call(what, target, scan, T, max_dist, mid, flags, *out):
         T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        check(entry(what)(target.handle, scan.handle, T, float(max_dist), *mid, int(flags), out))
+        check(entry(what)(target.handle, scan.handle, T, float(max_dist), *mid, int(flags), *out))
 
     def sums(what, *args):
         out = np.empty(29)
@@ -1498,7 +1553,24 @@ def _match_unit(unit):
         call("residuals", target, scan, T, max_dist, floats(p), flags, _ptr(out))
         return out
 
-    return {f"{unit}_{f.__name__}": f for f in (linearize, align, linearize_robust, align_robust, residuals)}
+    def linearize_adaptive(target, scan, T, max_dist, *args, adaptive, flags=0):
+        ad, keep = _ad(adaptive)
+        out, stats = np.empty(29), np.empty(4)
+        call("linearize_adaptive", target, scan, T, max_dist, floats(args) + (ad,), flags, out, stats)
+        return out, stats
+
+    def align_adaptive(target, scan, T_init, max_iter, tol, max_dist, *args, adaptive, flags=0, want_trace=False):
+        ad, keep = _ad(adaptive)
+        T0 = np.ascontiguousarray(T_init, dtype=np.float64).reshape(16)
+        T, iters = np.zeros(16), C.c_int(0)
+        rows = max(int(max_iter), 1)
+        stats, trace = np.zeros((rows, 4)), np.zeros((rows, 45)) if want_trace else None
+        check(entry("align_adaptive")(target.handle, scan.handle, T0, int(max_iter), float(tol), float(max_dist), *floats(args), ad, int(flags), T,
+                                      C.byref(iters), _ptr(trace), _ptr(stats)))
+        res = (T.reshape(4, 4), iters.value, stats[:iters.value])
+        return res + (trace[:iters.value],) if want_trace else res
+
+    return {f"{unit}_{f.__name__}": f for f in (linearize, align, linearize_robust, align_robust, residuals, linearize_adaptive, align_adaptive)}
 
 
 for _unit in MATCH_UNITS:

@@ -18,8 +18,11 @@
 //   k_color_robust         the same pass with each of the two rows weighed by a robust kernel of its own r r
 //                          (RobustSide<ColorArgs>, COLOR_ROBUST_W points per lane in flight), folded by k_color_fold
 //   k_color_residuals      both rows' r r of every scan point in the caller's order (match_residuals)
-//   ColorUnit              what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
-//                          match_align, match_residuals_entry)
+//   k_color_keys           the adaptive pass (include/pcr.h): a key per scan point in device order (match_residuals<., true>)
+//   k_color_adaptive       k_color_robust's reduce behind the selection over the keys (select.hip), its kernel read from the
+//                          selection's state (AdaptiveSide)
+//   ColorUnit              what the seven entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                          match_align, match_residuals_entry, match_linearize_adaptive, match_align_adaptive)
 //
 // Scan side: pcr_scan::inten, one float per point in device order.  Target side: the PtN records PlaneICP gathers and the
 // 16-byte colour records, 48 bytes per match from two arrays.
@@ -278,6 +281,15 @@ __global__ void __launch_bounds__(256) k_color_robust(const LinArgs a, const Rob
 __global__ void __launch_bounds__(256) k_color_residuals(const LinArgs a, const ColorArgs ca, const uint32_t *order, double *out) {
     match_residuals(a, ca, order, out);
 }
+// the adaptive pass (include/pcr.h: "adaptive pass"): a key per scan point in device order, +inf where there is no
+// correspondence; behind the selection over the keys (select.hip), k_color_robust's reduce with its kernel read from the
+// selection's state (AdaptiveSide), folded by k_color_fold
+__global__ void __launch_bounds__(256) k_color_keys(const LinArgs a, const ColorArgs ca, double *out) {
+    match_residuals<ColorArgs, true>(a, ca, nullptr, out);
+}
+__global__ void __launch_bounds__(256) k_color_adaptive(const LinArgs a, const AdaptiveSide<ColorArgs> ca) {
+    match_reduce<COLOR_ROBUST_W>(a, adaptive_side(ca));
+}
 
 // ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
 // The search is ICP's (its LinArgs carries the PtN records too); the parameter of a call is lambda_geometric, taken through
@@ -304,7 +316,10 @@ struct ColorUnit : MatchUnit {
     static constexpr auto robust = k_color_robust;
     static constexpr auto fold = k_color_fold;
     static constexpr auto residuals = k_color_residuals;
-    static constexpr const char *reduce_range = "pcr:color_reduce", *robust_range = "pcr:color_robust", *residuals_range = "pcr:color_residuals";
+    static constexpr auto keys = k_color_keys;
+    static constexpr auto adaptive = k_color_adaptive;
+    static constexpr const char *reduce_range = "pcr:color_reduce", *robust_range = "pcr:color_robust", *residuals_range = "pcr:color_residuals",
+                                *adaptive_range = "pcr:color_adaptive";
 };
 
 extern "C" pcr_status pcr_color_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
@@ -327,4 +342,13 @@ extern "C" pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const d
 extern "C" pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                           unsigned flags, double *s_out) {
     return match_residuals_entry<ColorUnit>(t, s, T, max_dist, flags, s_out, lambda_geometric);
+}
+extern "C" pcr_status pcr_color_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric, const pcr_adaptive *ad,
+                                                 unsigned flags, double out[29], double stats[4]) {
+    return match_linearize_adaptive<ColorUnit>(t, s, T, max_dist, ad, flags, out, stats, lambda_geometric);
+}
+extern "C" pcr_status pcr_color_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             double lambda_geometric, const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                             double *trace_or_null, double *stats_or_null) {
+    return match_align_adaptive<ColorUnit>(t, s, T_init, max_iter, tol, max_dist, ad, flags, T_out, iterations, trace_or_null, stats_or_null, lambda_geometric);
 }

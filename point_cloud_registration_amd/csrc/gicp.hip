@@ -16,8 +16,11 @@
 //   k_gicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<GicpArgs>, GICP_ROBUST_W
 //                     points per lane in flight), folded by k_gicp_fold
 //   k_gicp_residuals  d^T M d of every scan point in the caller's order (match_residuals)
-//   GicpUnit          what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
-//                     match_align, match_residuals_entry)
+//   k_gicp_keys       the adaptive pass (include/pcr.h): a key per scan point in device order (match_residuals<., true>)
+//   k_gicp_adaptive   k_gicp_robust's reduce behind the selection over the keys (select.hip), its kernel read from the
+//                     selection's state (AdaptiveSide)
+//   GicpUnit          what the seven entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                     match_align, match_residuals_entry, match_linearize_adaptive, match_align_adaptive)
 //
 // Target side: ONE 64-byte aligned record per point in cell-sorted order -- xyz, orig, c6, padding (GicpRec) -- so a
 // correspondence costs one line, the reason PtN exists.  The record is gathered whole (three 16-byte loads of one line); its
@@ -248,6 +251,15 @@ __global__ void __launch_bounds__(256) k_gicp_robust(const LinArgs a, const Robu
 __global__ void __launch_bounds__(256) k_gicp_residuals(const LinArgs a, const GicpArgs ga, const uint32_t *order, double *out) {
     match_residuals(a, ga, order, out);
 }
+// the adaptive pass (include/pcr.h: "adaptive pass"): a key per scan point in device order, +inf where there is no
+// correspondence; behind the selection over the keys (select.hip), k_gicp_robust's reduce with its kernel read from the
+// selection's state (AdaptiveSide), folded by k_gicp_fold
+__global__ void __launch_bounds__(256) k_gicp_keys(const LinArgs a, const GicpArgs ga, double *out) {
+    match_residuals<GicpArgs, true>(a, ga, nullptr, out);
+}
+__global__ void __launch_bounds__(256) k_gicp_adaptive(const LinArgs a, const AdaptiveSide<GicpArgs> ga) {
+    match_reduce<GICP_ROBUST_W>(a, adaptive_side(ga));
+}
 
 // ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
 // The search is ICP's; a call has no parameter of the unit's own
@@ -264,7 +276,10 @@ struct GicpUnit : MatchUnit {
     static constexpr auto robust = k_gicp_robust;
     static constexpr auto fold = k_gicp_fold;
     static constexpr auto residuals = k_gicp_residuals;
-    static constexpr const char *reduce_range = "pcr:gicp_reduce", *robust_range = "pcr:gicp_robust", *residuals_range = "pcr:gicp_residuals";
+    static constexpr auto keys = k_gicp_keys;
+    static constexpr auto adaptive = k_gicp_adaptive;
+    static constexpr const char *reduce_range = "pcr:gicp_reduce", *robust_range = "pcr:gicp_robust", *residuals_range = "pcr:gicp_residuals",
+                                *adaptive_range = "pcr:gicp_adaptive";
 };
 
 extern "C" pcr_status pcr_gicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
@@ -284,4 +299,13 @@ extern "C" pcr_status pcr_gicp_align_robust(pcr_target *t, pcr_scan *s, const do
 }
 extern "C" pcr_status pcr_gicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
     return match_residuals_entry<GicpUnit>(t, s, T, max_dist, flags, s_out);
+}
+extern "C" pcr_status pcr_gicp_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_adaptive *ad,
+                                                 unsigned flags, double out[29], double stats[4]) {
+    return match_linearize_adaptive<GicpUnit>(t, s, T, max_dist, ad, flags, out, stats);
+}
+extern "C" pcr_status pcr_gicp_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                             double *trace_or_null, double *stats_or_null) {
+    return match_align_adaptive<GicpUnit>(t, s, T_init, max_iter, tol, max_dist, ad, flags, T_out, iterations, trace_or_null, stats_or_null);
 }

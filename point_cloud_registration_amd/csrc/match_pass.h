@@ -11,7 +11,8 @@
 //   payloads(t, s)            PCR_ERR_NO_TARGET and its message where target or scan lack what the pass reads
 //   side(t, s, p)             the SIDE of a call, everything but rows
 //   reduce, robust, fold, residuals                 the four __global__ one-liners
-//   reduce_range, robust_range, residuals_range     their roctx range names
+//   keys, adaptive                                  the two of the adaptive pass: a key per scan point, the reduce behind the selection
+//   reduce_range, robust_range, residuals_range, adaptive_range     their roctx range names
 //   no_match(t, s, max_dist, &none)                 MatchUnit: never; vgicp.hip: a target with no kept voxel
 //
 // A SIDE is a unit's kernel-argument struct (GicpArgs, VgicpArgs, SymmArgs, ColorArgs): its arrays, its parameters, rows -- and
@@ -32,6 +33,7 @@
 
 #include "host_util.h"
 #include "pass_device.h"
+#include "select.h"
 
 // ---- robust weights (include/pcr.h: "robust kernels") ---------------------------------------------------------------------
 // kind, c and c2 = c * c (taken once on the host) travel by value
@@ -103,6 +105,22 @@ struct RobustSide : SIDE {
     }
 };
 
+// The SIDE of the adaptive pass (include/pcr.h: "adaptive pass"): RobustSide with the kernel read from what the selection left
+// on the device (select.h: w_kind, w_c, w_c2) by the kernel before the loop (adaptive_side) -- wave-uniform by construction and
+// kept in scalar registers, as the by-value RobustK of the robust kernels is.  The variants of the pass are data there: a trim
+// is the kernel whose weight is exactly 1 over a match list from which the selection dropped the keys above tau, the limit for
+// c -> 0 is Huber's at c = 0
+template <typename SIDE>
+struct AdaptiveSide : RobustSide<SIDE> {
+    const SelectState *st;
+};
+template <typename SIDE>
+__device__ __forceinline__ AdaptiveSide<SIDE> adaptive_side(AdaptiveSide<SIDE> sd) {
+    sd.rb.kind = __builtin_amdgcn_readfirstlane(sd.st->w_kind);
+    sd.rb.c = uniform_f64(sd.st->w_c); sd.rb.c2 = uniform_f64(sd.st->w_c2);
+    return sd;
+}
+
 // W points per lane in flight, the phases of reduce_stream (pass_device.h):
 //   phase A  index, coordinates and Scan of all W points.  A point past the end reads the lane's first point.
 //   phase B  the W matches.  No match: element 0 through a select on the index -- always there -- and skipped in phase C;
@@ -167,8 +185,10 @@ __device__ __forceinline__ void match_fold(const double *__restrict__ rows, int 
 
 // The sibling of match_reduce that writes instead of accumulating: SIDE::M squared residuals per scan point, +inf where the
 // point has no match or a gate drops it, at the point's CALLER index through `order` (pcr_scan::order; NULL: the device order
-// is the caller's), as k_rows scatters.  One point per lane and trip: nothing is folded, nothing depends on the grid
-template <typename SIDE>
+// is the caller's), as k_rows scatters.  One point per lane and trip: nothing is folded, nothing depends on the grid.
+// KEY: the key of the adaptive pass instead -- ONE double per point, the sum of its SIDE::M squared residuals in row order
+// (ColoredICP: s_G + s_C, one addition), in device order; `order` is not read
+template <typename SIDE, bool KEY = false>
 __device__ __forceinline__ void match_residuals(const LinArgs &a, const SIDE &sd, const uint32_t *__restrict__ order, double *__restrict__ out) {
     const PoseK &P = a.hp;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -187,9 +207,16 @@ __device__ __forceinline__ void match_residuals(const LinArgs &a, const SIDE &sd
             xform(P, x, y, z, tx, ty, tz);
             sd.each(a, P, x, y, z, tx, ty, tz, sc, m, typename SIDE::Resid(s, P, x, y, z));
         }
-        const int64_t dest = order ? (int64_t)order[i] : i;
+        if constexpr (KEY) {
+            double key = s[0];
 #pragma unroll
-        for (int k = 0; k < SIDE::M; ++k) out[SIDE::M * dest + k] = s[k];
+            for (int k = 1; k < SIDE::M; ++k) key = key + s[k];
+            out[i] = key;
+        } else {
+            const int64_t dest = order ? (int64_t)order[i] : i;
+#pragma unroll
+            for (int k = 0; k < SIDE::M; ++k) out[SIDE::M * dest + k] = s[k];
+        }
     }
 }
 
@@ -335,3 +362,122 @@ static pcr_status match_residuals_entry(pcr_target *t, pcr_scan *s, const double
     return match_residuals_run<U>(t, s, T, max_dist, flags, U::side(t, s, p), s_out);
 }
 
+
+// ---- the adaptive pass (include/pcr.h: "adaptive pass") --------------------------------------------------------------------
+// the caller's pcr_adaptive, checked
+static inline pcr_status adaptive_args(const pcr_adaptive *ad, pcr_adaptive *k) {
+    PCR_REQUIRE(ad->kind >= PCR_ROBUST_HUBER && ad->kind <= PCR_ROBUST_TRIM, "adaptive kind must be PCR_ROBUST_HUBER .. PCR_ROBUST_TRIM");
+    PCR_REQUIRE(ad->quantile > 0.0 && ad->quantile <= 1.0, "adaptive quantile must be in (0, 1]");                         // (false for NaN)
+    PCR_REQUIRE(ad->kind == PCR_ROBUST_TRIM || (ad->factor > 0.0 && isfinite(ad->factor)), "adaptive factor must be finite and > 0");
+    *k = *ad;
+    return PCR_OK;
+}
+
+// (m = 0, and what a pass without a launch returns)
+static inline void adaptive_nothing(double out[29], double stats[4]) {
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    stats[0] = (double)INFINITY; stats[1] = stats[2] = stats[3] = 0.0;
+}
+
+// What a call hands to every pass: the unit's block, the checked kernel, and -- from *_align_adaptive -- where the stats of
+// the next pass go (4 doubles per pass, advanced by the pass)
+template <typename U>
+struct AdaptiveParams {
+    typename U::Params unit;
+    pcr_adaptive ad;
+    mutable double *stats_rows;
+};
+
+// search -> key -> select (-> drop, under PCR_ROBUST_TRIM: the correspondences whose stored key is above tau leave the match
+// list of the call) -> reduce -> fold, and 29 + 5 doubles back: one stream synchronisation.  out[28] is m, the number of keys
+// < +inf, which is what the reduce counts -- but for a trim, where it counts the kept ones: n_le by construction
+template <typename U>
+static pcr_status adaptive_pass(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, const AdaptiveParams<U> &p,
+                                double out[29], double stats[4]) {
+    PCR_TRY(U::payloads(t, s));
+    bool none;
+    PCR_TRY(U::no_match(t, s, max_dist, &none));
+    if (none) { adaptive_nothing(out, stats); return PCR_OK; }
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
+    adaptive_nothing(out, stats);
+    if (s->n == 0) return PCR_OK;
+    pcr_context *ctx = t->ctx;
+    const int nb = choose_blocks(ctx, s->n);         // n and the device only
+    DevBuf<double> keys, rows, sums;
+    DevBuf<SelectState> st;
+    HIP_TRY(keys.alloc((size_t)s->n)); HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(40)); HIP_TRY(st.alloc(1));
+    const typename U::Side sd = U::side(t, s, p.unit);
+    AdaptiveSide<typename U::Side> asd{{sd, RobustK{PCR_ROBUST_HUBER, 0.0, 0.0}}, st.p};
+    asd.rows = rows.p;
+    // PCR_ADAPTIVE_TIMES=1 (developer, tools/adaptive_time.py): events around the key kernel and the selection, the two phases
+    // the pass has beyond the robust one; their milliseconds on stderr
+    static const bool times = env_flag("PCR_ADAPTIVE_TIMES");
+    StageTimes ev;
+    HIP_TRY(ev.init(times));
+    {
+        RoctxRange range(U::adaptive_range);
+        ev.mark(0, ctx->stream);
+        hipLaunchKernelGGL(U::keys, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, sd, keys.p);
+        ev.mark(1, ctx->stream);
+        PCR_TRY(pcr_select_launch(ctx, keys.p, s->n, p.ad.quantile, 0, p.ad.kind, p.ad.factor, st.p, sums.p + 32));
+        if (p.ad.kind == PCR_ROBUST_TRIM) PCR_TRY(pcr_select_drop_launch(ctx, keys.p, s->n, st.p, nn.p, PCR_NONE));
+        ev.mark(2, ctx->stream);
+        hipLaunchKernelGGL(U::adaptive, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, asd);
+        hipLaunchKernelGGL(U::fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
+    }
+    HIP_TRY(hipGetLastError());
+    double h[37];
+    HIP_TRY(hipMemcpyAsync(h, sums.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ev.on) fprintf(stderr, "pcr_adaptive_times %s n %lld keys_ms %.4f select_ms %.4f\n", U::adaptive_range, (long long)s->n, ev.ms(0), ev.ms(1));
+    for (int i = 0; i < 29; ++i) out[i] = h[i];
+    for (int i = 0; i < 4; ++i) stats[i] = h[32 + i];
+    out[28] = h[36];
+    return PCR_OK;
+}
+
+// the pcr_pass_fn of the adaptive pass
+template <typename U>
+static pcr_status adaptive_run(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
+    const AdaptiveParams<U> *p = (const AdaptiveParams<U> *)params;
+    double stats[4];
+    PCR_TRY(adaptive_pass<U>(t, s, T, max_dist, flags, *p, out, stats));
+    if (p->stats_rows) {
+        for (int i = 0; i < 4; ++i) p->stats_rows[i] = stats[i];
+        p->stats_rows += 4;
+    }
+    return PCR_OK;
+}
+
+// The two entry points of a unit behind its *_linearize_adaptive and *_align_adaptive: the order of refusals of
+// match_linearize, the adaptive kernel in the place of the robust one
+template <typename U, typename... Raw>
+static pcr_status match_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_adaptive *ad, unsigned flags,
+                                           double out[29], double stats[4], Raw... raw) {
+    PCR_REQUIRE(t && s && T && out && stats && ad, "NULL argument");
+    AdaptiveParams<U> p;
+    PCR_TRY(U::check(&p.unit, raw...));
+    PCR_TRY(adaptive_args(ad, &p.ad));
+    p.stats_rows = nullptr;
+    CtxScope scope(t->ctx);
+    double o[29], st[4];                             // (a pass refused behind the search writes nothing)
+    PCR_TRY(adaptive_pass<U>(t, s, T, max_dist, flags, p, o, st));
+    for (int i = 0; i < 29; ++i) out[i] = o[i];
+    for (int i = 0; i < 4; ++i) stats[i] = st[i];
+    return PCR_OK;
+}
+
+template <typename U, typename... Raw>
+static pcr_status match_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                       const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations, double *trace_or_null,
+                                       double *stats_or_null, Raw... raw) {
+    PCR_REQUIRE(t && s && T_init && T_out && ad, "NULL argument");
+    AdaptiveParams<U> p;
+    PCR_TRY(U::check(&p.unit, raw...));
+    PCR_TRY(adaptive_args(ad, &p.ad));
+    p.stats_rows = stats_or_null;
+    CtxScope scope(t->ctx);
+    return pcr_align_host_loop(adaptive_run<U>, t, s, U::kind, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+}

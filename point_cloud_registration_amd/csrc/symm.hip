@@ -14,8 +14,11 @@
 //   k_symm_robust        the same pass with every correspondence weighed by a robust kernel of r r (RobustSide<SymmArgs>,
 //                        SYMM_ROBUST_W points per lane in flight), folded by k_symm_fold
 //   k_symm_residuals     r r of every scan point in the caller's order (match_residuals)
-//   SymmUnit             what the five entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
-//                        match_align, match_residuals_entry)
+//   k_symm_keys          the adaptive pass (include/pcr.h): a key per scan point in device order (match_residuals<., true>)
+//   k_symm_adaptive      k_symm_robust's reduce behind the selection over the keys (select.hip), its kernel read from the
+//                        selection's state (AdaptiveSide)
+//   SymmUnit             what the seven entry points differ in; the rest of them is match_pass.h's (match_run, match_linearize,
+//                        match_align, match_residuals_entry, match_linearize_adaptive, match_align_adaptive)
 //
 // Scan side: pcr_scan::nrm, three floats per point in device order (12 bytes beside the 16 of index and coordinates).  Target
 // side: the PtN records PlaneICP gathers -- point and normal in one 32-byte sector.
@@ -152,6 +155,15 @@ __global__ void __launch_bounds__(256) k_symm_robust(const LinArgs a, const Robu
 __global__ void __launch_bounds__(256) k_symm_residuals(const LinArgs a, const SymmArgs sa, const uint32_t *order, double *out) {
     match_residuals(a, sa, order, out);
 }
+// the adaptive pass (include/pcr.h: "adaptive pass"): a key per scan point in device order, +inf where there is no
+// correspondence; behind the selection over the keys (select.hip), k_symm_robust's reduce with its kernel read from the
+// selection's state (AdaptiveSide), folded by k_symm_fold
+__global__ void __launch_bounds__(256) k_symm_keys(const LinArgs a, const SymmArgs sa, double *out) {
+    match_residuals<SymmArgs, true>(a, sa, nullptr, out);
+}
+__global__ void __launch_bounds__(256) k_symm_adaptive(const LinArgs a, const AdaptiveSide<SymmArgs> sa) {
+    match_reduce<SYMM_ROBUST_W>(a, adaptive_side(sa));
+}
 
 // ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
 // The search is ICP's (its LinArgs carries the PtN records too: pass.hip, pass_fill_lin); the parameter of a call is the normal
@@ -176,7 +188,10 @@ struct SymmUnit : MatchUnit {
     static constexpr auto robust = k_symm_robust;
     static constexpr auto fold = k_symm_fold;
     static constexpr auto residuals = k_symm_residuals;
-    static constexpr const char *reduce_range = "pcr:symm_reduce", *robust_range = "pcr:symm_robust", *residuals_range = "pcr:symm_residuals";
+    static constexpr auto keys = k_symm_keys;
+    static constexpr auto adaptive = k_symm_adaptive;
+    static constexpr const char *reduce_range = "pcr:symm_reduce", *robust_range = "pcr:symm_robust", *residuals_range = "pcr:symm_residuals",
+                                *adaptive_range = "pcr:symm_adaptive";
 };
 
 extern "C" pcr_status pcr_symm_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
@@ -199,4 +214,13 @@ extern "C" pcr_status pcr_symm_align_robust(pcr_target *t, pcr_scan *s, const do
 extern "C" pcr_status pcr_symm_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, unsigned flags,
                                          double *s_out) {
     return match_residuals_entry<SymmUnit>(t, s, T, max_dist, flags, s_out, min_cos);
+}
+extern "C" pcr_status pcr_symm_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double min_cos, const pcr_adaptive *ad,
+                                                 unsigned flags, double out[29], double stats[4]) {
+    return match_linearize_adaptive<SymmUnit>(t, s, T, max_dist, ad, flags, out, stats, min_cos);
+}
+extern "C" pcr_status pcr_symm_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             double min_cos, const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                             double *trace_or_null, double *stats_or_null) {
+    return match_align_adaptive<SymmUnit>(t, s, T_init, max_iter, tol, max_dist, ad, flags, T_out, iterations, trace_or_null, stats_or_null, min_cos);
 }

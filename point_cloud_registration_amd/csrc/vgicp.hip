@@ -15,8 +15,12 @@
 //   k_vgicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<VgicpArgs>,
 //   k_vgicp_residuals  VGICP_ROBUST_W points per lane in flight), folded by k_vgicp_fold; d^T M d of every scan point in the
 //                      caller's order (match_residuals)
-//   VgicpUnit          what the five entry points differ in -- the target with no kept voxel among it; the rest of them is
-//                      match_pass.h's (match_run, match_linearize, match_align, match_residuals_entry)
+//   k_vgicp_keys       the adaptive pass (include/pcr.h): a key per scan point in device order (match_residuals<., true>)
+//   k_vgicp_adaptive   k_vgicp_robust's reduce behind the selection over the keys (select.hip), its kernel read from the
+//                      selection's state (AdaptiveSide)
+//   VgicpUnit          what the seven entry points differ in -- the target with no kept voxel among it; the rest of them is
+//                      match_pass.h's (match_run, match_linearize, match_align, match_residuals_entry,
+//                      match_linearize_adaptive, match_align_adaptive)
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -144,6 +148,15 @@ __global__ void __launch_bounds__(256) k_vgicp_robust(const LinArgs a, const Rob
 __global__ void __launch_bounds__(256) k_vgicp_residuals(const LinArgs a, const VgicpArgs va, const uint32_t *order, double *out) {
     match_residuals(a, va, order, out);
 }
+// the adaptive pass (include/pcr.h: "adaptive pass"): a key per scan point in device order, +inf where there is no
+// correspondence; behind the selection over the keys (select.hip), k_vgicp_robust's reduce with its kernel read from the
+// selection's state (AdaptiveSide), folded by k_vgicp_fold
+__global__ void __launch_bounds__(256) k_vgicp_keys(const LinArgs a, const VgicpArgs va, double *out) {
+    match_residuals<VgicpArgs, true>(a, va, nullptr, out);
+}
+__global__ void __launch_bounds__(256) k_vgicp_adaptive(const LinArgs a, const AdaptiveSide<VgicpArgs> va) {
+    match_reduce<VGICP_ROBUST_W>(a, adaptive_side(va));
+}
 
 // ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
 // The search is VPlaneICP's, over the centroids; a call has no parameter of the unit's own
@@ -170,7 +183,10 @@ struct VgicpUnit : MatchUnit {
     static constexpr auto robust = k_vgicp_robust;
     static constexpr auto fold = k_vgicp_fold;
     static constexpr auto residuals = k_vgicp_residuals;
-    static constexpr const char *reduce_range = "pcr:vgicp_reduce", *robust_range = "pcr:vgicp_robust", *residuals_range = "pcr:vgicp_residuals";
+    static constexpr auto keys = k_vgicp_keys;
+    static constexpr auto adaptive = k_vgicp_adaptive;
+    static constexpr const char *reduce_range = "pcr:vgicp_reduce", *robust_range = "pcr:vgicp_robust", *residuals_range = "pcr:vgicp_residuals",
+                                *adaptive_range = "pcr:vgicp_adaptive";
 };
 
 extern "C" pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
@@ -190,4 +206,13 @@ extern "C" pcr_status pcr_vgicp_align_robust(pcr_target *t, pcr_scan *s, const d
 }
 extern "C" pcr_status pcr_vgicp_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out) {
     return match_residuals_entry<VgicpUnit>(t, s, T, max_dist, flags, s_out);
+}
+extern "C" pcr_status pcr_vgicp_linearize_adaptive(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, const pcr_adaptive *ad,
+                                                 unsigned flags, double out[29], double stats[4]) {
+    return match_linearize_adaptive<VgicpUnit>(t, s, T, max_dist, ad, flags, out, stats);
+}
+extern "C" pcr_status pcr_vgicp_align_adaptive(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                             const pcr_adaptive *ad, unsigned flags, double T_out[16], int *iterations,
+                                             double *trace_or_null, double *stats_or_null) {
+    return match_align_adaptive<VgicpUnit>(t, s, T_init, max_iter, tol, max_dist, ad, flags, T_out, iterations, trace_or_null, stats_or_null);
 }

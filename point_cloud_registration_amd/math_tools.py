@@ -53,6 +53,25 @@ def robust_weight(kind, s, scale):
     raise ValueError('kind must be None, "huber", "cauchy", "tukey" or "gm"')
 
 
+def trim_threshold(s, ratio):
+    """The threshold of the adaptive pass over the squared residual(s) ``s``, the NumPy statement of ``include/pcr.h``:
+    with m the number of ``s < inf`` (``inf``, NaN: no correspondence), ``k = max(1, floor(ratio * m))`` -- the product once,
+    in float64 -- and ``tau`` the k-th smallest of them -> ``(tau, k)``; ``(inf, 0)`` for m = 0.
+
+    A trim keeps ``s <= tau`` -- ties at ``tau`` included, so at least k: ``weights = (s <= tau)`` goes straight into
+    ``weights=`` of the aligners without a pass of their own (``ICP``, ``PlaneICP``, ``VPlaneICP``, ``NDT``); a robust scale
+    from the same rule is ``factor * sqrt(tau)``.  ``ratio`` must be in (0, 1]."""
+    ratio = float(ratio)
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError("ratio must be in (0, 1]")
+    s = np.asarray(s, dtype=np.float64).ravel()
+    f = np.sort(s[s < np.inf])
+    if f.size == 0:
+        return np.inf, 0
+    k = max(1, int(np.floor(np.float64(ratio) * np.float64(f.size))))
+    return float(f[k - 1]), k
+
+
 def skew(vector):
     """3x3 cross-product matrix of one vector (reference ``math_tools.py:61-64``)."""
     x, y, z = vector[0], vector[1], vector[2]

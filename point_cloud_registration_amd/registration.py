@@ -372,21 +372,47 @@ class MatchPass(Registration):
     correspondence inside the gate by a robust kernel of its squared residual (``math_tools.robust_weight``; ``include/pcr.h``
     says what the squared residual of each class is), inside the pass: ``calc_H_g_e2`` and ``align`` then return the IRLS sums
     and pose.  ``None`` passes no kernel, which the library defines as the plain pass: the bits the class returned before
-    there were kernels.  ``residuals`` returns the squared residuals a scale can be chosen from."""
+    there were kernels.  ``residuals`` returns the squared residuals a scale can be chosen from.
+
+    The adaptive pass (``include/pcr.h``) takes the threshold or the scale from each pass's own squared residuals, on the device:
+    ``trim=ratio`` in (0, 1] keeps the ``max(1, floor(ratio m))`` best of the m correspondences of every pass, ties at the
+    threshold included (trimmed ICP; exclusive with ``robust``); ``robust_scale=("quantile", q, factor)`` runs the kernel with
+    c = factor sqrt(the q-quantile of the squared residuals), recomputed every pass (``math_tools.trim_threshold`` is the rule of
+    both).  After a call ``last_adaptive`` = ``{"tau", "scale", "kept", "k"}`` of its last pass, after ``align`` also
+    ``last_adaptive_trace``, (iterations, 4) in that order.  With neither, the calls are what they were."""
     KIND = None           # no kind of pcr_linearize
     _UNIT = None          # "gicp", "vgicp", "symm", "color"
 
-    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, **kw):
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, trim=None, **kw):
         if kw.get("devices") is not None or kw.get("comm") is not None:
             raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
         if not 1 <= int(k) <= 64:
             raise ValueError("k must be in [1, 64]")
-        kind, scale = _capi.check_robust(robust, robust_scale)
+        adaptive = None
+        if trim is not None:
+            if robust is not None:
+                raise ValueError("trim and robust exclude each other")
+            adaptive = _capi.check_adaptive("trim", trim)
+        if isinstance(robust_scale, (tuple, list)):
+            if robust is None or len(robust_scale) != 3 or robust_scale[0] != "quantile":
+                raise ValueError('robust_scale must be a float, or ("quantile", q, factor) beside a robust kernel')
+            try:
+                q, factor = float(robust_scale[1]), float(robust_scale[2])
+            except (TypeError, ValueError) as exc:
+                raise ValueError('robust_scale must be a float, or ("quantile", q, factor) beside a robust kernel') from exc
+            kind, scale = _capi.check_robust(robust, 1.0)[0], tuple(robust_scale)      # ("robust must be ..." first)
+            adaptive = _capi.check_adaptive(robust, q, factor)
+        else:
+            kind, scale = _capi.check_robust(robust, robust_scale)
         super().__init__(max_iter=max_iter, tol=tol, **kw)
         self.max_dist = max_dist
         self.k = int(k)
         self.robust, self.robust_scale = robust, scale
-        self._robust = None if robust is None else (kind, scale)
+        self.trim = None if trim is None else adaptive[1]
+        self._robust = None if robust is None or adaptive is not None else (kind, scale)
+        self._adaptive = adaptive                     # (kind, quantile, factor) of pcr_adaptive, or None
+        self.last_adaptive = None
+        self.last_adaptive_trace = None
 
     def _pass_params(self):
         return ()
@@ -419,11 +445,25 @@ class MatchPass(Registration):
     def _entry(self, what):
         return getattr(_capi, f"{self._UNIT}_{what}")
 
+    _STATS = ("tau", "scale", "kept", "k")
+
     def _native_linearize(self, scan, cur_T):
+        if self._adaptive is not None:
+            out, stats = self._entry("linearize_adaptive")(self._target, scan, cur_T, self._max_dist(), *self._pass_params(),
+                                                           adaptive=self._adaptive, flags=self._flags)
+            self.last_adaptive = dict(zip(self._STATS, stats.tolist()))
+            return out
         return self._entry("linearize_robust")(self._target, scan, cur_T, self._max_dist(), *self._pass_params(), robust=self._robust,
                                                flags=self._flags)
 
     def _native_align(self, scan, cur_T):
+        if self._adaptive is not None:
+            T, iters, stats, trace = self._entry("align_adaptive")(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(),
+                                                                   *self._pass_params(), adaptive=self._adaptive, flags=self._flags,
+                                                                   want_trace=True)
+            self.last_adaptive_trace = stats
+            self.last_adaptive = dict(zip(self._STATS, stats[-1].tolist())) if iters else None
+            return T, iters, trace
         return self._entry("align_robust")(self._target, scan, cur_T, self.max_iter, self.tol, self._max_dist(), *self._pass_params(),
                                            robust=self._robust, flags=self._flags, want_trace=True)
 
