@@ -936,9 +936,14 @@ PCR_API pcr_status pcr_target_filter_band(pcr_target *t, double *band);
  * PCR_XORDER=0, no heavy cells; zeros otherwise): out[0] = candidates tested, out[1..2] = those of them
  * whose bound (p.x - q.x)^2 + (slab distance of the row)^2 was within the best distance at the time of
  * the test / within the final best -- what a scan that knew the order of x inside a row could not have
- * skipped, summed over queries                                                                      */
+ * skipped, summed over queries.
+ * pcr_nn_counters_edge: the queries OUTSIDE the target's grid box on their own: out[0] = how many, out[1..2] = their
+ * candidates and row segments, out[3..4] = the wave maxima of candidates and of row segments charged to them, out[5..6] =
+ * waves of 64 queries that hold at least one / all waves, out[7..8] = queries inside the box whose own cell is empty and
+ * has no list (they start from the cell's seed) and their candidates                                 */
 PCR_API pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[11]);
 PCR_API pcr_status pcr_nn_counters_x(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[3]);
+PCR_API pcr_status pcr_nn_counters_edge(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[9]);
 /* select the hot-path variant: 2 (default) = chosen per launch by the size of the scan: 1 = NN kernel
  * writing correspondences to HBM followed by a reduce kernel (faster for large scans: twice the
  * occupancy), 0 = one fused transform+NN+reduce kernel (faster for small, latency-bound scans: 100 k

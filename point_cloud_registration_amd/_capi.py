@@ -127,6 +127,7 @@ PROTOTYPES = {
     "pcr_get_pipeline": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pcr_nn_counters": (C.c_int, [_vp, _vp, _f64p, C.c_double, _f64p]),
     "pcr_nn_counters_x": (C.c_int, [_vp, _vp, _f64p, C.c_double, _f64p]),
+    "pcr_nn_counters_edge": (C.c_int, [_vp, _vp, _f64p, C.c_double, _f64p]),
     "pcr_set_reuse": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "pcr_get_reuse": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pcr_scan_reuse_stats": (C.c_int, [_vp, _f64p]),
@@ -1714,6 +1715,25 @@ def nn_counters_x(target, scan, T, max_dist):
                                   float(max_dist), out))
     n = max(scan.n, 1)
     return {"candidates": out[0] / n, "x_now": out[1] / n, "x_final": out[2] / n}
+
+
+def nn_counters_edge(target, scan, T, max_dist):
+    """The queries outside the target's grid box against those inside it (see include/pcr.h: pcr_nn_counters_edge): their
+    share of the queries and of the 64-query tiles, candidates and row segments per query of either class, the share of
+    all candidates (per lane, and charged at each wave's maximum) that falls on the outside ones, and the candidates per
+    query of the in-grid queries that start from a cell seed."""
+    e = np.zeros(9)
+    a = np.zeros(11)
+    Tf = np.ascontiguousarray(T, np.float64).reshape(16)
+    check(lib().pcr_nn_counters_edge(target.handle, scan.handle, Tf, float(max_dist), e))
+    check(lib().pcr_nn_counters(target.handle, scan.handle, Tf, float(max_dist), a))
+    n = max(scan.n, 1)
+    n_out, n_in = max(e[0], 1), max(n - e[0], 1)
+    return {"out_share": e[0] / n, "out_tile_share": e[5] / max(e[6], 1),
+            "cand_out": e[1] / n_out, "cand_in": (a[3] - e[1]) / n_in, "rows_out": e[2] / n_out, "rows_in": (a[1] - e[2]) / n_in,
+            "wave_cand_out": e[3] / n_out, "wave_cand_in": (a[7] - e[3]) / n_in,
+            "cand_share_out": e[1] / max(a[3], 1), "wave_cand_share_out": e[3] / max(a[7], 1), "wave_rows_share_out": e[4] / max(a[5], 1),
+            "empty_in_share": e[7] / n, "cand_empty_in": e[8] / max(e[7], 1)}
 
 
 def unpack29(out):

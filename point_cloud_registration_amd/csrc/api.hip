@@ -285,6 +285,10 @@ extern "C" pcr_status pcr_nn_counters_x(pcr_target *, pcr_scan *, const double *
     pcr_set_error("pcr_nn_counters_x needs the developer build of the library (make DEV=1: libpcr_hip_dev.so)");
     return PCR_ERR_INVALID;
 }
+extern "C" pcr_status pcr_nn_counters_edge(pcr_target *, pcr_scan *, const double *, double, double *) {
+    pcr_set_error("pcr_nn_counters_edge needs the developer build of the library (make DEV=1: libpcr_hip_dev.so)");
+    return PCR_ERR_INVALID;
+}
 extern "C" pcr_status pcr_nn_counters(pcr_target *, pcr_scan *, const double *, double, double *) {
     pcr_set_error("pcr_nn_counters needs the developer build of the library (make DEV=1: libpcr_hip_dev.so)");
     return PCR_ERR_INVALID;

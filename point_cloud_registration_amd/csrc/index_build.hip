@@ -503,6 +503,12 @@ static pcr_status pack_gap_field(pcr_context *ctx, uint32_t *cs, int nx, int ny,
     return PCR_OK;
 }
 
+// PCR_EDGE_SEED=0 (developer A/B switch, read once): queries outside the grid box start at the gate (GeomSwitches::edge_seed)
+static uint32_t edge_seed_rule() {
+    static const uint32_t on = [] { const char *e = getenv("PCR_EDGE_SEED"); return e && *e && atoi(e) == 0 ? 0u : 1u; }();
+    return on;
+}
+
 template <typename Real>
 static bool make_geom(const float lo[3], const float hi[3], double h, Geom<Real> *g, double *ncells) {
     g->ox = (Real)lo[0]; g->oy = (Real)lo[1]; g->oz = (Real)lo[2];
@@ -522,6 +528,7 @@ static bool make_geom(const float lo[3], const float hi[3], double h, Geom<Real>
     g->seed = nullptr;
     g->halo = (Real)0; g->cs_h = nullptr; g->pts_h = nullptr; g->j_h = nullptr; g->rowocc = nullptr; g->nyw = 0; g->nxb = 0; g->lbox = nullptr; g->gbox = nullptr; g->lbox_h = nullptr; g->gbox_h = nullptr;
     g->xq = (Real)0;
+    if constexpr (sizeof(Real) == 4) g->sw.edge_seed = edge_seed_rule();
     return true;
 }
 

@@ -195,13 +195,18 @@ __global__ void __launch_bounds__(256) k_nn_coop(const LinArgs a) {
 // work counters of the search (instrumentation; same traversal as k_nn_scan<0>): out[0..3] = per-lane
 // sums of rings, rows loaded, rows pruned by arithmetic, candidates tested; out[4..7] = the same with
 // the per-WAVE maximum charged to all 64 lanes (what the SIMD actually executes under divergence); out[11..12] = of the
-// candidates tested, those an x-ordered scan could not skip against `best` at the time / against the final best (NNStats)
+// candidates tested, those an x-ordered scan could not skip against `best` at the time / against the final best (NNStats);
+// out[13..21] = the queries OUTSIDE the grid box (NNCell::k0 != 0) on their own: how many, their candidates, their row segments,
+// the wave maxima of candidates and of row segments charged to them, the tiles (waves of 64 queries) that hold at least one /
+// all tiles; and the queries inside the box whose ring 0 scanned nothing (an empty cell without a list: the cell seed's
+// clientele, what a seeded outside query should come down to): how many, their candidates
 template <int HALO, int LB = PCR_RANGE_PLAIN>
 __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned long long *out) {
     const TileIter it(a);
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long cyc[3] = {0, 0, 0};                  // wave wall-clock: prologue, ring 0, outer rings
     unsigned long long xs[2] = {0, 0};
+    unsigned long long ex[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int64_t i0 = it.base - threadIdx.x; i0 < it.end; i0 += it.stride) {
         const int64_t i = i0 + threadIdx.x;
         NNStats st = {0, 0, 0, 0, 0, 0, 0.f};
@@ -226,6 +231,7 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
         if (live) kstart = nn_ring0<float, PtF, true, HALO != 0, 0, PCR_NN_BATCH, LB>(a.gf, a.pts, a.cell_start, c, tx, ty, tz, best, bj, bo, &st);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long t2 = __builtin_readcyclecounter();
+        const bool outside = live && c.k0 != 0, empty_in = live && c.k0 == 0 && st.rows_loaded == 0;
         if (live) nn_rings<float, PtF, true, 0, PCR_NN_BATCH, LB>(a.gf, a.pts, a.cell_start, c, kstart, tx, ty, tz, best, bj, bo, &st);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long t3 = __builtin_readcyclecounter();
@@ -238,10 +244,17 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
             for (int off = 32; off >= 1; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
             acc[c4] += v[c4];
             acc[4 + c4] += m;
+            if (c4 == 3) ex[3] += outside ? m : 0u;
+            if (c4 == 1) ex[4] += outside ? m : 0u;
         }
+        ex[0] += outside ? 1u : 0u; ex[1] += outside ? st.cand : 0u; ex[2] += outside ? st.rows_loaded : 0u;
+        ex[7] += empty_in ? 1u : 0u; ex[8] += empty_in ? st.cand : 0u;
+        const unsigned long long any_out = __ballot(outside), any_live = __ballot(live);
+        if ((threadIdx.x & 63) == 0) { ex[5] += any_out != 0ull ? 1u : 0u; ex[6] += any_live != 0ull ? 1u : 0u; }
     }
     for (int c = 0; c < 8; ++c) atomicAdd(&out[c], acc[c]);
     atomicAdd(&out[11], xs[0]); atomicAdd(&out[12], xs[1]);
+    for (int c = 0; c < 9; ++c) atomicAdd(&out[13 + c], ex[c]);
     if ((threadIdx.x & 63) == 0) for (int c = 0; c < 3; ++c) atomicAdd(&out[8 + c], cyc[c]);
 }
 
@@ -343,7 +356,7 @@ int pcr_dev_coop_blocks_per_cu() {
 }
 
 // ---- instrumentation: search work counters for one pose (point targets) ------------------------
-static pcr_status nn_counters_run(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[13]) {
+static pcr_status nn_counters_run(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[22]) {
     PCR_REQUIRE(t && s && T && out, "NULL argument");
     PCR_REQUIRE(!t->is_voxel, "counters are implemented for point targets");
     pcr_context *ctx = t->ctx;
@@ -360,10 +373,10 @@ static pcr_status nn_counters_run(pcr_target *t, pcr_scan *s, const double T[16]
     const double bound = max_dist * (1.0 + 1e-6);
     a.bound2_f = (float)(bound * bound);
     a.nblocks = choose_blocks(ctx, s->n);
-    unsigned long long h[13];
+    unsigned long long h[22];
     CtxScope scope(ctx);
     DevBuf<unsigned long long> d;
-    HIP_TRY(d.alloc(13));
+    HIP_TRY(d.alloc(22));
     HIP_TRY(hipMemsetAsync(d.p, 0, sizeof h, ctx->stream));
     if (t->gf.lbox && t->cs_h) hipLaunchKernelGGL((k_nn_counters<1, PCR_RANGE_BOXES>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
     else if (t->gf.lbox) hipLaunchKernelGGL((k_nn_counters<0, PCR_RANGE_BOXES>), dim3(a.nblocks), dim3(256), 0, ctx->stream, a, d.p);
@@ -374,20 +387,27 @@ static pcr_status nn_counters_run(pcr_target *t, pcr_scan *s, const double T[16]
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h, d.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 13; ++i) out[i] = (double)h[i];
+    for (int i = 0; i < 22; ++i) out[i] = (double)h[i];
     return PCR_OK;
 }
 extern "C" pcr_status pcr_nn_counters(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[11]) {
-    double all[13];
+    double all[22];
     PCR_TRY(nn_counters_run(t, s, T, max_dist, all));
     for (int i = 0; i < 11; ++i) out[i] = all[i];
     return PCR_OK;
 }
 extern "C" pcr_status pcr_nn_counters_x(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[3]) {
     PCR_REQUIRE(out, "NULL argument");
-    double all[13];
+    double all[22];
     PCR_TRY(nn_counters_run(t, s, T, max_dist, all));
     out[0] = all[3]; out[1] = all[11]; out[2] = all[12];
+    return PCR_OK;
+}
+extern "C" pcr_status pcr_nn_counters_edge(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double out[9]) {
+    PCR_REQUIRE(out, "NULL argument");
+    double all[22];
+    PCR_TRY(nn_counters_run(t, s, T, max_dist, all));
+    for (int i = 0; i < 9; ++i) out[i] = all[13 + i];
     return PCR_OK;
 }
 

@@ -439,49 +439,70 @@ __device__ __forceinline__ int nn_ring0(const Geom<Real> &g, const PT *__restric
                                         NNCell<Real> &c, Real qx, Real qy, Real qz,
                                         Real &best, uint32_t &bj, uint32_t &borig, NNStats *st = nullptr,
                                         NNTrack<Real> *tk = nullptr) {
-    if (c.k0 != 0) return c.k0;                   // outside the grid box: rings below k0 hold no cells
-    const uint32_t own = ((uint32_t)c.cz * (uint32_t)g.ny + (uint32_t)c.cy) * (uint32_t)g.nx + (uint32_t)c.cx;
-    constexpr bool ext = HALO;                   // (HALO launches only happen for targets that have the lists)
-    const uint32_t *__restrict__ csr = ext ? g.cs_h : cs;
-    const uint32_t w0 = csr[own], w1 = csr[own + 1];
-    const int gap = g.cs_mask != 0xffffffffu ? (int)(w0 >> PCR_GAP_SHIFT) : 0;
-    if (ext) {
-        // the extended list holds COPIES: track the position in it, then translate the winner to its
-        // cell-sorted index (j_h is laid out like the lists, so neighbouring queries share its lines).
-        // An EMPTY cell may have a list too (its neighbours' points within the halo): a far-pose query that
-        // landed one cell off the surface is served like one inside an occupied cell.
-        const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
-        if (e_ > s_) {
+    // A query outside the grid box (k0 != 0): rings below k0 hold no cells.  The plain float32 point search seeds it from the
+    // box cell nearest to it (its own cell clamped onto the box): that cell's entry of the seed table, which is the first
+    // record of an occupied cell (k_gap_pack: the nearest occupied cell of an occupied cell is itself) and a point of the
+    // nearest occupied cell otherwise.  A query whose scan pose is off at the map's border used to enter the ring loop with
+    // `best` at the gate and meet the farthest rows of its first shell first, at 2.1 times the candidates of a query inside
+    // the box.  Exactness: the seed is a real target point, measured by the candidates' own formula and kept only if it beats
+    // `best` under the (distance, original index) key; the rings still visit every row that can hold a record at or below
+    // `best`.  Such a lane skips the own-cell scan below and joins the lanes in empty cells at the seed, so that a wave with
+    // both kinds pays the seed's two round trips once.  A query beyond the gate from the box (k0 > kmax) leaves before any
+    // load, as it always did; so does every outside query of the other searches and of a target without the seed table.
+    constexpr bool EDGE = TRACK == 0 && sizeof(Real) == 4;
+    const bool outside = c.k0 != 0;
+    if constexpr (EDGE) {
+        if (outside && !(g.sw.edge_seed != 0u && g.seed != nullptr && c.k0 <= c.kmax)) return c.k0;
+    } else {
+        if (outside) return c.k0;
+    }
+    const int ccx = EDGE ? min(max(c.cx, 0), g.nx - 1) : c.cx, ccy = EDGE ? min(max(c.cy, 0), g.ny - 1) : c.cy, ccz = EDGE ? min(max(c.cz, 0), g.nz - 1) : c.cz;
+    const uint32_t own = ((uint32_t)ccz * (uint32_t)g.ny + (uint32_t)ccy) * (uint32_t)g.nx + (uint32_t)ccx;
+    int gap = c.k0;
+    if (!(EDGE && outside)) {
+        constexpr bool ext = HALO;                   // (HALO launches only happen for targets that have the lists)
+        const uint32_t *__restrict__ csr = ext ? g.cs_h : cs;
+        const uint32_t w0 = csr[own], w1 = csr[own + 1];
+        gap = g.cs_mask != 0xffffffffu ? (int)(w0 >> PCR_GAP_SHIFT) : 0;
+        if (ext) {
+            // the extended list holds COPIES: track the position in it, then translate the winner to its
+            // cell-sorted index (j_h is laid out like the lists, so neighbouring queries share its lines).
+            // An EMPTY cell may have a list too (its neighbours' points within the halo): a far-pose query that
+            // landed one cell off the surface is served like one inside an occupied cell.
+            const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
+            if (e_ > s_) {
+                if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
+                uint32_t ej = PCR_NONE;
+                if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>((const PtF *)g.pts_h, g.lbox_h, g.gbox_h, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, ej, borig, st);
+                // (x order: the list's points lie within the halo of the cell: the query's place in [-halo, h + halo])
+                else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>((const PtF *)g.pts_h, s_, e_, (c.fx + g.halo) * __frcp_rn(g.h + 2.f * g.halo), 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, ej, borig, st);
+                else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>((const PtF *)g.pts_h, s_, e_, qx, qy, qz, 0.f, best, ej, borig, st);
+                else nn_scan_range<Real, PT, TRACK, B>((const PT *)g.pts_h, s_, e_, qx, qy, qz, best, ej, borig, tk);
+                if (ej != PCR_NONE) bj = g.j_h[ej];
+                c.reach0 = g.halo;
+                // a whole-cell halo: the list held every point of rings 0 and 1; rings closer than the gap are empty anyway
+                const int base = g.halo >= g.h ? 2 : 1;
+                return gap > base ? gap : base;
+            }
+        } else if (gap == 0) {
+            const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
             if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-            uint32_t ej = PCR_NONE;
-            if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>((const PtF *)g.pts_h, g.lbox_h, g.gbox_h, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, ej, borig, st);
-            // (x order: the list's points lie within the halo of the cell: the query's place in [-halo, h + halo])
-            else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>((const PtF *)g.pts_h, s_, e_, (c.fx + g.halo) * __frcp_rn(g.h + 2.f * g.halo), 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, ej, borig, st);
-            else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>((const PtF *)g.pts_h, s_, e_, qx, qy, qz, 0.f, best, ej, borig, st);
-            else nn_scan_range<Real, PT, TRACK, B>((const PT *)g.pts_h, s_, e_, qx, qy, qz, best, ej, borig, tk);
-            if (ej != PCR_NONE) bj = g.j_h[ej];
-            c.reach0 = g.halo;
-            // a whole-cell halo: the list held every point of rings 0 and 1; rings closer than the gap are empty anyway
-            const int base = g.halo >= g.h ? 2 : 1;
-            return gap > base ? gap : base;
+            if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st);
+            else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, c.fx * g.inv_h, 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, bj, borig, st);
+            else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, 0.f, best, bj, borig, st);
+            else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
+            return 1;
         }
-    } else if (gap == 0) {
-        const uint32_t s_ = w0 & g.cs_mask, e_ = w1 & g.cs_mask;
-        if (STATS) { st->rings++; st->rows_loaded++; st->cand += LB != PCR_RANGE_PLAIN ? 0u : ((e_ - s_ + PCR_NN_BATCH - 1) / PCR_NN_BATCH) * PCR_NN_BATCH; }
-        if constexpr (LB == PCR_RANGE_BOXES) nn_scan_range_lb<B, STATS>(pts, g.lbox, g.gbox, g.h * 0.00390625f, s_, e_, qx, qy, qz, best, bj, borig, st);
-        else if constexpr (LB == PCR_RANGE_XORDER) nn_scan_range_x<B, STATS>(pts, s_, e_, c.fx * g.inv_h, 2.f * (g.xq + g.slack), 0.f, qx, qy, qz, best, bj, borig, st);
-        else if constexpr (STATS && LB == PCR_RANGE_PLAIN && TRACK == 0 && sizeof(Real) == 4) nn_scan_range_xstat<B>(pts, s_, e_, qx, qy, qz, 0.f, best, bj, borig, st);
-        else nn_scan_range<Real, PT, TRACK, B>(pts, s_, e_, qx, qy, qz, best, bj, borig, tk);
-        return 1;
     }
     if (g.seed) {                                 // a real point nearby bounds the search from the start
         const uint32_t j0 = g.seed[own];
         if (j0 != PCR_NONE) {
+            if (STATS && EDGE && outside) st->cand += 1;
             nn_test<Real, PT, TRACK>(pts[j0], j0, qx, qy, qz, best, bj, borig, tk);
             if (TRACK) nn_track_refresh<Real, TRACK>(*tk, best);
         }
     }
-    return gap;                                   // rings closer than `gap` are empty
+    return gap;                                   // rings closer than `gap` are empty (outside the box: than k0)
 }
 
 #ifndef PCR_OCC_MIN_RING

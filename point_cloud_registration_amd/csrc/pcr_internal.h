@@ -36,6 +36,16 @@ void pcr_set_error(const char *fmt, ...);
         }                                           \
     } while (0)
 
+// Developer switches of the plain float32 point search.  They ride in the tail padding of Geom<float> (behind xq: the size
+// of the structure, and with it the argument layout of every kernel that takes one, stays what it was); Geom<double> has
+// no such padding and carries none.
+template <typename Real> struct GeomSwitches {};
+template <> struct GeomSwitches<float> {
+    // 1 (default): a query OUTSIDE the grid box starts from a real point of the box cell nearest to it (nn_device.h:
+    // nn_ring0); 0 (PCR_EDGE_SEED=0, read once when the first grid is laid out): it starts at the gate, as it used to
+    uint32_t edge_seed;
+};
+
 // Dense cell grid geometry.  Real = float for point targets, double for voxel centroids.
 template <typename Real>
 struct Geom {
@@ -74,7 +84,9 @@ struct Geom {
     // for positions i < j of a row range or of a list, x[i] <= x[j] + xq + slack.  nn_scan_range_x scans such a range from the
     // query's x outward and stops on either side at the first record beyond the remaining budget.
     Real xq;
+    [[no_unique_address]] GeomSwitches<Real> sw;
 };
+static_assert(sizeof(Geom<float>) == 136 && sizeof(Geom<double>) == 160, "Geom is a kernel argument: its layout is pinned");
 #define PCR_LB_MIN 24            // ranges up to this many records are scanned plainly
 #ifndef PCR_HALO2_FRAC
 #define PCR_HALO2_FRAC 0.25      // margin of the deeper list set, x cell

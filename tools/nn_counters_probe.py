@@ -1,7 +1,8 @@
 """Developer probe (developer build: PCR_LIB=.../libpcr_hip_dev.so): work counters of the point search per query at every pose of
 a bench config's Gauss-Newton trajectory -- row segments, candidates tested, and, on a target in the old order (PCR_XORDER=0),
 how many of those candidates a scan that knew the order of x inside a row could NOT have skipped: against the best distance at
-the time of the test (x_now) and against the final best (x_final).   python tools/nn_counters_probe.py [config ...]"""
+the time of the test (x_now) and against the final best (x_final); and the queries outside the target's grid box against those
+inside it (nn_counters_edge; PCR_EDGE_SEED=0 in the environment: without their seed).   python tools/nn_counters_probe.py [config ...]"""
 import os, sys, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as B
@@ -18,3 +19,4 @@ for cfg in sys.argv[1:] or ["plane_b01"]:
         c = _capi.nn_counters(tgt, sc, tr[k, :16].reshape(4, 4), 2.0)
         print(cfg, "pose", k, {a: round(b, 2) for a, b in c.items()},
               {a: round(b, 2) for a, b in _capi.nn_counters_x(tgt, sc, tr[k, :16].reshape(4, 4), 2.0).items()}, flush=True)
+        print(cfg, "pose", k, "edge", {a: round(b, 3) for a, b in _capi.nn_counters_edge(tgt, sc, tr[k, :16].reshape(4, 4), 2.0).items()}, flush=True)
