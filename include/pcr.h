@@ -884,6 +884,44 @@ PCR_API int pcr_fgr_blocks(int64_t m);
  * it serves on this device, 0 in a library without it                                                                   */
 PCR_API pcr_status pcr_fgr_solo_max(pcr_context *ctx, int64_t *m_max);
 
+/* ---- consensus sets from the compatibility graph of the matches: SC2 (no reference counterpart) ---------------
+ * Where 1-3 % of the matches are right, a triple of matches is clean once in 10^6 (RANSAC) and the right ones do not dominate
+ * the first Gauss-Newton steps (FGR).  The length of a pair of matches is invariant under a rigid motion, so the right ones
+ * can be told apart before any pose exists: the compatibility graph of TEASER and of SC2-PCR (Chen et al., CVPR 2022), and
+ * its second-order measure, the number of compatible neighbours that two compatible matches share.  Everything below is an
+ * integer: two calls, any grid and a restatement agree bit for bit.
+ * src, dst: m x 3 float32 host arrays; row i is one match p_i -> q_i.  Non-finite values are allowed (see below).
+ * 1. Compatibility, float64 over the widened float32 points, no fma, every dot product (x*x + y*y) + z*z:
+ *      a2 = |p_i - p_j|^2, b2 = |q_i - q_j|^2;  C_ij = 1 iff i != j and fabs(sqrt(a2) - sqrt(b2)) <= d
+ *    (the float64 sqrt is correctly rounded).  Negating a difference is exact, so C is symmetric by construction; a NaN
+ *    anywhere makes the comparison false: a match with a non-finite coordinate is compatible with nothing.  C is a bit matrix
+ *    of m rows of W = ceil(m / 64) 64-bit words: bit (j & 63) of word (j >> 6) of row i is C_ij; the diagonal and the padding
+ *    bits of the last word are 0.
+ * 2. Degrees: deg1_i = popcount(row_i);  deg2_i = the sum over j with C_ij = 1 of popcount(row_i & row_j) -- the row sum of
+ *    C o (C C), twice the number of triangles of the graph through i.
+ * 3. Seeds: the n_seeds rows with the largest deg2, ties to the smaller row, in that order; n_seeds is clipped to m
+ *    (*n_seeds_out = min(n_seeds, m), so many rows of seeds / members / scores are written).
+ * 4. The consensus set of seed s, k slots: s itself comes first, its score = popcount(row_s) = deg1_s; then up to k - 1 rows j
+ *    with C_sj = 1 by score_sj = popcount(row_s & row_j) descending, ties to the smaller j -- the maximum of the 64-bit key
+ *    (score << 32) | (0xffffffff - j), k - 1 times; rows with score 0 are included, last.  Slots beyond the set: member -1,
+ *    score -1.
+ * The pose from these sets (a least-squares fit per seed, scored with pcr_pose_score, the winner refined) is the host's:
+ *   global_registration.py: sc2_pose.  The two-stage selection and the spectral weights of the paper are left out.
+ * pcr_compat_consensus builds the bits once, computes the degrees, picks the seeds on the host and runs the consensus kernel.
+ * PCR_ERR_INVALID: m < 0 or m > PCR_COMPAT_M_MAX; d not finite or not > 0; k < 2 or k > PCR_COMPAT_K_MAX; n_seeds < 1 -- the
+ *   outputs are then left untouched and the context stays usable.  m == 0 returns PCR_OK without a launch and writes nothing
+ *   but *n_seeds_out = 0.  PCR_COMPAT_TIMES=1 in the environment (read once per process) reports the kernels' milliseconds on
+ *   stderr.  One GPU of one process.                                                                                      */
+#define PCR_COMPAT_M_MAX 32768        /* bit matrix <= 128 MiB */
+#define PCR_COMPAT_K_MAX 64
+PCR_API pcr_status pcr_compat_bits(pcr_context *ctx, const float *src, const float *dst, int64_t m, double d,
+                                   uint64_t *bits /* m x ceil(m / 64) */);
+PCR_API pcr_status pcr_compat_degrees(pcr_context *ctx, const float *src, const float *dst, int64_t m, double d, int64_t *deg1 /* m */,
+                                      int64_t *deg2 /* m */);
+PCR_API pcr_status pcr_compat_consensus(pcr_context *ctx, const float *src, const float *dst, int64_t m, double d, int n_seeds, int k,
+                                        int64_t *deg1_or_null /* m */, int64_t *deg2_or_null /* m */, int32_t *seeds /* n_seeds */,
+                                        int32_t *members /* n_seeds x k */, int32_t *scores /* n_seeds x k */, int *n_seeds_out);
+
 /* ---- instrumentation ------------------------------------------------------------------
  * With profiling on, every launch of a hot-path kernel is bracketed by HIP events on the
  * context's stream; pcr_profile_read drains them (synchronises) and reports per-kernel

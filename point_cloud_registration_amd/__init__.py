@@ -24,7 +24,8 @@ from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
 from .features import compute_fpfh, compute_fpfh_rows, match_features, select_matches
 from .keypoints import iss_keypoints
-from .global_registration import score_poses, fit_rigid, ransac_pose, fgr_pose, register_global
+from .global_registration import (score_poses, fit_rigid, ransac_pose, fgr_pose, register_global, match_compatibility,
+                                  sc2_pose)
 
 __all__ = [
     "Registration", "ICP", "PlaneICP", "VPlaneICP", "NDT", "GICP", "VGICP", "SymmetricICP", "ColoredICP", "KDTree", "VoxelGrid", "voxel_filter",
@@ -33,5 +34,5 @@ __all__ = [
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
     "score_poses", "fit_rigid", "ransac_pose", "fgr_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
-    "robust_weight", "trim_threshold",
+    "robust_weight", "trim_threshold", "match_compatibility", "sc2_pose",
 ]

@@ -112,6 +112,11 @@ PROTOTYPES = {
                                  C.POINTER(C.c_int64)]),
     "pcr_fgr_blocks": (C.c_int, [C.c_int64]),
     "pcr_fgr_solo_max": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    # the compatibility graph of a match list, its degrees and the consensus sets around its seeds (include/pcr.h)
+    "pcr_compat_bits": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_double, _vp]),
+    "pcr_compat_degrees": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_double, _vp, _vp]),
+    "pcr_compat_consensus": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                       C.POINTER(C.c_int)]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_reset": (C.c_int, [_vp]),
     "pcr_profile_read": (C.c_int, [_vp, _i64p, _f64p]),
@@ -1321,6 +1326,71 @@ def fgr_solo_max(ctx):
     n = C.c_int64(0)
     check(lib().pcr_fgr_solo_max(ctx.handle, C.byref(n)))
     return n.value
+
+
+COMPAT_M_MAX, COMPAT_K_MAX = 32768, 64          # PCR_COMPAT_M_MAX, PCR_COMPAT_K_MAX of include/pcr.h
+
+
+def check_compat(src, dst, d):
+    """The matches of the pcr_compat_* calls as C-contiguous float32 (M, 3) arrays -- non-finite values are allowed: such a
+    match is compatible with nothing -- and the threshold as a float: M <= PCR_COMPAT_M_MAX, d finite and > 0, else ValueError
+    (checked before the GPU is touched)."""
+    src, dst = np.asarray(src), np.asarray(dst)
+    if src.ndim != 2 or src.shape[1] != 3 or src.shape != dst.shape:
+        raise ValueError("src and dst must have one shape (M, 3)")
+    if len(src) > COMPAT_M_MAX:
+        raise ValueError(f"more than {COMPAT_M_MAX} matches (PCR_COMPAT_M_MAX)")
+    d = float(d)
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError("the compatibility threshold must be finite and > 0")
+    return cloud_f32(src, "src and dst", finite=False), cloud_f32(dst, "src and dst", finite=False), d
+
+
+def compat_bits(ctx, src, dst, d):
+    """pcr_compat_bits -> the compatibility matrix (M, ceil(M / 64)) uint64.  ``ctx`` may be a callable, as for ``pose_score``."""
+    src, dst, d = check_compat(src, dst, d)
+    m = len(src)
+    bits = np.zeros((m, (m + 63) // 64), np.uint64)
+    if m:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_compat_bits(ctx.handle, src, dst, m, d, _ptr(bits)))
+    return bits
+
+
+def compat_degrees(ctx, src, dst, d):
+    """pcr_compat_degrees -> (deg1 (M,) int64, deg2 (M,) int64)."""
+    src, dst, d = check_compat(src, dst, d)
+    m = len(src)
+    deg1, deg2 = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    if m:
+        if callable(ctx):
+            ctx = ctx()
+        check(lib().pcr_compat_degrees(ctx.handle, src, dst, m, d, _ptr(deg1), _ptr(deg2)))
+    return deg1, deg2
+
+
+def compat_consensus(ctx, src, dst, d, n_seeds, k):
+    """pcr_compat_consensus -> dict(deg1 (M,) int64, deg2 (M,) int64, seeds (S,) int32, members (S, k) int32, scores (S, k)
+    int32), S = min(n_seeds, M)."""
+    src, dst, d = check_compat(src, dst, d)
+    if int(n_seeds) != n_seeds or not 1 <= int(n_seeds) < 1 << 31:
+        raise ValueError("n_seeds must be an integer >= 1")
+    if int(k) != k or not 2 <= int(k) <= COMPAT_K_MAX:
+        raise ValueError(f"k must be an integer in [2, {COMPAT_K_MAX}]")
+    n_seeds, k, m = int(n_seeds), int(k), len(src)
+    s = min(n_seeds, m)
+    out = {"deg1": np.zeros(m, np.int64), "deg2": np.zeros(m, np.int64), "seeds": np.full(s, -1, np.int32),
+           "members": np.full((s, k), -1, np.int32), "scores": np.full((s, k), -1, np.int32)}
+    if m:
+        if callable(ctx):
+            ctx = ctx()
+        n_out = C.c_int(0)
+        check(lib().pcr_compat_consensus(ctx.handle, src, dst, m, d, s, k, _ptr(out["deg1"]), _ptr(out["deg2"]), _ptr(out["seeds"]),
+                                         _ptr(out["members"]), _ptr(out["scores"]), C.byref(n_out)))
+        if n_out.value != s:
+            raise PcrError(f"pcr_compat_consensus wrote {n_out.value} seeds, {s} expected")
+    return out
 
 
 def gn_set(ctx, J, r):

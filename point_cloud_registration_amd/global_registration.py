@@ -4,9 +4,10 @@
 
 ``ransac_pose`` draws pose hypotheses from triples of matches, scores every one of them against every match on the GPU and
 refines the winner over its inliers; ``fgr_pose`` (fast global registration, ``csrc/fgr.hip``) runs a graduated robust
-Gauss-Newton loop over the matches instead; ``register_global`` chains ``compute_fpfh``, ``match_features`` and ``ransac_pose`` --
-over every point, or over keypoints (``keypoints.py``) with descriptors at those rows only.  The
-result is an ``init_T`` for ``align`` of any of the local aligners.  Everything is computed over the **float32 copy** of the
+Gauss-Newton loop over the matches instead; ``sc2_pose`` (``csrc/compat.hip``) fits consensus sets of the matches'
+compatibility graph, for match lists of which a few per cent are right; ``register_global`` chains ``compute_fpfh``,
+``match_features`` and ``ransac_pose`` -- over every point, or over keypoints (``keypoints.py``) with descriptors at those rows
+only.  The result is an ``init_T`` for ``align`` of any of the local aligners.  Everything is computed over the **float32 copy** of the
 points, and the same call twice returns the same bits.
 """
 
@@ -231,6 +232,96 @@ def fgr_pose(source, target, ia, ib, max_dist, iterations=64, division_factor=1.
                "n_valid": int(n_valid)}
 
 
+def _compat_pairs(source, target, ia, ib, who):
+    """``_pairs`` for the compatibility calls: their own limit on the number of matches, said before anything is copied."""
+    if np.ndim(ia) == 1 and len(ia) > _capi.COMPAT_M_MAX:
+        raise ValueError(f"{who}: {len(ia)} matches, the compatibility matrix takes at most {_capi.COMPAT_M_MAX} (PCR_COMPAT_M_MAX); "
+                         'match fewer rows: keypoints="iss", mutual=True or ratio= of register_global / match_features')
+    return _pairs(source, target, ia, ib)
+
+
+def match_compatibility(source, target, ia, ib, max_dist, return_bits=False, device=None):
+    """The compatibility graph of the correspondences ``source[ia] -> target[ib]`` (``include/pcr.h``: ``pcr_compat_bits``,
+    kernels in ``csrc/compat.hip``): matches i and j are compatible when the lengths ``|p_i - p_j|`` and ``|q_i - q_j|``
+    differ by at most ``max_dist`` -- a rigid motion keeps lengths, so right matches are compatible with each other whatever
+    the pose.  ``deg1[i]`` counts the matches compatible with i, ``deg2[i]`` sums, over those, the compatible matches the two
+    have in common (the second-order measure of SC2-PCR).  Integers throughout: the same call twice returns the same bits.
+
+    -> ``(deg1, deg2)`` (M,) int64; with ``return_bits`` also the matrix as (M, ceil(M / 64)) uint64, bit ``j & 63`` of word
+    ``j >> 6`` of row i.  At most ``PCR_COMPAT_M_MAX`` = 32768 matches."""
+    src, dst = _compat_pairs(source, target, ia, ib, "match_compatibility")
+    src, dst, d = _capi.check_compat(src, dst, max_dist)
+    box = []
+
+    def ctx():
+        if not box:
+            box.append(_capi.get_context(device))
+        return box[0]
+    deg1, deg2 = _capi.compat_degrees(ctx, src, dst, d)
+    if not return_bits:
+        return deg1, deg2
+    return deg1, deg2, _capi.compat_bits(ctx, src, dst, d)
+
+
+def sc2_pose(source, target, ia, ib, max_dist, compat_dist=None, n_seeds=64, k=20, refine_rounds=5, return_info=False, device=None):
+    """A pose from the correspondences ``source[ia] -> target[ib]`` by consensus sets of their compatibility graph (SC2-PCR,
+    Chen et al. 2022), for match lists of which a few per cent are right: there ``ransac_pose`` draws no clean triple (at 1 %
+    one in 10^6) and ``fgr_pose`` is not dominated by the right matches.
+
+    The graph is ``match_compatibility`` at ``compat_dist`` (``None``: ``max_dist``).  The ``n_seeds`` matches with the largest
+    second-order degree are the seeds; a seed's consensus set is itself and the up to ``k - 1`` matches compatible with it
+    that share the most compatible neighbours with it (``include/pcr.h``: ``pcr_compat_consensus``; all of that on the GPU, in
+    integers).  Every seed with at least 3 members gets ``fit_rigid`` over its members; the poses, rounded to float32, are
+    scored against all matches at ``max_dist`` in one call, and the winner -- most inliers, then the earlier seed -- ends as
+    ``ransac_pose`` does: refined up to ``refine_rounds`` times over its inliers and returned with its rotation made
+    orthonormal.  This is the one-stage, unweighted form: the paper's second selection stage and its spectral (leading
+    eigenvector) weights are left out -- once the winner is refined over all its inliers they add nothing on the cases
+    measured (``docs/EXPERIMENTS.md``).  Deterministic: the same call twice returns the same bits.
+
+    -> ``T`` (4, 4) float64; fewer than 3 matches or no seed with 3 members: ``ransac_pose``'s no-match result, the identity
+    and count 0.  With ``return_info`` also a dict with ``pose``, ``inliers``, ``count``, ``fitness``, ``rmse`` as for
+    ``ransac_pose`` -- and its ``hypothesis`` (the winning seed's position in ``seeds``, -1: none) and ``n_valid`` (the seeds
+    that were fitted) -- plus ``deg1``, ``deg2`` (M,) int64, ``seeds`` (S,), ``members`` and ``scores`` (S, k) int32 (-1:
+    empty slot), ``seed`` (the winning seed's row, -1: none) and ``counts`` (S,) int32 (-1: fewer than 3 members).
+    More than ``PCR_COMPAT_M_MAX`` = 32768 matches: ValueError."""
+    src, dst = _compat_pairs(source, target, ia, ib, "sc2_pose")
+    m = len(src)
+    refine_rounds = int(refine_rounds)
+    if refine_rounds < 0:
+        raise ValueError("refine_rounds must be >= 0")
+    max_dist = _capi.check_distance(max_dist, "max_dist")
+    src, dst, d = _capi.check_compat(src, dst, max_dist if compat_dist is None else compat_dist)
+    box = []
+
+    def ctx():
+        if not box:
+            box.append(_capi.get_context(device))
+        return box[0]
+    res = _capi.compat_consensus(ctx, src, dst, d, n_seeds, k)
+    members = res["members"]
+    sizes = (members >= 0).sum(axis=1)
+    counts = np.full(len(members), -1, np.int32)
+    fitted = np.flatnonzero(sizes >= 3)
+    T, count, mask, rmse, win = np.eye(4), 0, np.zeros(m, bool), np.inf, -1
+    pose = _poses12(T)[0][0]
+    if len(fitted):
+        Ts = np.stack([fit_rigid(src[members[e, :sizes[e]]], dst[members[e, :sizes[e]]]) for e in fitted])
+        counts[fitted] = _capi.pose_score(ctx, src, dst, _poses12(Ts)[0], max_dist)
+        win = int(np.argmax(counts))                            # the first of the largest: ties to the earlier seed
+
+        def score(Tc):
+            c, msk = _capi.pose_score(ctx, src, dst, _poses12(Tc)[0], max_dist, want_mask=True)
+            return int(c[0]), msk[0]
+        T, count, mask, rmse = refine_pose(score, src, dst, Ts[int(np.searchsorted(fitted, win))], refine_rounds)
+        pose = _poses12(T)[0][0]
+        T = _proper(T)
+    if not return_info:
+        return T
+    return T, {"pose": pose, "inliers": mask, "count": int(count), "fitness": count / m if m else 0.0, "rmse": rmse, "hypothesis": win,
+               "n_valid": int(len(fitted)), "deg1": res["deg1"], "deg2": res["deg2"], "seeds": res["seeds"], "members": members,
+               "scores": res["scores"], "seed": int(res["seeds"][win]) if win >= 0 else -1, "counts": counts}
+
+
 def _keypoint_rows(rows, n, name):
     rows = np.asarray(rows)
     if rows.ndim != 1 or (len(rows) and not np.issubdtype(rows.dtype, np.integer)):
@@ -248,16 +339,17 @@ def register_global(source, target, feature_radius, max_dist, normals=None, mutu
     """Global registration end to end: ``compute_fpfh`` on both clouds at ``feature_radius``, ``match_features`` (source
     against target, ``mutual`` / ``ratio``), then ``ransac_pose`` with the remaining keywords.  ``normals``: ``None`` to
     estimate them, or a pair ``(source_normals, target_normals)``.  ``method="fgr"`` hands the matches and the remaining
-    keywords to ``fgr_pose`` instead.
+    keywords to ``fgr_pose`` instead, ``method="sc2"`` to ``sc2_pose`` (at most 32768 matches: the choice where only a few per
+    cent of them are right).
 
     ``keypoints``: ``None`` describes and matches every point; ``"iss"`` detects ISS keypoints on both clouds
     (``iss_keypoints(cloud, **keypoint_args)``); a pair ``(source_rows, target_rows)`` uses the caller's own.  Descriptors are
     then computed at those rows only (``compute_fpfh_rows``), a few thousand rows are matched instead of every point, and the
     matches are mapped back to rows of ``source`` and ``target`` before ``ransac_pose``.  Fewer than 3 keypoints on either side
     give no matches: ``ransac_pose``'s no-match result."""
-    if method not in ("ransac", "fgr"):
-        raise ValueError('method must be "ransac" or "fgr"')
-    pose_from_matches = ransac_pose if method == "ransac" else fgr_pose
+    if method not in ("ransac", "fgr", "sc2"):
+        raise ValueError('method must be "ransac", "fgr" or "sc2"')
+    pose_from_matches = {"ransac": ransac_pose, "fgr": fgr_pose, "sc2": sc2_pose}[method]
     ns, nt = (None, None) if normals is None else normals
     if keypoints is None:
         if keypoint_args is not None:
