@@ -1010,6 +1010,11 @@ PCR_API pcr_status pcr_get_reuse(pcr_context *ctx, int *mode, double *tau, doubl
  * the list passes had to search / points they covered; out[5..7] = mode, searched points (-1 = not read
  * back) and typical displacement (m) of the last pass                                                      */
 PCR_API pcr_status pcr_scan_reuse_stats(pcr_scan *s, double out[8]);
+/* How many pcr_linearize passes of this context had the last level of their fold taken by the host: a host-driven pass on
+ * one GPU (no communicator) that is neither ICP nor a certify + list pass hands the host 8 partial rows in pinned memory
+ * instead of folding them on the device; the host adds them in the device's order, so the sums are bit-identical.
+ * PCR_HOST_FOLD=0 in the environment of a new context keeps every pass on the device path (the count stays 0).       */
+PCR_API pcr_status pcr_context_host_fold_passes(pcr_context *ctx, uint64_t *passes);
 /* variant 1: 1 (default) = the reduce kernel folds the per-block partial sums itself
  * (k_reduce_finalize); 0 = separate fold kernel                                             */
 PCR_API pcr_status pcr_set_fuse_finalize(pcr_context *ctx, int on);

@@ -136,6 +136,7 @@ PROTOTYPES = {
     "pcr_set_reuse": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "pcr_get_reuse": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pcr_scan_reuse_stats": (C.c_int, [_vp, _f64p]),
+    "pcr_context_host_fold_passes": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "pcr_hash64": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcr_target_filter_band": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "pcr_target_index_halo2": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -433,6 +434,12 @@ class Context:
         m, t, u = C.c_int(0), C.c_double(0), C.c_double(0)
         check(lib().pcr_get_reuse(self.handle, C.byref(m), C.byref(t), C.byref(u)))
         return {"mode": m.value, "tau": t.value, "mu": u.value}
+
+    def host_fold_passes(self):
+        """Passes of this context whose last fold level the host took (0 with PCR_HOST_FOLD=0)."""
+        n = C.c_uint64(0)
+        check(lib().pcr_context_host_fold_passes(self.handle, C.byref(n)))
+        return int(n.value)
 
     def get_pipeline(self):
         v, f, m = C.c_int(0), C.c_int(0), C.c_int(0)

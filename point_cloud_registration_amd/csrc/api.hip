@@ -199,6 +199,8 @@ extern "C" pcr_status pcr_context_create(int device, pcr_context **out) {
     if (vo && *vo) ctx->vox_occ = atoi(vo) != 0;
     const char *tl = getenv("PCR_TILE_LOCAL");
     if (tl && *tl) ctx->tile_local = atoi(tl) != 0;
+    const char *hf = getenv("PCR_HOST_FOLD");
+    if (hf && *hf) ctx->host_fold = atoi(hf) != 0;
     const char *sd = getenv("PCR_STALL_DEBUG");
     if (sd && *sd) ctx->stall_debug = atoi(sd) != 0;
     const char *rp = getenv("PCR_RETIRE_PERIOD");
@@ -227,6 +229,7 @@ extern "C" pcr_status pcr_context_destroy(pcr_context *ctx) {
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
+    if (ctx->h_rows) (void)hipHostFree(ctx->h_rows);
     if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
     if (ctx->d_pose) (void)hipFree(ctx->d_pose);
     if (ctx->d_trace) (void)hipFree(ctx->d_trace);
@@ -344,6 +347,12 @@ extern "C" pcr_status pcr_scan_reuse_stats(pcr_scan *s, double out[8]) {
     out[0] = (double)s->st_passes[0]; out[1] = (double)s->st_passes[1]; out[2] = (double)s->st_passes[2];
     out[3] = (double)s->st_marked; out[4] = (double)s->st_listed_of;
     out[5] = (double)s->last_mode; out[6] = (double)s->last_marked; out[7] = s->last_motion;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_context_host_fold_passes(pcr_context *ctx, uint64_t *passes) {
+    PCR_REQUIRE(ctx && passes, "NULL argument");
+    *passes = ctx->host_fold_passes;
     return PCR_OK;
 }
 

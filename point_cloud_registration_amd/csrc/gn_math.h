@@ -205,3 +205,14 @@ PCR_HD static inline void gn_filter_bounds(double band, double bound, float *bou
     *bound2_ff = (float)(bf * bf * 1.000001);
     *mu_ff = (float)(2.0 * band + 3e-5 * bf);
 }
+
+// ---- host fold: the last level of the in-kernel fold (pass_device.h: ticket_fold_emit) on the host ----------------------
+// rows[g * 32 + k]: component k of group g's row; tot[k] in the order the emitting block adds the 8 group rows.  Plain
+// IEEE double adds, as written: the file that calls this must not be built with a flag that lets the compiler reassociate.
+PCR_HD static inline void gn_fold8_rows(const volatile double *rows, double *tot, int ncomp) {
+    for (int k = 0; k < ncomp; ++k) {
+        const double v0 = rows[k], v1 = rows[32 + k], v2 = rows[64 + k], v3 = rows[96 + k];
+        const double v4 = rows[128 + k], v5 = rows[160 + k], v6 = rows[192 + k], v7 = rows[224 + k];
+        tot[k] = ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7));
+    }
+}

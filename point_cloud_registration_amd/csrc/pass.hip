@@ -14,6 +14,8 @@ static int grid8(int64_t want, int64_t cap = INT64_MAX) {
     return nb < 8 ? 8 : (int)nb;
 }
 
+#define PCR_HOST_ROWS_BYTES (sizeof(double) * 8 * 32 + sizeof(uint32_t) * 8 * PCR_GFLAG_STRIDE)
+
 static double cell_edge(const pcr_target *t) { return t->is_voxel ? t->gd.h : (double)t->gf.h; }
 
 pcr_status pcr_ensure_scratch(pcr_context *ctx, int64_t n_points) {
@@ -28,6 +30,10 @@ pcr_status pcr_ensure_scratch(pcr_context *ctx, int64_t n_points) {
         HIP_TRY(hipHostMalloc(&ctx->h_out, sizeof(double) * 64, hipHostMallocMapped | hipHostMallocCoherent));
         memset(ctx->h_out, 0, sizeof(double) * 64);
         HIP_TRY(hipHostGetDevicePointer((void **)&ctx->h_out_dev, ctx->h_out, 0));
+        // host fold: 8 group rows of 32 doubles, then the 8 group sequence words (PCR_GFLAG_STRIDE words apart)
+        HIP_TRY(hipHostMalloc((void **)&ctx->h_rows, PCR_HOST_ROWS_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(ctx->h_rows, 0, PCR_HOST_ROWS_BYTES);
+        HIP_TRY(hipHostGetDevicePointer((void **)&ctx->h_rows_dev, ctx->h_rows, 0));
         // 8 + 1 tickets (a 128-byte line each), then the tile counters
         // ... then the word of k_nn_fix (the stamp of the last filter pass that left work for it)
         const size_t ctr_words = 9 * PCR_TICKET_STRIDE + (size_t)PCR_TILE_CTRS * PCR_TILE_STRIDE + 16;
@@ -525,8 +531,20 @@ pcr_status pcr_run_linearize(pcr_target *t, pcr_scan *s, int kind, const double 
     volatile uint32_t *flag = (volatile uint32_t *)(ctx->h_out + 32);
     ps.f.host_out = direct ? ctx->h_out_dev : nullptr;
     ps.f.host_flag = direct ? (volatile uint32_t *)(ctx->h_out_dev + 32) : nullptr;
-    const uint32_t seq = ++ctx->seq;
+    if (++ctx->seq == 0) ctx->seq = 1;      // (never 0: the sequence words start out zeroed)
+    const uint32_t seq = ctx->seq;
     ps.f.seq = seq;
+    // host fold: the 8 group leaders of the in-kernel fold store their rows to pinned memory and the host adds them -- no
+    // second ticket level on the device (ticket_fold_emit).  Not for ICP (the emitting block forms H from the sums with
+    // multiplications, which host and device need not contract alike) and not for a LIST pass (its count of searched points
+    // is summed by the emitting block); d_out is not written by such a pass, and nothing reads it after a direct one.
+    const bool host_fold = direct && ctx->host_fold && ctx->h_rows_dev != nullptr && ps.fused_fin && kind != PCR_ICP && mode != PCR_NN_LIST;
+    volatile uint32_t *gflags = (volatile uint32_t *)(ctx->h_rows + 8 * 32);
+    if (host_fold) {
+        ps.f.host_rows = ctx->h_rows_dev;
+        ps.f.host_gflags = (volatile uint32_t *)(ctx->h_rows_dev + 8 * 32);
+        ctx->host_fold_passes += 1;
+    }
     const bool stall_dbg = ctx->stall_debug;
     struct timespec ts0, ts1, ts2, tc0, tc2;
     if (stall_dbg) { clock_gettime(CLOCK_MONOTONIC, &ts0); clock_gettime(CLOCK_THREAD_CPUTIME_ID, &tc0); }
@@ -553,7 +571,15 @@ pcr_status pcr_run_linearize(pcr_target *t, pcr_scan *s, int kind, const double 
         if (cs != PCR_OK) return cs;
         HIP_TRY(hipGetLastError());
     }
-    if (flagged) {
+    if (host_fold) {
+        auto all_groups = [&] {
+            for (int g = 0; g < 8; ++g)
+                if (gflags[g * PCR_GFLAG_STRIDE] != seq) return false;
+            return true;
+        };
+        PCR_TRY(wait_host_word(ctx, all_groups, "the fold of a group"));
+        gn_fold8_rows(ctx->h_rows, ctx->h_out, 29);
+    } else if (flagged) {
         PCR_TRY(wait_host_word(ctx, [&] { return *flag == seq; }, "finalize kernel"));
     } else {
         HIP_TRY(hipMemcpyAsync(ctx->h_out, ctx->d_out, sizeof(double) * 31, hipMemcpyDeviceToHost, ctx->stream));

@@ -435,14 +435,80 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
 // One halving step: lanes whose `MASK` bit is clear keep components [0, HALF), the others keep
 // [HALF, 2*HALF); each lane adds its partner's copy of what it keeps.  HALF and MASK are template
 // constants so every acc[] index is static (a runtime-indexed array would live in scratch).
+//
+// PCR_FOLD_SWAP (default 1, gfx950): the exchanges go through the cross-lane paths of the VALU instead of the LDS crossbar
+// (__shfl_xor = ds_bpermute_b32, two per double, each with an address and a wait on lgkmcnt).
+//  - masks 32 and 16 (24 of the 31 exchanges): v_permlane32_swap / v_permlane16_swap trade the upper half of acc[i] for
+//    the lower half of acc[i + HALF] (halves of the wave / of each 32-lane half).  After the two dword swaps every lane
+//    holds, for the component it keeps, its own value in one register pair and its partner's in the other: one add, no
+//    select.  The lower lanes add (own, partner's), the upper lanes (partner's, own): the same two operands as the
+//    fallback's keep + received, and an IEEE add commutes, so the sums are bit-identical (only the payload of a NaN that
+//    meets another NaN may differ).
+//  - masks 8, 2, 1 and the last pair: DPP moves (row_ror:8, quad_perm) of the selected `send`; operand order as the fallback.
+//  - mask 4 has no DPP form on gfx9 and stays on __shfl_xor.
+// Every lane of the wave must be active (all callers fold in uniform control flow, in front of a __syncthreads()).
+// Per fold 64 -> 4 ds_bpermute_b32, 101 fewer v_cndmask and 29 fewer waits on lgkmcnt; every wave of a pass folds at the same
+// moment, at the head of the serial tail of the kernel (k_reduce_finalize<PLANE, 0> at 1.06 M points: 16.2 -> 15.4 us;
+// docs/EXPERIMENTS.md).
+// PCR_FOLD_SWAP=0 keeps the __shfl_xor form everywhere: the fallback for other targets and the A/B partner.
+#ifndef PCR_FOLD_SWAP
+#define PCR_FOLD_SWAP 1
+#endif
+#if PCR_FOLD_SWAP && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_permlane32_swap) && __has_builtin(__builtin_amdgcn_permlane16_swap) && __has_builtin(__builtin_amdgcn_update_dpp)
+#define PCR_FOLD_SWAP_ON 1
+#endif
+#endif
+#ifndef PCR_FOLD_SWAP_ON
+#define PCR_FOLD_SWAP_ON 0
+#endif
+
+#if PCR_FOLD_SWAP_ON
+#define PCR_DPP_ROW_ROR8 0x128            // lane l of a 16-lane row reads lane l ^ 8
+#define PCR_DPP_QUAD_XOR2 0x4E            // quad_perm:[2,3,0,1]
+#define PCR_DPP_QUAD_XOR1 0xB1            // quad_perm:[1,0,3,2]
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false),
+                            __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false));
+}
+#endif
+
+// the partner's copy of v: lane l reads lane l ^ MASK
+template <int MASK>
+__device__ __forceinline__ double xchg_f64(double v) {
+#if PCR_FOLD_SWAP_ON
+    if constexpr (MASK == 8) return dpp_f64<PCR_DPP_ROW_ROR8>(v);
+    else if constexpr (MASK == 2) return dpp_f64<PCR_DPP_QUAD_XOR2>(v);
+    else if constexpr (MASK == 1) return dpp_f64<PCR_DPP_QUAD_XOR1>(v);
+    else
+#endif
+    return shfl_xor_f64(v, MASK);
+}
+
 template <int HALF, int MASK>
 __device__ __forceinline__ void fold_step(double *acc, int lane) {
+#if PCR_FOLD_SWAP_ON
+    if constexpr (MASK == 32 || MASK == 16) {
+#pragma unroll
+        for (int i = 0; i < HALF; ++i) {
+            const unsigned alo = (unsigned)__double2loint(acc[i]), ahi = (unsigned)__double2hiint(acc[i]);
+            const unsigned blo = (unsigned)__double2loint(acc[i + HALF]), bhi = (unsigned)__double2hiint(acc[i + HALF]);
+            // [0]: the first operand with its upper lanes (rows) replaced, [1]: the second with its lower ones replaced
+            const auto lo = MASK == 32 ? __builtin_amdgcn_permlane32_swap(alo, blo, false, false) : __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
+            const auto hi = MASK == 32 ? __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false) : __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
+            acc[i] = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+        }
+        return;
+    }
+#endif
     const bool upper = (lane & MASK) != 0;
 #pragma unroll
     for (int i = 0; i < HALF; ++i) {
         const double send = upper ? acc[i] : acc[i + HALF];
         const double keep = upper ? acc[i + HALF] : acc[i];
-        acc[i] = keep + shfl_xor_f64(send, MASK);
+        acc[i] = keep + xchg_f64<MASK>(send);
     }
 }
 
@@ -453,7 +519,7 @@ __device__ __forceinline__ void wave_fold32(double *acc, int lane) {
     fold_step<4, 8>(acc, lane);
     fold_step<2, 4>(acc, lane);
     fold_step<1, 2>(acc, lane);
-    acc[0] += shfl_xor_f64(acc[0], 1);
+    acc[0] += xchg_f64<1>(acc[0]);
 }
 
 // COHERENT: the store is written through to memory at agent scope, so that a block on ANOTHER XCD
@@ -552,6 +618,7 @@ __device__ __forceinline__ void linearize_body(const LinArgs &a, const PoseK &P,
 #endif
 #ifndef PCR_TICKET_STRIDE
 #define PCR_TICKET_STRIDE 32         // words between the tickets of k_reduce_finalize's fold: a 128-byte line each
+#define PCR_GFLAG_STRIDE 16          // words between the group sequence words of the host fold: a 64-byte host line each
 #endif
 #ifndef PCR_TILE_STATIC_ROUNDS
 #define PCR_TILE_STATIC_ROUNDS 1   // 2 static rounds already unbalance the far poses (whole kernel 127 -> 155 us)
@@ -920,6 +987,10 @@ struct FinArgs {
     double *host_out;          // optional: the same 29 values straight into pinned host memory ...
     volatile uint32_t *host_flag;   // ... followed by this sequence number (host spins on it)
     uint32_t seq;
+    // host fold (NULL: the second ticket level below): pinned host memory for the 8 group rows (32 doubles each) and
+    // one sequence word per group, PCR_GFLAG_STRIDE words apart; the host adds the rows (gn_fold8_rows)
+    double *host_rows;
+    volatile uint32_t *host_gflags;
     // certified reuse: what the search of this pass did (PCR_NN_*, -1 = read it from the pose) and the per-block
     // counts of k_certify; reported in out[29] (points searched by a LIST pass) and out[30] (mode)
     int nn_mode;
@@ -1033,6 +1104,14 @@ __device__ __forceinline__ void finalize_emit(const FinArgs &f, const double *to
 // takes a group's last ticket folds the group's partials into row nblocks+g; the group leader that takes the
 // last of the 8 second-level tickets folds those rows and emits.  8 x (nblocks/8) + 8 serialised atomics
 // instead of nblocks.
+// Host fold (f.host_rows != NULL: a host-driven pass on one GPU that is neither ICP nor a LIST pass, pass.hip): there is no
+// second level on the device.  Each group leader stores its row to pinned host memory, fences, writes the group's sequence
+// word and leaves; the host, which spins on pinned memory anyway, waits for the 8 words and adds the 8 rows in the order of
+// the last level below (gn_math.h: gn_fold8_rows), so the sums are the same bits.  That takes the group-row write-through and
+// its wait, the second ticket, the 8 agent-scope loads, the LDS hop and finalize_emit's staging out of the serial tail of the
+// kernel (k_reduce_finalize<PLANE, 0> at 1.06 M points: 15.3 -> 14.0 us).  Nobody emits then: f.out is not written and the
+// function returns false in every block, so whatever relies on "the block that emitted" (the inline Gauss-Newton step, the
+// batch, the device-resident loop, the communicator path) must leave host_rows NULL.
 // (returns true in the ONE block that folded the last contribution and emitted the result)
 __device__ __forceinline__ bool ticket_fold_emit(double *acc, const LinArgs &a, const FinArgs &f) {
     block_store_partials<true>(acc, a.partials);
@@ -1075,11 +1154,30 @@ __device__ __forceinline__ bool ticket_fold_emit(double *acc, const LinArgs &a, 
     part[r0][c] = (((s16[0] + s16[1]) + (s16[2] + s16[3])) + ((s16[4] + s16[5]) + (s16[6] + s16[7]))) +
                   (((s16[8] + s16[9]) + (s16[10] + s16[11])) + ((s16[12] + s16[13]) + (s16[14] + s16[15])));
     __syncthreads();
+    double t = 0.0;
     if (threadIdx.x < 32) {
         const int k = threadIdx.x;
-        const double t = ((part[0][k] + part[1][k]) + (part[2][k] + part[3][k])) + ((part[4][k] + part[5][k]) + (part[6][k] + part[7][k]));
-        __hip_atomic_store(&rows[(size_t)(f.nblocks + g) * 32 + k], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = ((part[0][k] + part[1][k]) + (part[2][k] + part[3][k])) + ((part[4][k] + part[5][k]) + (part[6][k] + part[7][k]));
     }
+    if (f.host_rows != nullptr) {
+        // ---- host fold: the group row goes to pinned host memory, then the group's sequence word (the hand-off of
+        // finalize_emit: payload, system fence by every storing thread, barrier, flag).  The host adds the 8 rows in the
+        // order of the last level below.  No second ticket, no emitting block: the leader of group 0 re-arms the tile counters
+        // (the search that used them ended before this kernel began, the next one starts after it).
+        if (threadIdx.x < 32) {
+            f.host_rows[g * 32 + threadIdx.x] = t;
+            __threadfence_system();
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            f.host_gflags[g * PCR_GFLAG_STRIDE] = f.seq;
+            __hip_atomic_store(ctr1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next pass
+        }
+        if (g == 0 && threadIdx.x < PCR_TILE_CTRS) f.tile_ctr[threadIdx.x * PCR_TILE_STRIDE] = 0;
+        return false;
+    }
+    if (threadIdx.x < 32)
+        __hip_atomic_store(&rows[(size_t)(f.nblocks + g) * 32 + threadIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // group row stored (lanes 0..31 of wave 0)
     if (threadIdx.x == 0) {
         __hip_atomic_store(ctr1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // re-armed for the next pass

@@ -224,6 +224,13 @@ struct pcr_context {
     double *h_out = nullptr;        // pinned + mapped: 32 doubles, then the completion sequence number
     double *h_out_dev = nullptr;    // device-side address of h_out
     uint32_t seq = 0;
+    // host fold (pcr_run_linearize, one GPU, no communicator): the 8 group leaders of the in-kernel fold store their rows
+    // here and the host adds them (pass_device.h: ticket_fold_emit).  One pinned + mapped block: 8 x 32 doubles, then 8
+    // sequence words a 64-byte line apart.  PCR_HOST_FOLD=0 (read once when the context is created) keeps every pass
+    // on the device path.
+    double *h_rows = nullptr, *h_rows_dev = nullptr;
+    bool host_fold = true;
+    uint64_t host_fold_passes = 0;     // passes whose last level the host folded (pcr_context_host_fold_passes)
     uint32_t passes_since_query = 0;   // see retire_completed (pass.hip)
     bool stall_debug = false;          // PCR_STALL_DEBUG: report where a pass slower than 1 ms spent its time
     int retire_period = 0;             // hipStreamQuery every n-th pass (PCR_RETIRE_PERIOD; 0 = never, the default)
