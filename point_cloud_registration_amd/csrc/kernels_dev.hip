@@ -232,7 +232,10 @@ __global__ void __launch_bounds__(256) k_nn_counters(const LinArgs a, unsigned l
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long t2 = __builtin_readcyclecounter();
         const bool outside = live && c.k0 != 0, empty_in = live && c.k0 == 0 && st.rows_loaded == 0;
-        if (live) nn_rings<float, PtF, true, 0, PCR_NN_BATCH, LB>(a.gf, a.pts, a.cell_start, c, kstart, tx, ty, tz, best, bj, bo, &st);
+        if (live) {
+            if constexpr (LB == PCR_RANGE_XORDER && PCR_ROWS_ONCE) nn_rows_x<true>(a.gf, a.pts, a.cell_start, c, kstart, tx, ty, tz, best, bj, bo, &st);
+            else nn_rings<float, PtF, true, 0, PCR_NN_BATCH, LB>(a.gf, a.pts, a.cell_start, c, kstart, tx, ty, tz, best, bj, bo, &st);
+        }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const unsigned long long t3 = __builtin_readcyclecounter();
         cyc[0] += t1 - t0; cyc[1] += t2 - t1; cyc[2] += t3 - t2;

@@ -15,6 +15,9 @@
 // cell assignment can never prune the true nearest neighbour.  Ties in distance are broken by
 // the smaller original index (the oracle's rule), which makes the result independent of the
 // storage order.
+// On an x-ordered point target (records of a row of cells in ascending x) the plain float32 search runs its rings in the
+// (y, z) plane only and takes every row of cells ONCE, its whole x extent within the budget as one range that is walked from
+// the query's x outward (nn_rows_x below; nn_rings serves every other search).
 //
 // Arithmetic: point targets d2 = fma(dz, dz, fma(dy, dy, dx*dx)) in float32 (explicit fused
 // multiply-adds, exactly specified); centroids d2 = (dx*dx + dy*dy) + dz*dz in float64 with no
@@ -587,6 +590,105 @@ __device__ __forceinline__ void nn_rings(const Geom<Real> &g, const PT *__restri
 #undef PB
 }
 
+// ---- x-ordered targets: every row of cells once (the plain float32 point search, LB == PCR_RANGE_XORDER) ---------------------
+// nn_rings visits a row (dz, dy) as a shell row of ring k = max(|dz|, |dy|) with its x extent cut to cx -+ k, and again in every
+// later ring for its two end cells: up to 1 + 2 (kmax - k) sites, each a dependent pair of cell_start loads and then records.
+// On an x-ordered target nn_scan_range_x already does in x what the rings do in x -- it walks outward from the query and leaves
+// at |dx| > sqrt(best - dyz^2) -- so here the rings run in the (y, z) plane only: ring m = the rows with max(|dz|, |dy|) == m,
+// every row ONCE, its whole x extent within the budget as one range.  All lanes share the order (z outer, address order inside
+// a ring), so a wave stays on one row at a time.  After rings 0 .. m-1 every unvisited point is at least
+// (m-1) h + (distance to the nearest y or z face of the own cell) away, which ends the search (the strict form of nn_certified).
+// `kstart` is nn_ring0's: every cell at Chebyshev distance below it is empty, outside the box or was covered by ring 0, so a
+// row with m < kstart gives the two parts left and right of those cells -- scanned from the end that faces the query, each only
+// when its nearest face is within the budget -- and the own cell is never scanned twice.
+// Exactness: every record with dx^2 + dyz2(row) <= best is tested.  Rows are skipped only on a lower bound of their slab
+// distance, cells only on the clip (nn_rings' own, with limits 0 .. nx-1) or because ring 0 covered them, records only by the
+// exit of nn_scan_range_x; ties go through the (distance, original index) key.
+// PCR_ROWS_ONCE=0 (compile time; the A/B partner) keeps nn_rings for these targets.
+#ifndef PCR_ROWS_ONCE
+#define PCR_ROWS_ONCE 1
+#endif
+template <bool STATS = false, int B = PCR_NN_BATCH>
+__device__ __forceinline__ void nn_rows_x(const Geom<float> &g, const PtF *__restrict__ pts, const uint32_t *__restrict__ cs,
+                                          const NNCell<float> &c, int kstart, float qx, float qy, float qz,
+                                          float &best, uint32_t &bj, uint32_t &borig, NNStats *st = nullptr) {
+    typedef RealTraits<float> RT;
+    if (nn_certified<float>(g, c, kstart, best)) return;           // (this is where reach0 counts)
+    const float lim = 1.0e9f;
+    const int cx = c.cx, cy = c.cy, cz = c.cz;
+    const float fx = c.fx, fy = c.fy, fz = c.fz;
+    const uint32_t unx = (uint32_t)g.nx, plane = (uint32_t)g.ny * (uint32_t)g.nx;   // ncells < 2^32
+    const float xm = 2.f * (g.xq + g.slack);
+    // an outside query: the first ring of rows that touches the box
+    const int m0 = max(max(-cy, cy - (g.ny - 1)), max(max(-cz, cz - (g.nz - 1)), 0));
+    for (int m = m0; m <= c.kmax; ++m) {
+        {
+            // every row of ring m and beyond is at least lb away in (y, z): the stop rule, the strict form of nn_certified
+            const float lb = fmaxf((float)(m - 1) * g.h + fminf(fminf(fy, g.h - fy), fminf(fz, g.h - fz)) - g.slack, 0.f);
+            if (m >= 1 && lb > 0.f && lb * lb > best) break;
+            // A ring below kstart only holds cells at least kstart cells away in x, on either side at least dxe away.  When that
+            // and lb together are out of reach, no row of the ring has a site: on to the next ring without walking its rows
+            // (a query outside the box in x, a query in a wide gap: nn_rings started at kstart and paid nothing for them).
+            if (m < kstart) {
+                const float dxe = fmaxf((float)(kstart - 1) * g.h + fminf(fx, g.h - fx) - g.slack, 0.f);
+                if (dxe * dxe + lb * lb > best) continue;
+            }
+        }
+        if (STATS) st->rings++;
+        const int nseg = m < kstart ? 2 : 1;
+        const int zlo = max(cz - m, 0), zhi = min(cz + m, g.nz - 1);
+        const int yhi = min(cy + m, g.ny - 1);
+        for (int z = zlo; z <= zhi; ++z) {
+            const int dzc = z - cz;
+            float dzm = dzc == 0 ? 0.f : (dzc > 0 ? (float)dzc * g.h - fz : (float)(-dzc - 1) * g.h + fz);
+            dzm = fmaxf(dzm - g.slack, 0.f);
+            const float dz2 = dzm * dzm;
+            if (dz2 > best) continue;
+            // the two slabs of the ring hold all its y; the slabs between them only y = cy -+ m
+            const bool zshell = (dzc == m) || (dzc == -m);
+            const int ystep = zshell ? 1 : 2 * m;
+            // One iteration = one site.  A row with m < kstart takes two iterations (sg = 0: left of the covered cells, 1: right
+            // of them) and works its distance and clip out again for the second, against the best the first one left: nothing of
+            // a row (clip, address, distance) stays in registers across a scan.  (yy, side) is the site of this iteration; (y, sg)
+            // already points at the next one.  It ends: sg goes 0 -> 1 at most once per row, then y grows by ystep >= 1 (2 m only
+            // in a slab between the ring's two, which exists only for m >= 1).  yy < 0 is the row cy - m of such a slab
+            // outside the box.
+            for (int y = zshell ? max(cy - m, 0) : cy - m, sg = 0; y <= yhi;) {
+                const int yy = y, side = sg;
+                if (nseg == 2 && sg == 0) sg = 1; else { sg = 0; y += ystep; }
+                if (yy < 0) continue;
+                const int dyc = yy - cy;
+                float dym = dyc == 0 ? 0.f : (dyc > 0 ? (float)dyc * g.h - fy : (float)(-dyc - 1) * g.h + fy);
+                dym = fmaxf(dym - g.slack, 0.f);
+                const float dyz2 = dz2 + dym * dym;
+                if (dyz2 > best) { if (STATS && side == 0) st->rows_pruned++; continue; }
+                if (nseg == 2) {
+                    // the distance to the nearest face of the first cell beyond the covered ones on this side: before the clip
+                    float dxe = side == 0 ? (float)(kstart - 1) * g.h + fx : (float)kstart * g.h - fx;
+                    dxe = fmaxf(dxe - g.slack, 0.f);
+                    if (!(dyz2 + dxe * dxe <= best)) continue;
+                }
+                int xl = 0, xh = g.nx - 1;
+                if (best < RT::inf()) {                     // clip the row to the remaining budget
+                    const float xr = RT::sqrt_fast(best - dyz2) * 1.000002f + g.slack;
+                    const float a = (qx - xr - g.ox) * g.inv_h, b = (qx + xr - g.ox) * g.inv_h;
+                    if (a > (float)xl) xl = (int)RT::floor_(fminf(a, lim));
+                    if (b < (float)xh) xh = (int)RT::floor_(fmaxf(b, -lim));
+                }
+                float t;
+                if (nseg == 2) {
+                    if (side == 0) { xh = min(xh, cx - kstart); t = 1.f; } else { xl = max(xl, cx + kstart); t = 0.f; }
+                } else t = ((float)(cx - xl) + fx * g.inv_h) * __frcp_rn((float)(xh - xl + 1));
+                if (xl > xh) continue;
+                const uint32_t row = (uint32_t)z * plane + (uint32_t)yy * unx;
+                const uint32_t s_ = cs[row + (uint32_t)xl] & g.cs_mask, e_ = cs[row + (uint32_t)xh + 1u] & g.cs_mask;
+                if (STATS) st->rows_loaded++;
+                nn_scan_range_x<B, STATS>(pts, s_, e_, t, xm, dyz2, qx, qy, qz, best, bj, borig, st);
+            }
+        }
+    }
+}
+
 // The same rings with the rows of a slab taken from the row-occupancy bitmap (Geom::rowocc): the centroid search when
 // the gate spans >= 5 rings (kernels.hip: k_nn_scan<VOXEL = 2>).  A separate function on purpose: routing the plain
 // search through the shared row body (a lambda) cost the 1e8-point search 5-13 % (74.5 / 80.5 vs 70.9 ms per 26 passes).
@@ -701,7 +803,9 @@ __device__ __forceinline__ void nn_search(const Geom<Real> &g, const PT *__restr
     NNCell<Real> c = nn_cell<Real>(g, qx, qy, qz, bound2);
     static_assert(LB == PCR_RANGE_PLAIN || (sizeof(Real) == 4 && TRACK == 0 && !OCC), "leaf / group boxes, x order: plain float32 point search only");
     const int kstart = nn_ring0<Real, PT, STATS, HALO, TRACK, B, LB>(g, pts, cs, c, qx, qy, qz, best, bj, borig, st, tk);
-    if constexpr (LB != PCR_RANGE_PLAIN) {
+    if constexpr (LB == PCR_RANGE_XORDER && PCR_ROWS_ONCE) {
+        nn_rows_x<STATS, B>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st);
+    } else if constexpr (LB != PCR_RANGE_PLAIN) {
         nn_rings<Real, PT, STATS, TRACK, B, LB>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
     } else if (OCC) nn_rings_occ<Real, PT, STATS, TRACK>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
     else nn_rings<Real, PT, STATS, TRACK, B>(g, pts, cs, c, kstart, qx, qy, qz, best, bj, borig, st, tk);
