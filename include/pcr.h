@@ -959,8 +959,13 @@ PCR_API int pcr_x_order_rule(int f32_point_target, int heavy, int64_t n, int cel
 PCR_API pcr_status pcr_target_index_halo(pcr_target *t, double *halo, int64_t *records);
 /* point targets: the same of the second, deeper set of lists (margin 0.25 x cell), which the library builds once a target
  * has served a dozen search + reduce passes and which serves the passes of a Gauss-Newton run whose scan still moves by
- * more than 0.12 cell per pass; both 0 while it does not exist                                                         */
+ * 0.12 to 0.4 cell per pass (the mid set); both 0 while it does not exist                                              */
 PCR_API pcr_status pcr_target_index_halo2(pcr_target *t, double *halo, int64_t *records);
+/* point targets: margin and records of list set `set`: 0 near (= pcr_target_index_halo), 1 mid (= pcr_target_index_halo2),
+ * 2 far (margin 0.35 x cell, built with the mid set except on heavy targets, serves the passes whose scan moves by 0.4 to
+ * 1.5 cell; beyond that the near set, no list reaching across such a step); both 0 while
+ * the set does not exist                                                                                               */
+PCR_API pcr_status pcr_target_index_list_set(pcr_target *t, int set, double *halo, int64_t *records);
 /* voxel targets: the bound (metres) on how far rounding to float32 moved any centroid of the filter index -- what the
  * float32 filter search of the centroid search (voxel.py:171-179) subtracts from its lower bounds before the float64
  * check; 1.75 x 2^-24 x the largest coordinate magnitude of the centroid grid.  0 = no filter index (not built yet:

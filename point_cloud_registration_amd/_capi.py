@@ -140,6 +140,7 @@ PROTOTYPES = {
     "pcr_hash64": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcr_target_filter_band": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "pcr_target_index_halo2": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "pcr_target_index_list_set": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pcr_usable_cpus": (C.c_int, []),
     "pcr_has_dev_kernels": (C.c_int, []),
     "pcr_abi_version": (C.c_int, []),
@@ -757,13 +758,18 @@ class Target:
         check(lib().pcr_target_filter_band(self.handle, C.byref(band)))
         halo2, nh2 = C.c_double(0), C.c_int64(0)
         check(lib().pcr_target_index_halo2(self.handle, C.byref(halo2), C.byref(nh2)))
+        sets = []                       # near, mid, far: (margin in metres, records); zeros while a set does not exist
+        for k in range(3):
+            hk, nk = C.c_double(0), C.c_int64(0)
+            check(lib().pcr_target_index_list_set(self.handle, k, C.byref(hk), C.byref(nk)))
+            sets.append((hk.value, nk.value))
         pmax, p99, heavy = C.c_int64(0), C.c_int64(0), C.c_int(0)
         check(lib().pcr_target_index_population(self.handle, C.byref(pmax), C.byref(p99), C.byref(heavy)))
         xq = C.c_double(0)
         check(lib().pcr_target_index_x_order(self.handle, C.byref(xq)))
         return {"cell": cell.value, "dims": tuple(int(d) for d in dims), "occupied": occ.value, "n": n.value,
                 "halo": halo.value, "halo_records": nh.value, "filter_band": band.value,
-                "halo2": halo2.value, "halo2_records": nh2.value,
+                "halo2": halo2.value, "halo2_records": nh2.value, "list_sets": sets,
                 "pop_max": pmax.value, "pop_p99": p99.value, "heavy": bool(heavy.value),
                 "x_ordered": xq.value > 0.0, "xq": xq.value}
 

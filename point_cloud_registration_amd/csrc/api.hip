@@ -470,10 +470,12 @@ static void target_free(pcr_target *t) { pcr_target_release(t); }
 void pcr_target_release(pcr_target *t) {
     if (!t) return;
     target_free(t->filter);
-    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->lbox_h2, t->gbox_h2, t->cs_h, t->pts_h, t->j_h, t->cs_h2, t->pts_h2, t->j_h2, t->pts, t->pn, t->col, t->cint, t->gcov, t->pts64, t->means, t->vnorm, t->vicov, t->vcov,
+    void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->cs_h, t->pts_h, t->j_h, t->pts, t->pn, t->col, t->cint, t->gcov, t->pts64, t->means, t->vnorm, t->vicov, t->vcov,
                     t->st_mean, t->st_cov, t->st_norm, t->st_icov, t->st_counts, t->st_keys};
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     for (void *p : ptrs) pcr_persist_free(t->ctx, p);
+    for (const pcr_target::ListSet &d : t->deep)
+        for (void *p : {(void *)d.cs, (void *)d.pts, (void *)d.j, (void *)d.lbox, (void *)d.gbox}) pcr_persist_free(t->ctx, p);
     delete t;
 }
 
@@ -681,8 +683,16 @@ extern "C" pcr_status pcr_target_index_halo(pcr_target *t, double *halo, int64_t
 
 extern "C" pcr_status pcr_target_index_halo2(pcr_target *t, double *halo, int64_t *records) {
     PCR_REQUIRE(t, "NULL argument");
-    if (halo) *halo = t->is_voxel ? 0.0 : (double)t->halo2;
-    if (records) *records = t->is_voxel ? 0 : t->n_h2;
+    if (halo) *halo = t->is_voxel ? 0.0 : (double)t->deep[0].halo;
+    if (records) *records = t->is_voxel ? 0 : t->deep[0].n;
+    return PCR_OK;
+}
+
+extern "C" pcr_status pcr_target_index_list_set(pcr_target *t, int set, double *halo, int64_t *records) {
+    PCR_REQUIRE(t && set >= 0 && set <= PCR_DEEP_SETS, "NULL argument or no such list set");
+    if (set == 0) return pcr_target_index_halo(t, halo, records);
+    if (halo) *halo = t->is_voxel ? 0.0 : (double)t->deep[set - 1].halo;
+    if (records) *records = t->is_voxel ? 0 : t->deep[set - 1].n;
     return PCR_OK;
 }
 

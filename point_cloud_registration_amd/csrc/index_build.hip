@@ -988,35 +988,40 @@ pcr_status pcr_build_point_grid(pcr_context *ctx, const float *d_xyz, int64_t n,
     return PCR_OK;       // (no row-occupancy bitmap for point targets: measured slower, nn_device.h)
 }
 
-// The second, DEEPER set of extended lists of a point target (halo PCR_HALO2_FRAC x cell), built by the first pass that
-// gets its cost back (pass.hip: pass_setup); a pass picks one of the two sets by how far the scan moved.
+// The DEEPER sets of extended lists of a point target (mid: halo PCR_HALO2_FRAC x cell, far: PCR_HALO3_FRAC), built by the first
+// pass that gets their cost back (pass.hip: pass_setup); a pass picks one of the sets by how far the scan moved.
 pcr_status pcr_build_deep_lists(pcr_context *ctx, pcr_target *t) {
-    if (t->is_voxel || !t->cs_h || t->n <= 0 || t->cs_h2) return PCR_OK;
-    // (an opt-out and a size cap.  PCR_DEEP_LISTS=0 never builds the set; the estimate -- copies per point scale
-    // with (1 + 2 margin)^2 on a surface: 2.3 at 0.25 cell where the first set holds n_h / n at 0.1 -- must fit PCR_DEEP_LISTS_MB,
-    // default 1/16 of the device's free memory, or the target keeps the one set)
-    {
-        const char *de = getenv("PCR_DEEP_LISTS");
-        if (de && atoi(de) == 0) return PCR_OK;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        const char *mb = getenv("PCR_DEEP_LISTS_MB");
-        const double budget = mb && *mb ? atof(mb) * 1048576.0 : (double)free_b / 16.0;
-        const double grow = (1.0 + 2.0 * PCR_HALO2_FRAC) * (1.0 + 2.0 * PCR_HALO2_FRAC) / (1.2 * 1.2);
-        const double est = (double)(t->n_h > 0 ? t->n_h : t->n) * grow * 20.0 + 4.0 * ((double)t->gf.nx * t->gf.ny * t->gf.nz);
-        if (est > budget) return PCR_OK;
-    }
-    DevBuf<uint32_t> cs_h, j_h;
-    DevBuf<PtF> pts_h;
-    int64_t n_h = 0;
-    PCR_TRY(build_halo_lists(ctx, t->gf, t->pts, t->n, t->cell_start, PCR_HALO2_FRAC, &cs_h, &pts_h, &j_h, &n_h));
-    if (n_h <= 0) return PCR_OK;
-    t->halo2 = (float)(PCR_HALO2_FRAC * (double)t->gf.h);
-    t->n_h2 = n_h;
-    t->cs_h2 = cs_h.release(); t->pts_h2 = pts_h.release(); t->j_h2 = j_h.release();
-    if (t->heavy) {
-        PCR_TRY(make_leaf_boxes(ctx, t->pts_h2, n_h, t->gf.h, t->gf.slack, &t->lbox_h2, &t->gbox_h2));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (t->is_voxel || !t->cs_h || t->n <= 0 || t->deep[0].cs) return PCR_OK;
+    // (an opt-out and a size cap.  PCR_DEEP_LISTS=0 never builds a set; the estimate -- copies per point scale
+    // with (1 + 2 margin)^2 on a surface: 2.3 at 0.25 cell and 3.2 at 0.35 where the first set holds n_h / n at 0.1 -- of a set
+    // and the sets before it must fit PCR_DEEP_LISTS_MB, default 1/16 of the device's free memory, or the target does without it)
+    const char *de = getenv("PCR_DEEP_LISTS");
+    if (de && atoi(de) == 0) return PCR_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    const char *mb = getenv("PCR_DEEP_LISTS_MB");
+    const double budget = mb && *mb ? atof(mb) * 1048576.0 : (double)free_b / 16.0;
+    const double frac[PCR_DEEP_SETS] = {PCR_HALO2_FRAC, PCR_HALO3_FRAC};
+    double used = 0.0;
+    // (a heavy target gets the mid set only: the far set's depth was measured on clouds of even density, and on a LiDAR sweep
+    // it lost -- plane_lidar 0.243 -> 0.248 ms per step)
+    for (int k = 0; k < (t->heavy ? 1 : PCR_DEEP_SETS); ++k) {
+        const double grow = (1.0 + 2.0 * frac[k]) * (1.0 + 2.0 * frac[k]) / (1.2 * 1.2);
+        used += (double)(t->n_h > 0 ? t->n_h : t->n) * grow * 20.0 + 4.0 * ((double)t->gf.nx * t->gf.ny * t->gf.nz);
+        if (used > budget) break;
+        DevBuf<uint32_t> cs_h, j_h;
+        DevBuf<PtF> pts_h;
+        int64_t n_h = 0;
+        PCR_TRY(build_halo_lists(ctx, t->gf, t->pts, t->n, t->cell_start, frac[k], &cs_h, &pts_h, &j_h, &n_h));
+        if (n_h <= 0) break;          // (the copies do not fit the 28-bit offsets: nor would a deeper set's)
+        pcr_target::ListSet &d = t->deep[k];
+        d.halo = (float)(frac[k] * (double)t->gf.h);
+        d.n = n_h;
+        d.cs = cs_h.release(); d.pts = pts_h.release(); d.j = j_h.release();
+        if (t->heavy) {
+            PCR_TRY(make_leaf_boxes(ctx, d.pts, n_h, t->gf.h, t->gf.slack, &d.lbox, &d.gbox));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
     }
     return PCR_OK;
 }

@@ -277,7 +277,7 @@ __device__ __forceinline__ void pose_arm(PoseDev *p, const double *T, int max_it
     p->iter = 0;
     p->done = max_iter > 0 ? PCR_LOOP_RUNNING : PCR_LOOP_MAXITER;
     p->tile_local = 0;
-    p->halo_deep = 1;          // the first pass knows nothing about its distance to the target: the deeper lists (equal there)
+    p->halo_deep = PCR_DEEP_SETS;   // the first pass knows nothing about its distance to the target: the deepest lists there are
 }
 
 // The O(1) tail of an iteration on the device (ONE thread): record the trace row, dx = -solve(H, g),
@@ -299,7 +299,7 @@ __device__ __forceinline__ void gn_update(const FinArgs &f, double (*A)[7]) {
     // hand-out policy of the next search (see pass_enqueue): block-local once the scan moves by less than local_len
     const double moved = r == 0 ? gn_typical_motion(T_old, T, f.bb_c, f.bb_e) : 0.0;
     p->tile_local = (r == 0 && f.local_len > 0.0 && moved < f.local_len) ? 1 : 0;
-    p->halo_deep = (r == 0 && moved >= f.deep_len) ? 1 : 0;
+    p->halo_deep = (r != 0 || moved >= f.out_len) ? 0 : (moved >= f.far_len ? 2 : (moved >= f.deep_len ? 1 : 0));
     int done = r == 2 ? PCR_LOOP_SINGULAR : (r == 1 ? PCR_LOOP_CONVERGED : PCR_LOOP_RUNNING);
     if (r == 0) pose_write(p, T);
     const int it1 = it + 1;

@@ -71,6 +71,7 @@ struct Pass {
     bool fused_fin;      // the fold of the block partials inside the producing kernel instead of k_finalize
     bool gn_inline;      // device-resident loop, fused kernel, one GPU: the Gauss-Newton step runs inside the fused kernel
     double motion;       // typical displacement of the scan since the previous pass over it (host-driven passes; -1 unknown)
+    bool list_force;     // PCR_LIST_SET put one deeper list set in place of both (pass_fill_lin)
     int nn_mode;         // PCR_NN_FULL / TRACK / LIST
     bool reuse_ready;    // the scan has the buffers of the certified-reuse path
     bool q6;             // PlaneICP pass over a float64 point target: float64 search (quirk Q6, pcr_target::pts64)
@@ -216,7 +217,19 @@ static void pass_fill_lin(Pass *ps, double max_dist, unsigned flags, bool use_fi
         a.band_f = (float)(t->band64 * 1.000001);
         flags |= PCR_IFLAG_NOGATE;
     }
-    if (deep && t->cs_h2) { a.cs_h2 = t->cs_h2; a.pts_h2 = t->pts_h2; a.j_h2 = t->j_h2; a.halo2_f = t->halo2; a.lbox_h2 = t->lbox_h2; a.gbox_h2 = t->gbox_h2; }
+    if (deep) {
+        // (PCR_LIST_SET = 0 / 1 / 2, developer switch: every plain full search reads that set, near / mid / far, if the target has it)
+        const char *fe = getenv("PCR_LIST_SET");
+        const int force = fe && *fe ? atoi(fe) : -1;
+        for (int k = 0, have = -1; k < PCR_DEEP_SETS; ++k) {      // a set the target lacks reads as the deepest one below it
+            if (t->deep[k].cs) have = k;
+            const int use = force < 0 ? have : (force >= 1 && force <= PCR_DEEP_SETS && t->deep[force - 1].cs ? force - 1 : -1);
+            if (use < 0) continue;
+            const pcr_target::ListSet &d = t->deep[use];
+            a.deep[k].cs = d.cs; a.deep[k].pts = d.pts; a.deep[k].j = d.j; a.deep[k].lbox = d.lbox; a.deep[k].gbox = d.gbox; a.deep[k].halo = d.halo;
+        }
+        ps->list_force = force >= 1 && a.deep[0].halo > 0.f;
+    }
     a.md_f = (float)max_dist; a.md_d = max_dist;
     const double bound = max_dist * (1.0 + 1e-6);
     a.bound2_f = (float)(bound * bound); a.bound2_d = bound * bound;
@@ -238,6 +251,9 @@ static void pass_fill_fin(Pass *ps) {
     for (int i = 0; i < 3; ++i) { f.bb_c[i] = s->bb_c[i]; f.bb_e[i] = s->bb_e[i]; }
     f.local_len = ctx->local_frac * cell_edge(ps->t);
     f.deep_len = PCR_HALO2_MOVE * cell_edge(ps->t);
+    f.far_len = PCR_HALO3_MOVE * cell_edge(ps->t);
+    f.out_len = ps->t->heavy ? HUGE_VAL : PCR_HALO_OUT_MOVE * cell_edge(ps->t);      // (heavy targets: mid from deep_len on, as measured)
+    if (ps->list_force) { f.deep_len = f.far_len = 0.0; f.out_len = HUGE_VAL; }       // (PCR_LIST_SET: whatever the step, the forced set)
     f.ucnt = s->ucnt; f.n_ucnt = ps->a.nblocks;
     f.partials = ctx->d_partials; f.tile_ctr = ctx->d_tile_ctr + 9 * PCR_TICKET_STRIDE; f.tickets = ctx->d_tile_ctr;
     f.nblocks = ps->a.nblocks; f.kind = ps->kind; f.out = ctx->d_out;
@@ -427,10 +443,11 @@ static pcr_status enqueue_search(Pass *ps, dim3 grid, bool filter) {
             const bool fhalo = ps->q6 ? ps->t->cs_h != nullptr : ps->t->filter->cs_h != nullptr;
             launch_nn_filter(fhalo, ps->a.sched_local == 1 ? 1 : 0, !ps->fused_fin, ps->q6, nn_grid, ctx->stream, a);
         } else {
-            // host-driven pass over a point target: the list set by how far the scan moved since the previous pass (unknown: the deeper one)
-            if (!vox && a.pose == nullptr && a.halo2_f > 0.f && mode == PCR_NN_FULL && !(ps->motion >= 0.0 && ps->motion < ps->f.deep_len)) {
-                ps->a.gf.halo = a.halo2_f; ps->a.gf.cs_h = a.cs_h2; ps->a.gf.pts_h = a.pts_h2; ps->a.gf.j_h = a.j_h2;
-                ps->a.gf.lbox_h = a.lbox_h2; ps->a.gf.gbox_h = a.gbox_h2;
+            // host-driven pass over a point target: the list set by how far the scan moved since the previous pass (unknown: the deepest one)
+            if (!vox && a.pose == nullptr && mode == PCR_NN_FULL) {
+                const double m = ps->motion;
+                const int k = m < 0.0 ? 1 : (m >= ps->f.out_len ? -1 : (m >= ps->f.far_len ? 1 : (m >= ps->f.deep_len ? 0 : -1)));
+                if (k >= 0 && a.deep[k].halo > 0.f) use_lists(ps->a.gf, a.deep[k]);
             }
             launch_plain_search(ps, nn_grid);
         }

@@ -64,13 +64,16 @@ struct LinArgs {
     uint32_t *nn_j;
     uint32_t *tile_ctr;   // tile counters (64 B apart) of the NN kernels' dynamic hand-out
     int sched_local;      // 1: block-local hand-out (small scans), 0: global counters (see nn_tile_loop)
-    // the deeper set of extended lists of a point target (pcr_target::cs_h2 ...; halo2_f = 0: none).  Host-driven passes
-    // put the set they chose into gf; the device-resident loop (pose != NULL) picks per iteration (PoseDev::halo_deep)
-    const uint32_t *cs_h2;
-    const void *pts_h2;
-    const uint32_t *j_h2;
-    float halo2_f;
-    const float4 *lbox_h2, *gbox_h2;     // leaf / group boxes of the deeper lists (heavy targets)
+    // the deeper sets of extended lists of a point target (pcr_target::deep; [0] mid, [1] far; halo = 0: none -- the host fills
+    // a missing set with the deepest one below it).  Host-driven passes put the set they chose into gf; the device-resident
+    // loop (pose != NULL) picks per iteration (PoseDev::halo_deep)
+    struct DeepLists {
+        const uint32_t *cs;
+        const void *pts;
+        const uint32_t *j;
+        const float4 *lbox, *gbox;       // leaf / group boxes of the lists (heavy targets)
+        float halo;
+    } deep[PCR_DEEP_SETS];
 };
 
 // what the rows kernels (rows.hip: k_rows<KIND, MODE>) read and write besides LinArgs; every array is in CALLER order
@@ -89,13 +92,17 @@ struct RowArgs {
     int64_t *col_idx;
 };
 
-// the geometry a point search of this launch reads: gf, with the deeper lists swapped in when the device-resident loop
-// asked for them (wave-uniform: a handful of scalar selects at kernel start)
+// the geometry a point search reads from one of the deeper list sets
+__host__ __device__ __forceinline__ void use_lists(Geom<float> &g, const LinArgs::DeepLists &d) {
+    g.halo = d.halo; g.cs_h = d.cs; g.pts_h = d.pts; g.j_h = d.j; g.lbox_h = d.lbox; g.gbox_h = d.gbox;
+}
+// the geometry a point search of this launch reads: gf, with a deeper set swapped in when the device-resident loop
+// asked for one (wave-uniform: a handful of scalar selects at kernel start)
 __device__ __forceinline__ Geom<float> select_lists(const LinArgs &a) {
     Geom<float> g = a.gf;
-    if (a.pose != nullptr && a.halo2_f > 0.f && __builtin_amdgcn_readfirstlane(a.pose->halo_deep) != 0) {
-        g.halo = a.halo2_f; g.cs_h = a.cs_h2; g.pts_h = a.pts_h2; g.j_h = a.j_h2; g.lbox_h = a.lbox_h2; g.gbox_h = a.gbox_h2;
-    }
+    const int k = a.pose != nullptr ? __builtin_amdgcn_readfirstlane(a.pose->halo_deep) : 0;
+    if (k >= 2 && a.deep[1].halo > 0.f) use_lists(g, a.deep[1]);
+    else if (k >= 1 && a.deep[0].halo > 0.f) use_lists(g, a.deep[0]);
     return g;
 }
 
@@ -999,7 +1006,8 @@ struct FinArgs {
     // bounding box of the scan and the displacement below which the next search deals its tiles block-locally
     float bb_c[3], bb_e[3];
     double local_len;
-    double deep_len;           // ... and the displacement from which on it reads the deeper set of extended lists
+    double deep_len, far_len;  // ... and the displacements from which on it reads the mid / the far set of extended lists
+    double out_len;            // ... and the near set again (a step no list reaches across)
     // device-resident Gauss-Newton loop (pcr_align; registration.py:89-111 behind the boundary)
     PoseDev *pose;             // NULL: plain pass
     int max_iter;

@@ -91,10 +91,25 @@ static_assert(sizeof(Geom<float>) == 136 && sizeof(Geom<double>) == 160, "Geom i
 #ifndef PCR_HALO2_FRAC
 #define PCR_HALO2_FRAC 0.25      // margin of the deeper list set, x cell
 #endif
-#define PCR_HALO2_AFTER 12       // passes a point target serves before the deeper set is built (~0.3 ms: repaid after ~60 passes)
+#define PCR_HALO2_AFTER 12       // passes a point target serves before the deeper sets are built (docs/EXPERIMENTS.md: what they cost)
 #ifndef PCR_HALO2_MOVE
-#define PCR_HALO2_MOVE 0.12      // the deeper set serves passes whose scan moved by at least this x cell since the previous pass
+#define PCR_HALO2_MOVE 0.12      // the mid set serves passes whose scan moved by at least this x cell since the previous pass
 #endif
+// the far set: deeper again, for the steps of the middle of a Gauss-Newton run (plane_b01, k_nn_scan at a 0.58-cell / 1.06-cell
+// step: 0.25 cell 67.2 / 112.0 us, 0.35 cell 62.5 / 104.5, 0.45 cell 59.7 / 103.9; at a 0.29-cell step 0.25 wins, 28.1 against
+// 31.6 and 34.7).  0.35, not 0.45: with 100 MB of far lists beside the other two sets the converged poses lost 1 us each
+#ifndef PCR_HALO3_FRAC
+#define PCR_HALO3_FRAC 0.35
+#endif
+#ifndef PCR_HALO3_MOVE
+#define PCR_HALO3_MOVE 0.4
+#endif
+// ... and from this step on no list reaches the matches and the shallowest one costs least (plane_b01 at a step of two cells,
+// k_nn_scan: 0.1 cell 153.7 us, 0.25 cell 154.4, 0.45 cell 157.6): the near set
+#ifndef PCR_HALO_OUT_MOVE
+#define PCR_HALO_OUT_MOVE 1.5
+#endif
+#define PCR_DEEP_SETS 2          // list sets beyond the first: mid (PCR_HALO2_FRAC), far (PCR_HALO3_FRAC)
 #define PCR_GAP_SHIFT 28
 #define PCR_GAP_MAX 15
 
@@ -120,7 +135,7 @@ struct PoseDev {
     int iter;              // passes completed
     int done;              // 0 running, 1 converged, 2 singular, 3 max_iter reached
     int tile_local;        // hand-out policy of the next search, decided by k_gn_update from the size of its step
-    int halo_deep;         // the next search reads the deeper set of extended lists (the step was large), same decision point
+    int halo_deep;         // the list set the next search reads, by the size of the step: 0 near, 1 mid, 2 far; same decision point
 };
 #define PCR_LOOP_RUNNING 0
 #define PCR_LOOP_CONVERGED 1
@@ -296,21 +311,24 @@ struct pcr_target {
     uint32_t *cell_start = nullptr;
     uint32_t *cell_seed = nullptr;
     unsigned long long *rowocc = nullptr;   // row-occupancy bitmap of the grid (Geom::rowocc)
-    float4 *lbox = nullptr, *gbox = nullptr, *lbox_h = nullptr, *gbox_h = nullptr, *lbox_h2 = nullptr, *gbox_h2 = nullptr;   // Geom::lbox ...
+    float4 *lbox = nullptr, *gbox = nullptr, *lbox_h = nullptr, *gbox_h = nullptr;   // Geom::lbox ...
     int64_t pop_max = 0, pop_p99 = 0;       // largest / 99th-percentile population of an occupied cell (pcr_target_index_population)
     bool heavy = false;                     // some cells hold far more points than the average: boxes built, box-aware search
     uint32_t *cs_h = nullptr;        // extended (halo) lists of point targets
     PtF *pts_h = nullptr;
     uint32_t *j_h = nullptr;
     int64_t n_h = 0;                 // records in pts_h
-    // a second, deeper set of the same lists (halo PCR_HALO2_FRAC x cell), built lazily once the target has served
-    // PCR_HALO2_AFTER search + reduce passes; a pass reads it while the scan still moves by more than PCR_HALO2_MOVE x cell
-    // per pass (measured per pose on plane_b01, halo 0.1 / 0.25: 232 / 232, 180 / 180, 105 / 89, 49 / 40, 32 / 39 us)
-    uint32_t *cs_h2 = nullptr;
-    PtF *pts_h2 = nullptr;
-    uint32_t *j_h2 = nullptr;
-    int64_t n_h2 = 0;
-    float halo2 = 0;
+    // deeper sets of the same lists (mid: halo PCR_HALO2_FRAC x cell, far: PCR_HALO3_FRAC), built lazily once the target has
+    // served PCR_HALO2_AFTER search + reduce passes; a pass reads the set that fits how far the scan moved since the previous
+    // pass (PCR_HALO2_MOVE / PCR_HALO3_MOVE x cell; docs/EXPERIMENTS.md: the list-depth table)
+    struct ListSet {
+        uint32_t *cs = nullptr;
+        PtF *pts = nullptr;
+        uint32_t *j = nullptr;
+        float4 *lbox = nullptr, *gbox = nullptr;     // leaf / group boxes (heavy targets)
+        int64_t n = 0;               // records in pts
+        float halo = 0;              // metres; 0: not built
+    } deep[PCR_DEEP_SETS];
     int split_passes = 0;            // search + reduce passes served (point targets)
     bool deep_tried = false;
     // point targets
