@@ -523,7 +523,7 @@ static bool make_geom(const float lo[3], const float hi[3], double h, Geom<Real>
     double mag = 0;
     for (int a = 0; a < 3; ++a) { mag = fmax(mag, fabs((double)lo[a])); mag = fmax(mag, fabs((double)hi[a])); }
     const double eps = sizeof(Real) == 4 ? 1.2e-7 : 2.3e-16;
-    g->slack = (Real)(16.0 * eps * (mag + h) + 1e-30);
+    g->slack = (Real)((double)PCR_SLACK_ULPS * eps * (mag + h) + 1e-30);
     g->cs_mask = 0xffffffffu;
     g->seed = nullptr;
     g->halo = (Real)0; g->cs_h = nullptr; g->pts_h = nullptr; g->j_h = nullptr; g->rowocc = nullptr; g->nyw = 0; g->nxb = 0; g->lbox = nullptr; g->gbox = nullptr; g->lbox_h = nullptr; g->gbox_h = nullptr;

@@ -110,6 +110,12 @@ static_assert(sizeof(Geom<float>) == 136 && sizeof(Geom<double>) == 160, "Geom i
 #define PCR_HALO_OUT_MOVE 1.5
 #endif
 #define PCR_DEEP_SETS 2          // list sets beyond the first: mid (PCR_HALO2_FRAC), far (PCR_HALO3_FRAC)
+// Geom::slack (index_build.hip: make_geom) in units of the relative spacing of the grid's number format at the box's largest
+// coordinate.  16 ships; 0 and 1 are what docs/EXPERIMENTS.md ("Does the magnitude net hold anything?") built to see which tests
+// notice: tests/test_gpu_magnitude.py fails without slack
+#ifndef PCR_SLACK_ULPS
+#define PCR_SLACK_ULPS 16
+#endif
 #define PCR_GAP_SHIFT 28
 #define PCR_GAP_MAX 15
 
