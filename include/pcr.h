@@ -399,7 +399,9 @@ PCR_API pcr_status pcr_vgicp_align(pcr_target *t, pcr_scan *s, const double T_in
  *   c  = (n_q.x v_0 + n_q.y v_1) + n_q.z v_2
  *   normal gate: skipped unless |c| >= min_cos (a NaN c is skipped); min_cos = 0 keeps every finite pair
  *   s  = c < 0 ? -1 : +1                                PCA normals carry no sign: the objective does not depend on it -- negating
- *                                                       any n_p or n_q returns the same bits
+ *                                                       any n_p or n_q returns the same bits wherever c != 0.  At c == 0 (-0
+ *                                                       included) there is no sign to follow: s = +1, and negating ONE of the
+ *                                                       two normals turns m into 0.5 (n_q - v); such a pair passes min_cos = 0 only
  *   m  = 0.5 (n_q + s v)                                componentwise; the products with s and 0.5 are exact
  *   r  = (m_0 d_0 + m_1 d_1) + m_2 d_2,  J = [m, p x (R^T m)]      PCR_PLANE's row with m in the place of the normal
  *   H += J^T J, g += J^T r, e2 += r r (fma), count += 1            PCR_PLANE's accumulation; out[29] as pcr_linearize
