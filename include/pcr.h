@@ -779,6 +779,48 @@ PCR_API pcr_status pcr_target_iss_saliency(pcr_target *t, float r, double gamma2
 PCR_API pcr_status pcr_target_iss_keypoints(pcr_target *t, float r_salient, float r_nonmax, double gamma21, double gamma32,
                                             int min_neighbors, uint8_t *is_keypoint, double *saliency_or_null);
 
+/* ---- radius and hybrid neighbourhoods for normals and covariances (no reference counterpart) ----
+ * The k nearest neighbours of a LiDAR return lie on its own ring line; a ball (Open3D's KDTreeSearchParamRadius, PCL's
+ * setRadiusSearch) or a ball capped at its nearest max_nn (KDTreeSearchParamHybrid) does not.  For a point p of a cloud, a
+ * radius r (float32, finite, >= 0) and 0 <= max_nn <= 64, always over the float32 copy of the points:
+ * Radius set (max_nn == 0): exactly what pcr_radius_query returns for the query p against its own cloud -- the float32 rule
+ *   sqrtf(dist2_f32) <= r, p itself and its exact duplicates included; a point with a NaN or infinite coordinate has the
+ *   empty set.
+ * Hybrid set (1 <= max_nn <= 64): the first min(max_nn, count) entries of that segment in its order, (squared distance, index)
+ *   ascending: the nearest max_nn OF THE BALL, with the radius search's <= r -- not the bounded k-NN's strict <.
+ * Moments, all in float64 from the widened float32 inputs, no contraction, every sum a plain +: count = the members of the
+ *   set; the anchor a = the first member in summation order; for every member d = q - a, s1 += d (3 sums), s2 += d d^T (6
+ *   sums); mean = a + s1 / count; raw covariance C = s2 / count - (s1 / count)(s1 / count)^T, stored xx xy xz yy yz zz -- the
+ *   arithmetic of the ISS scatter matrix above.  The empty set has count 0, mean 0 and C = 0.
+ * Summation order: the radius set in ascending order of the index's cell-sorted position (the order in which the radius
+ *   search walks the members for ANY query), so two points with the same set get the same bits; the hybrid set in list order,
+ *   nearest first.
+ * Normal: the unit eigenvector of the smallest eigenvalue of C (cyclic Jacobi in float64, as pcr_target_estimate_normals),
+ *   rounded to float32; exactly (0, 0, 0) when count < 3.  A zero normal makes PlaneICP's row vanish (J = 0, r = 0) instead of
+ *   pulling along an arbitrary direction: a target point whose ball holds fewer than three points takes no part in its pose.
+ *   (SymmetricICP averages it with the scan's normal; its min_cos > 0 gates such a pair out.)
+ * Covariance: C through the mode / eps finish of pcr_target_estimate_covariances (PCR_COV_PLANE: I - (1 - eps) n n^T with n the
+ *   eigenvector above; PCR_COV_RAW: C itself), rounded to float32.  A set of one member (or none) has C = 0: that call's k = 1.
+ * pcr_target_ball_moments: count (n), mean3 (n x 3), cov6 (n x 6, the raw covariance) in the order of the array the target
+ *   was created from.  pcr_target_estimate_normals_radius fills the target's normals exactly as pcr_target_estimate_normals
+ *   does (pcr_target_get_normals, PlaneICP, SymmetricICP, ColoredICP and FPFH then read them; a colour payload is freed),
+ *   pcr_target_estimate_covariances_radius its covariances as pcr_target_estimate_covariances does; the _scan_ pair estimates
+ *   every scan point within the scan, as pcr_scan_estimate_normals / _covariances do.  The _out_or_null arrays receive the
+ *   estimate and the counts in the caller's order.  No atomics: the same call twice returns the same bits.
+ * PCR_ERR_INVALID, checked in this order, nothing written: a NULL argument; r negative, NaN or infinite; max_nn outside
+ *   [0, 64]; (covariances) a bad mode / eps; a voxel target; a scan that does not know the caller's order where an output is
+ *   asked for.  An empty cloud returns PCR_OK without a launch.
+ * PCR_BALL_TIMES=1 (environment, read once): every call reports its kernel's milliseconds on stderr.                     */
+PCR_API pcr_status pcr_target_ball_moments(pcr_target *t, float r, int max_nn, int64_t *count, double *mean3, double *cov6);
+PCR_API pcr_status pcr_target_estimate_normals_radius(pcr_target *t, float r, int max_nn, float *normals_out_or_null,
+                                                      int64_t *count_out_or_null);
+PCR_API pcr_status pcr_scan_estimate_normals_radius(pcr_scan *s, float r, int max_nn, float *normals_out_or_null,
+                                                    int64_t *count_out_or_null);
+PCR_API pcr_status pcr_target_estimate_covariances_radius(pcr_target *t, float r, int max_nn, int mode, double eps,
+                                                          float *cov_out_or_null, int64_t *count_out_or_null);
+PCR_API pcr_status pcr_scan_estimate_covariances_radius(pcr_scan *s, float r, int max_nn, int mode, double eps,
+                                                        float *cov_out_or_null, int64_t *count_out_or_null);
+
 /* ---- pose hypotheses from correspondences: RANSAC (no reference counterpart) ---------------
  * The last third of a global registration: from matches (pcr_feature_match) to a pose that an aligner can start from.
  * src, dst: m x 3 float32 host arrays, finite; row j is one correspondence, scan point -> map point.  A pose is 12 float32:

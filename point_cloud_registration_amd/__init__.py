@@ -19,7 +19,7 @@ from .symmetric_icp import SymmetricICP
 from .colored_icp import ColoredICP
 from .kdtree import KDTree
 from .voxel import VoxelGrid, voxel_filter, color_by_voxel, get_keys
-from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree
+from .estimate_normals import estimate_normals, get_norm_lines, estimate_norm_with_tree, ball_moments
 from .caratheodory import fast_caratheodory, create_gn_set
 from .outliers import remove_radius_outliers, remove_statistical_outliers
 from .features import compute_fpfh, compute_fpfh_rows, match_features, select_matches
@@ -34,5 +34,5 @@ __all__ = [
     "skew_time_vector", "skew", "skew2", "fast_caratheodory", "create_gn_set",
     "remove_radius_outliers", "remove_statistical_outliers", "compute_fpfh", "match_features", "select_matches",
     "score_poses", "fit_rigid", "ransac_pose", "fgr_pose", "register_global", "iss_keypoints", "compute_fpfh_rows",
-    "robust_weight", "trim_threshold", "match_compatibility", "sc2_pose",
+    "robust_weight", "trim_threshold", "match_compatibility", "sc2_pose", "ball_moments",
 ]

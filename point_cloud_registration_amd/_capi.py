@@ -99,6 +99,12 @@ PROTOTYPES = {
     # ISS keypoints (include/pcr.h, keypoints.py)
     "pcr_target_iss_saliency": (C.c_int, [_vp, C.c_float, C.c_double, C.c_double, C.c_int, _f64p, _f64p, _i64p]),
     "pcr_target_iss_keypoints": (C.c_int, [_vp, C.c_float, C.c_float, C.c_double, C.c_double, C.c_int, _u8p, _vp]),
+    # radius and hybrid neighbourhoods for normals and covariances (include/pcr.h, ball.py)
+    "pcr_target_ball_moments": (C.c_int, [_vp, C.c_float, C.c_int, _i64p, _f64p, _f64p]),
+    "pcr_target_estimate_normals_radius": (C.c_int, [_vp, C.c_float, C.c_int, _vp, _vp]),
+    "pcr_scan_estimate_normals_radius": (C.c_int, [_vp, C.c_float, C.c_int, _vp, _vp]),
+    "pcr_target_estimate_covariances_radius": (C.c_int, [_vp, C.c_float, C.c_int, C.c_int, C.c_double, _vp, _vp]),
+    "pcr_scan_estimate_covariances_radius": (C.c_int, [_vp, C.c_float, C.c_int, C.c_int, C.c_double, _vp, _vp]),
     # pose hypotheses from correspondences and pose scoring (include/pcr.h, global_registration.py)
     "pcr_pose_score": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, _f32p, C.c_int64, C.c_float, _i32p, _vp]),
     "pcr_ransac_poses": (C.c_int, [_vp, _f32p, _f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float,
@@ -361,6 +367,22 @@ def check_radius(r):
     if not (np.isfinite(r) and r >= 0):
         raise ValueError(f"radius must be finite and >= 0, got {r}")
     return r
+
+
+def check_ball(radius, max_nn):
+    """A ball neighbourhood as (float radius, int max_nn): the radius finite and >= 0, ``max_nn`` None or 0 (the whole ball) or
+    an integer in [1, 64] (its nearest ``max_nn``), the library's own rule (csrc/ball_moments.hip: ball_check), else ValueError
+    before the GPU is touched.  ``max_nn`` without a radius is an error as well."""
+    if radius is None:
+        if max_nn is not None:
+            raise ValueError("max_nn needs a radius")
+        raise ValueError("radius must be finite and >= 0, got None")
+    r = check_radius(radius)
+    if max_nn is None:
+        return r, 0
+    if int(max_nn) != max_nn or not 0 <= int(max_nn) <= 64:
+        raise ValueError("max_nn must be an integer in [0, 64] (0 or None: the whole ball)")
+    return r, int(max_nn)
 
 
 def check_iss(gamma_21, gamma_32, min_neighbors):
@@ -686,6 +708,30 @@ class Target:
         check(lib().pcr_target_get_normals(self.handle, out))
         return out
 
+    # -- radius / hybrid neighbourhoods (include/pcr.h): ``max_nn`` None or 0 = the whole ball; everything in the caller's order
+    def ball_moments(self, r, max_nn=None):
+        """-> (count (N,) int64, mean (N, 3) float64, cov (N, 6) float64: the raw covariance xx xy xz yy yz zz)."""
+        r, max_nn = check_ball(r, max_nn)
+        n = self.size()
+        count, mean, cov = np.zeros(n, np.int64), np.zeros((n, 3), np.float64), np.zeros((n, 6), np.float64)
+        check(lib().pcr_target_ball_moments(self.handle, r, max_nn, count, mean, cov))
+        return count, mean, cov
+
+    def estimate_normals_radius(self, r, max_nn=None, want=True, want_counts=False):
+        """Fills the target's normals from the ball; -> normals (N, 3) float32 (``want``), or (normals, counts (N,) int64)."""
+        r, max_nn = check_ball(r, max_nn)
+        out = np.empty((self.size(), 3), np.float32) if want else None
+        cnt = np.zeros(self.size(), np.int64) if want_counts else None
+        check(lib().pcr_target_estimate_normals_radius(self.handle, r, max_nn, _ptr(out), _ptr(cnt)))
+        return (out, cnt) if want_counts else out
+
+    def estimate_covariances_radius(self, r, max_nn=None, mode=COV_PLANE, eps=1e-3, want=True, want_counts=False):
+        r, max_nn = check_ball(r, max_nn)
+        out = np.empty((self.size(), 6), np.float32) if want else None
+        cnt = np.zeros(self.size(), np.int64) if want_counts else None
+        check(lib().pcr_target_estimate_covariances_radius(self.handle, r, max_nn, int(mode), float(eps), _ptr(out), _ptr(cnt)))
+        return (out, cnt) if want_counts else out
+
     # -- ColoredICP: float32 intensities (N,) and tangent-plane gradients (N, 3), in the caller's order (include/pcr.h)
     def set_intensity(self, intensity, gradient=None):
         intensity = np.ascontiguousarray(intensity, dtype=np.float32)
@@ -989,6 +1035,21 @@ class Scan:
         out = np.empty((self.n, 3), np.float32) if want else None
         check(lib().pcr_scan_estimate_normals(self.handle, int(k), _ptr(out)))
         return out
+
+    # -- the same from a ball (include/pcr.h: radius and hybrid neighbourhoods), as the methods of ``Target``
+    def estimate_normals_radius(self, r, max_nn=None, want=True, want_counts=False):
+        r, max_nn = check_ball(r, max_nn)
+        out = np.empty((self.n, 3), np.float32) if want else None
+        cnt = np.zeros(self.n, np.int64) if want_counts else None
+        check(lib().pcr_scan_estimate_normals_radius(self.handle, r, max_nn, _ptr(out), _ptr(cnt)))
+        return (out, cnt) if want_counts else out
+
+    def estimate_covariances_radius(self, r, max_nn=None, mode=COV_PLANE, eps=1e-3, want=True, want_counts=False):
+        r, max_nn = check_ball(r, max_nn)
+        out = np.empty((self.n, 6), np.float32) if want else None
+        cnt = np.zeros(self.n, np.int64) if want_counts else None
+        check(lib().pcr_scan_estimate_covariances_radius(self.handle, r, max_nn, int(mode), float(eps), _ptr(out), _ptr(cnt)))
+        return (out, cnt) if want_counts else out
 
     def set_normals(self, normals):
         normals = np.ascontiguousarray(normals, dtype=np.float32)

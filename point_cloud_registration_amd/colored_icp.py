@@ -70,7 +70,7 @@ class ColoredICP(MatchPass):
                 raise ValueError("gradient must be finite")
         tree = KDTree(target, device=self._device, _ctx=self._ctx())
         if n is None:
-            tree._target.estimate_normals(self.k, compat=False, want=False)
+            self._estimate_normals(tree._target, compat=False)      # (the gradient below stays with the k nearest neighbours)
         else:
             tree._target.set_normals(n)
         tree._target.set_intensity(inten, g)

@@ -42,11 +42,7 @@ template <typename LIST>
 __device__ __forceinline__ void gicp_cov_finish(const PtF *pts, const PtF me, int mode, double eps, float *cov, LIST &L) {
     double c[6];
     knn_cov6_f64(L, pts, c);
-    if (mode == PCR_COV_PLANE) {
-        double n[3];
-        smallest_eigvec3(c, n);
-        plane_cov6(n, eps, c);
-    }
+    cov6_finish(mode, eps, c);
     float *dst = cov + 6 * (size_t)pt_orig(me);
 #pragma unroll
     for (int a = 0; a < 6; ++a) dst[a] = (float)c[a];

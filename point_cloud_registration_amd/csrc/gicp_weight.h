@@ -13,6 +13,16 @@ __device__ __forceinline__ void plane_cov6(const double n[3], double eps, double
     c[3] = 1.0 - s * n[1] * n[1]; c[4] = -s * n[1] * n[2]; c[5] = 1.0 - s * n[2] * n[2];
 }
 
+// what a per-point covariance estimate does with the raw covariance of a neighbourhood (k_gicp_cov, k_ball_moments):
+// PCR_COV_PLANE replaces it by the plane regulariser of its normal, PCR_COV_RAW keeps it
+__device__ __forceinline__ void cov6_finish(int mode, double eps, double c[6]) {
+    if (mode == PCR_COV_PLANE) {
+        double n[3];
+        smallest_eigvec3(c, n);
+        plane_cov6(n, eps, c);
+    }
+}
+
 // M6 = (Cq + R Cp R^T)^-1 as xx xy xz yy yz zz, float64.  CQ: the type the target side's covariance is stored in (widened
 // entry by entry before the sum)
 template <typename CQ>

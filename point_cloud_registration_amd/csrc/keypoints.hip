@@ -20,25 +20,7 @@
 
 #define ISS_BLOCK RAD_BLOCK
 
-struct IssSink {
-    float r, b2;
-    const PtF *pts;
-    double ax, ay, az;       // the anchor: the first member offered
-    double s1[3], s2[6];     // sums of d and of d d^T (xx xy xz yy yz zz)
-    uint32_t k;
-    __device__ __forceinline__ float bound() const { return b2; }
-    __device__ __forceinline__ void offer(float d2f, uint32_t j, uint32_t) {
-        if (d2f <= b2 && rad_member(d2f, r)) {                               // (NaN fails the pre-test)
-            const PtF q = pts[j];
-            if (k == 0u) { ax = (double)q.x; ay = (double)q.y; az = (double)q.z; }
-            const double dx = (double)q.x - ax, dy = (double)q.y - ay, dz = (double)q.z - az;
-            s1[0] = s1[0] + dx; s1[1] = s1[1] + dy; s1[2] = s1[2] + dz;
-            s2[0] = s2[0] + dx * dx; s2[1] = s2[1] + dx * dy; s2[2] = s2[2] + dx * dz;
-            s2[3] = s2[3] + dy * dy; s2[4] = s2[4] + dy * dz; s2[5] = s2[5] + dz * dz;
-            ++k;
-        }
-    }
-};
+typedef RadMoments IssSink;      // (radius_device.h: the anchor and the 9 float64 sums, shared with ball_moments.hip)
 
 struct IssNmsSink {
     float r, b2;

@@ -100,3 +100,43 @@ __device__ __forceinline__ void rad_ball_walk(const Geom<float> &g, const PtF *_
         }
     }
 }
+
+// ---- a sink: the moments of the members ------------------------------------------------------------------------------------
+// Float64 sums of d = q - a and d d^T over the members, a = the FIRST member offered.  rad_ball_walk offers records in ascending
+// cell-sorted index for any query -- slabs by z, rows by y, a row's cells by x, one contiguous range of records per row -- so the
+// anchor and the order of the sums are functions of the member set alone.  The anchor, the 9 sums and k stay in registers.
+// Shared by keypoints.hip (k_iss_saliency) and ball_moments.hip; add() alone sums a list that is not walked.
+struct RadMoments {
+    float r, b2;
+    const PtF *pts;
+    double ax, ay, az;       // the anchor: the first member offered
+    double s1[3], s2[6];     // sums of d and of d d^T (xx xy xz yy yz zz)
+    uint32_t k;
+    __device__ __forceinline__ void init(float r_, const PtF *pts_) {
+        r = r_; b2 = rad_bound2(r_); pts = pts_; k = 0u;
+        ax = ay = az = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s1[c] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s2[c] = 0.0;
+    }
+    __device__ __forceinline__ float bound() const { return b2; }
+    __device__ __forceinline__ void add(const PtF q) {
+        if (k == 0u) { ax = (double)q.x; ay = (double)q.y; az = (double)q.z; }
+        const double dx = (double)q.x - ax, dy = (double)q.y - ay, dz = (double)q.z - az;
+        s1[0] = s1[0] + dx; s1[1] = s1[1] + dy; s1[2] = s1[2] + dz;
+        s2[0] = s2[0] + dx * dx; s2[1] = s2[1] + dx * dy; s2[2] = s2[2] + dx * dz;
+        s2[3] = s2[3] + dy * dy; s2[4] = s2[4] + dy * dz; s2[5] = s2[5] + dz * dz;
+        ++k;
+    }
+    __device__ __forceinline__ void offer(float d2f, uint32_t j, uint32_t) {
+        if (d2f <= b2 && rad_member(d2f, r)) add(pts[j]);                    // (NaN fails the pre-test)
+    }
+    // m = s1 / k and the raw covariance C = s2 / k - m m^T (xx xy xz yy yz zz); zeros for the empty set
+    __device__ __forceinline__ void finish(double m[3], double c[6]) const {
+        const double kd = (double)(k != 0u ? k : 1u);
+        m[0] = s1[0] / kd; m[1] = s1[1] / kd; m[2] = s1[2] / kd;
+        c[0] = s2[0] / kd - m[0] * m[0]; c[1] = s2[1] / kd - m[0] * m[1]; c[2] = s2[2] / kd - m[0] * m[2];
+        c[3] = s2[3] / kd - m[1] * m[1]; c[4] = s2[4] / kd - m[1] * m[2]; c[5] = s2[5] / kd - m[2] * m[2];
+    }
+};

@@ -38,8 +38,8 @@ class ScanCovariances:
                 raise ValueError("source_cov must have shape (N, 6) or (N, 3, 3)")
             return c
         return self._payload_scan(source, fresh, "_gicp_cov", given if source_cov is not None else None, _capi.Scan.set_covariances,
-                                  ("estimated", self.k, self.regularization, self.eps),
-                                  lambda scan: scan.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False))
+                                  ("estimated", self._neighbourhood(), self.regularization, self.eps),
+                                  lambda scan: self._estimate_covariances(scan, _MODES[self.regularization], self.eps))
 
 
 class DistributionPass(ScanCovariances, MatchPass):
@@ -109,7 +109,7 @@ class GICP(DistributionPass):
                 raise ValueError("cov must have shape (N, 6) or (N, 3, 3)")
         tree = KDTree(target, device=self._device, _ctx=self._ctx())
         if c is None:
-            tree._target.estimate_covariances(self.k, _MODES[self.regularization], self.eps, want=False)
+            self._estimate_covariances(tree._target, _MODES[self.regularization], self.eps)
         else:
             tree._target.set_covariances(c)
         self.kdtree, self.target = tree, target

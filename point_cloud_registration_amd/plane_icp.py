@@ -5,13 +5,16 @@ import numpy as np
 from . import _capi
 from .kdtree import KDTree
 from .math_tools import skew, transform_points
-from .registration import Registration
+from .registration import Registration, ball_neighbourhood
 
 
 class PlaneICP(Registration):
     KIND = _capi.PLANE
 
-    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=15, compat_normals=True, **kw):
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=15, compat_normals=True, normal_radius=None, normal_max_nn=None, **kw):
+        """``normal_radius`` (with ``normal_max_nn``: its nearest ``normal_max_nn``): ``set_target`` estimates the normals from
+        every point within that radius instead of from the ``k`` nearest neighbours, as ``estimate_normals(radius=...)`` does."""
+        self._normal_ball = ball_neighbourhood(self, normal_radius, normal_max_nn, kw, "normal_radius")
         super().__init__(max_iter=max_iter, tol=tol, **kw)
         self.max_dist = max_dist
         self.k = k
@@ -35,7 +38,10 @@ class PlaneICP(Registration):
             # k-NN PCA normals on the GPU (estimate_normals.py:27-87).  They stay there: ``self.normal`` (the attribute the
             # reference sets, plane_icp.py:23-24) reads them back the first time somebody asks -- 12.7 MB over PCIe per
             # 1.06 M points, 0.35 ms of a 3.4 ms set_target that align() never needs
-            self.kdtree._target.estimate_normals(self.k, compat=self._compat_normals, want=False)
+            if self._normal_ball is not None:
+                self.kdtree._target.estimate_normals_radius(*self._normal_ball, want=False)
+            else:
+                self.kdtree._target.estimate_normals(self.k, compat=self._compat_normals, want=False)
             self._normal = None
         else:
             self._normal = np.asarray(norm)

@@ -89,6 +89,18 @@ def normalize_batch_inputs(sources, poses=None):
     return arrays, offsets, item_scan, Ts
 
 
+def ball_neighbourhood(obj, radius, max_nn, kw, name="radius"):
+    """The ``radius`` / ``max_nn`` keywords of a class that estimates normals or covariances -> None (the k nearest
+    neighbours) or ``(radius, max_nn)`` as ``_capi.check_ball`` returns them.  The ball estimates run on one GPU of one
+    process: with ``devices=`` or ``comm=`` among the keywords ``kw`` they are refused."""
+    if radius is None and max_nn is None:
+        return None
+    ball = _capi.check_ball(radius, max_nn)
+    if kw.get("devices") is not None or kw.get("comm") is not None:
+        raise NotImplementedError(f"{type(obj).__name__} does not support {name}= with devices= or comm=")
+    return ball
+
+
 class Registration:
     KIND = None           # _capi.ICP / PLANE / VPLANE / NDT in the subclasses
 
@@ -383,7 +395,11 @@ class MatchPass(Registration):
     KIND = None           # no kind of pcr_linearize
     _UNIT = None          # "gicp", "vgicp", "symm", "color"
 
-    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, trim=None, **kw):
+    def __init__(self, max_iter=30, max_dist=2, tol=1e-3, k=10, robust=None, robust_scale=1.0, trim=None, radius=None, max_nn=None, **kw):
+        # what the class estimates -- target and scan payloads -- comes from the ball when there is one (include/pcr.h: radius
+        # and hybrid neighbourhoods), else from the k nearest neighbours
+        self._ball = ball_neighbourhood(self, radius, max_nn, kw)
+        self.radius, self.max_nn = radius, max_nn
         if kw.get("devices") is not None or kw.get("comm") is not None:
             raise ValueError(f"{type(self).__name__} runs on one GPU of one process: not with comm= or devices=")
         if not 1 <= int(k) <= 64:
@@ -416,6 +432,22 @@ class MatchPass(Registration):
 
     def _pass_params(self):
         return ()
+
+    # -- what the class estimates, on a ``_capi.Target`` or a ``_capi.Scan`` alike
+    def _neighbourhood(self):
+        """What a payload cache remembers of the neighbourhood an estimate came from: a scan that served a ``k = 10`` aligner
+        is estimated again for one with a ball, and the other way round."""
+        return ("k", self.k) if self._ball is None else ("ball",) + self._ball
+
+    def _estimate_normals(self, cloud, **target_only):
+        if self._ball is not None:
+            return cloud.estimate_normals_radius(*self._ball, want=False)
+        return cloud.estimate_normals(self.k, want=False, **target_only)
+
+    def _estimate_covariances(self, cloud, mode, eps):
+        if self._ball is not None:
+            return cloud.estimate_covariances_radius(*self._ball, mode=mode, eps=eps, want=False)
+        return cloud.estimate_covariances(self.k, mode, eps, want=False)
 
     def _pass_scan(self, source, *extras, **kw):
         """The device copy of ``source`` with what the class's pass needs on it (``source_cov``, ``source_normals``, ...)."""

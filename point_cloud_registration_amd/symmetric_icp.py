@@ -44,7 +44,7 @@ class SymmetricICP(MatchPass):
                 raise ValueError("norm must have the shape of the target")
         tree = KDTree(target, device=self._device, _ctx=self._ctx())
         if n is None:
-            tree._target.estimate_normals(self.k, compat=False, want=False)
+            self._estimate_normals(tree._target, compat=False)
         else:
             tree._target.set_normals(n)
         self.kdtree, self.target = tree, target
@@ -78,7 +78,7 @@ class SymmetricICP(MatchPass):
                 raise ValueError("source_normals must have shape (N, 3)")
             return nrm
         return self._payload_scan(source, fresh, "_symm_nrm", given if source_normals is not None else None, _capi.Scan.set_normals,
-                                  ("estimated", self.k), lambda scan: scan.estimate_normals(self.k, want=False))
+                                  ("estimated", self._neighbourhood()), self._estimate_normals)
 
     def _pass_scan(self, source, source_normals=None):
         return self._symm_scan(source, source_normals)
