@@ -566,6 +566,56 @@ PCR_API pcr_status pcr_color_align_robust(pcr_target *t, pcr_scan *s, const doub
 PCR_API pcr_status pcr_color_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, double lambda_geometric,
                                        unsigned flags, double *s_out);
 
+/* ---- Voxelized GICP with direct voxel neighbourhoods: 1, 7 or 27 voxels, no search ------------
+ * The association of the VGICP paper and of fast_gicp / small_gicp (DIRECT1 / DIRECT7 / DIRECT27): a scan point is paired
+ * with the kept voxel that CONTAINS its transformed position and with that voxel's neighbours, one distribution-to-
+ * distribution term per voxel found; the voxels are found by integer lookup in the target's hash keys.  The rule:
+ *   t        the float32 transform of scan point p as every pass computes it: ((R0 x + R1 y) + R2 z) + t, nothing contracted
+ *   cell     c = floor((double)t / voxel_size) per axis: voxel_size the double the target was built with, IEEE float64
+ *            division (no reciprocal).  A point with a non-finite coordinate, or with |c| > 2^40 on an axis, has no voxel.
+ *            (A float32 cloud is BUILT with the division in float32.  The two agree exactly for power-of-two voxel sizes;
+ *            otherwise they agree except for coordinates within rounding of a voxel face.)
+ *   offsets  neighbors = 1: (0,0,0)
+ *            neighbors = 7: (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
+ *            neighbors = 27: dz outer, dy middle, dx inner, each -1, 0, +1: the own voxel is column 13
+ *   voxel    of cell c + o: the kept voxel whose key equals the build's hash of c + o,
+ *            ((((z P) mod M) + y) P) mod M + x with P = 116101, M = 10^10 and the non-negative modulo -- the keys
+ *            pcr_target_voxels_get returns.  The hash is the build's own identity of a voxel: the lookup inherits its
+ *            collisions and adds none.
+ *   pair     (point, found voxel v) is kept iff sqrt((dx^2 + dy^2) + dz^2) < max_dist with d = (double)t - mean_v (strict,
+ *            float64: the gate of pcr_vgicp_linearize)
+ *   term     every kept pair contributes exactly what a correspondence of pcr_vgicp_linearize contributes: M = (Cv + R Cp
+ *            R^T)^-1 with its det == 0 rule, the same accumulation; under a robust kernel the weight w(d^T M d) of
+ *            pcr_vgicp_linearize_robust.  The pairs of a point are added in offset order.  No weighting by point counts.
+ *   out[28]  the number of kept pairs
+ * pcr_target_voxels_lookup: the key-order indices (rows of pcr_target_voxels_get) of the voxels of m float32 points, taken as
+ *   already transformed: idx is m x neighbors int64, -1 where there is no kept voxel.  The lookup data are built by the first
+ *   call that needs them and freed with the target; keys that do not ascend strictly give PCR_ERR_INVALID then.
+ * pcr_target_voxels_set_keys: the keys of a target made by pcr_target_voxels_create_from_stats, n int64 in the order of its
+ *   means (such a target has none, and every call of this section gives PCR_ERR_NO_TARGET until it does).  PCR_ERR_INVALID
+ *   on a target built from points: its keys are the build's.  Only the ORDER of the keys is ever checked (strictly ascending,
+ *   by the first lookup).  That key i is the hash of the cell mean i lies in is the caller's responsibility and is NOT
+ *   verified: with keys that do not belong to the means a point is paired with whatever voxel its cell's key names, the gate
+ *   on the distance to that voxel's mean being the only thing that still drops such a pair.
+ * pcr_vgicp_direct_linearize: out[29] as pcr_vgicp_linearize; rb NULL or PCR_ROBUST_NONE: the plain pass.  One launch, one
+ *   lane per scan point, and the fold of pcr_vgicp_linearize: no atomics, the grid depends on the scan size and the device
+ *   only -- two calls return the same bits.  Refused, in this order: NULL arguments; neighbors not 1, 7 or 27
+ *   (PCR_ERR_INVALID); the robust kernel; a point target, a target without covariances or keys, a scan without covariances
+ *   (PCR_ERR_NO_TARGET); different contexts; max_dist <= 0; a context with a communicator (PCR_ERR_UNSUPPORTED).  A target
+ *   with no kept voxel and an empty scan give zeros.  A refused call writes nothing.
+ * pcr_vgicp_direct_align: the host-driven loop of pcr_vgicp_align over that pass: same step, same trace rows.
+ * pcr_vgicp_direct_residuals: d^T M d of every (point, offset), n x neighbors float64 in the caller's order (the scan must
+ *   know it), +inf where there is no kept pair.                                                                            */
+PCR_API pcr_status pcr_target_voxels_lookup(pcr_target *t, const float *xyz, int64_t m, int neighbors, int64_t *idx);
+PCR_API pcr_status pcr_target_voxels_set_keys(pcr_target *t, const int64_t *keys);
+PCR_API pcr_status pcr_vgicp_direct_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, int neighbors,
+                                              const pcr_robust *rb_or_null, unsigned flags, double out[29]);
+PCR_API pcr_status pcr_vgicp_direct_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
+                                          int neighbors, const pcr_robust *rb_or_null, unsigned flags, double T_out[16], int *iterations,
+                                          double *trace_or_null);
+PCR_API pcr_status pcr_vgicp_direct_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, int neighbors,
+                                              unsigned flags, double *s_out);
+
 /* ---- adaptive pass: trimmed ICP and robust scales taken from each pass's own residuals ---------
  * No reference counterpart (Chetverikov et al.: "The Trimmed Iterative Closest Point Algorithm", ICPR 2002; what PCL offers as
  * CorrespondenceRejectorTrimmed / CorrespondenceRejectorMedianDistance and libpointmatcher as TrimmedDistOutlierFilter /

@@ -209,6 +209,14 @@ PROTOTYPES = {
     "pcr_color_align_robust": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_double, _vp, C.c_uint, _f64p,
                                          C.POINTER(C.c_int), _vp]),
     "pcr_color_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_double, C.c_uint, _vp]),
+    # VGICP with direct voxel neighbourhoods: the containing-voxel lookup and the pass over 1, 7 or 27 voxels per point
+    # (include/pcr.h); rb: a pcr_robust by pointer, or NULL
+    "pcr_target_voxels_lookup": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp]),
+    "pcr_target_voxels_set_keys": (C.c_int, [_vp, _vp]),
+    "pcr_vgicp_direct_linearize": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_int, _vp, C.c_uint, _f64p]),
+    "pcr_vgicp_direct_align": (C.c_int, [_vp, _vp, _f64p, C.c_int, C.c_double, C.c_double, C.c_int, _vp, C.c_uint, _f64p,
+                                         C.POINTER(C.c_int), _vp]),
+    "pcr_vgicp_direct_residuals": (C.c_int, [_vp, _vp, _f64p, C.c_double, C.c_int, C.c_uint, _vp]),
     # the adaptive pass of the same four: a trim or a robust scale from each pass's own residuals, and the exact order statistic
     # behind it (include/pcr.h); ad: a pcr_adaptive by pointer; stats: 4 doubles (per iteration)
     "pcr_order_statistic": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
@@ -784,6 +792,23 @@ class Target:
         out = np.empty((self.size(), 6), np.float64)
         check(lib().pcr_target_voxels_get_covariances(self.handle, out))
         return out
+
+    # -- direct voxel lookup (include/pcr.h): the kept voxel that contains a point, and its neighbours
+    def lookup(self, q, neighbors=1):
+        """-> (M, neighbors) int64 rows of voxel_stats for the float32 points ``q``, -1 where there is no kept voxel."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("points must have shape (M, 3)")
+        idx = np.empty((q.shape[0], max(int(neighbors), 0)), np.int64)
+        check(lib().pcr_target_voxels_lookup(self.handle, _ptr(q), q.shape[0], int(neighbors), _ptr(idx)))
+        return idx
+
+    def set_voxel_keys(self, keys):
+        """The hash keys of a target made by ``voxels_from_stats``, in the order of its means."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        if keys.shape != (self.size(),):
+            raise ValueError("keys must have shape (Nv,)")
+        check(lib().pcr_target_voxels_set_keys(self.handle, _ptr(keys)))
 
     def voxel_stats(self, names=("mean", "cov", "norm", "icov", "counts", "keys")):
         n = self.size()
@@ -1720,6 +1745,34 @@ def _match_unit(unit):
 
 for _unit in MATCH_UNITS:
     globals().update(_match_unit(_unit))
+
+
+# ---- VGICP with direct voxel neighbourhoods (include/pcr.h): entry points of its own, not a row of MATCH_UNITS -------------
+NEIGHBORS = (1, 7, 27)
+
+
+def vgicp_direct_linearize(target, scan, T, max_dist, neighbors, robust=None, flags=0):
+    """pcr_vgicp_direct_linearize -> the 29 sums over the kept (point, voxel) pairs; ``robust``: (kind, scale), or None -> NULL."""
+    rb, keep = _rb(robust)
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty(29)
+    check(lib().pcr_vgicp_direct_linearize(target.handle, scan.handle, T, float(max_dist), int(neighbors), rb, int(flags), out))
+    return out
+
+
+def vgicp_direct_align(target, scan, T_init, max_iter, tol, max_dist, neighbors, robust=None, flags=0, want_trace=False):
+    """pcr_vgicp_direct_align -> (T, iterations[, trace rows])."""
+    rb, keep = _rb(robust)
+    return _align(lib().pcr_vgicp_direct_align, (target.handle, scan.handle), T_init, max_iter, tol, max_dist, flags, want_trace,
+                  mid=(int(neighbors), rb))
+
+
+def vgicp_direct_residuals(target, scan, T, max_dist, neighbors, flags=0):
+    """pcr_vgicp_direct_residuals -> (N, neighbors) float64 in the caller's order, inf where there is no kept pair."""
+    T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+    out = np.empty((scan.n, max(int(neighbors), 0)))
+    check(lib().pcr_vgicp_direct_residuals(target.handle, scan.handle, T, float(max_dist), int(neighbors), int(flags), _ptr(out)))
+    return out
 
 
 _linearize_fast = None

@@ -471,7 +471,7 @@ void pcr_target_release(pcr_target *t) {
     if (!t) return;
     target_free(t->filter);
     void *ptrs[] = {t->cell_start, t->cell_seed, t->rowocc, t->lbox, t->gbox, t->lbox_h, t->gbox_h, t->cs_h, t->pts_h, t->j_h, t->pts, t->pn, t->col, t->cint, t->gcov, t->pts64, t->means, t->vnorm, t->vicov, t->vcov,
-                    t->st_mean, t->st_cov, t->st_norm, t->st_icov, t->st_counts, t->st_keys};
+                    t->st_mean, t->st_cov, t->st_norm, t->st_icov, t->st_counts, t->st_keys, t->key_inv};
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     for (void *p : ptrs) pcr_persist_free(t->ctx, p);
     for (const pcr_target::ListSet &d : t->deep)

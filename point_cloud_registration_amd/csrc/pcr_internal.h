@@ -364,6 +364,9 @@ struct pcr_target {
     double *st_mean = nullptr, *st_cov = nullptr, *st_norm = nullptr, *st_icov = nullptr;
     int64_t *st_counts = nullptr, *st_keys = nullptr;
     double voxel_size = 0;
+    // direct voxel lookup (vgicp_direct.hip), built by the first call that needs it: key_inv[i] = position in `means` (and in
+    // vcov) of the voxel at key-order index i, once st_keys has been seen to ascend strictly
+    uint32_t *key_inv = nullptr;
     // float32 filter of the centroid search (k_nn_filter): a point index over the float32-ROUNDED centroids, in the
     // order of `means` (its "original index" is the cell-sorted index of the centroid); filter_band bounds how far a
     // centroid moves when it is rounded to float32 (metres).  nullptr: no filter (coordinates too large, PCR_VOX_FILTER=0)

@@ -57,6 +57,16 @@ class VoxelGrid:
         out["dist"] = dist
         return out
 
+    def lookup(self, points, neighbors=1):
+        """The kept voxel that CONTAINS each point and its neighbours -> (N, neighbors) int64 rows of ``mean``, -1 where there
+        is no kept voxel.  Points are cast to float32, as ``align`` casts a scan; the cell is ``floor(float64(p) /
+        voxel_size)``, found by integer lookup in the build's hash keys (``include/pcr.h``: direct voxel neighbourhoods).
+        ``neighbors``: 1 (the own voxel), 7 (own, -x, +x, -y, +y, -z, +z) or 27 (dz outer, dy middle, dx inner; own = column
+        13)."""
+        if neighbors not in _capi.NEIGHBORS:
+            raise ValueError("neighbors must be 1, 7 or 27")
+        return self._target.lookup(np.asarray(points), neighbors)
+
 
 class _CentroidTree:
     """KDTree(means) of the reference (voxel.py:165): float64 nearest-centroid search on the GPU."""

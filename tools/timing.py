@@ -1,9 +1,9 @@
-"""What the developer probes tools/{radius,fpfh,iss,ransac,compat,ball}_time.py share: HIP events around a call, the library's
+"""What the developer probes tools/{radius,fpfh,iss,ransac,compat,ball,direct}_time.py share: HIP events around a call, the library's
 PCR_*_TIMES lines collected from stderr meanwhile, medians over the timed calls, and the radius for a wanted mean count.
 
-A PCR_*_TIMES line is a prefix (pcr_radius_times, ...), then words and "name value" fields; a phase is a field whose name ends
+A PCR_*_TIMES line is a prefix (pcr_radius_times, ..., pcr_direct_times), then words and "name value" fields; a phase is a field whose name ends
 in _ms: PHASE (a regex) finds them, phase_ms(text) -> [(name, milliseconds)].  tests/test_gpu_stage_times.py pins that format
-(tests/test_gpu_compat.py for pcr_compat_times).
+(tests/test_gpu_compat.py for pcr_compat_times, tests/test_gpu_direct.py for pcr_direct_times).
 
 Importing this module touches no GPU: the context's stream and the two events are made by the first call_ms."""
 import ctypes
@@ -15,7 +15,8 @@ import tempfile
 import numpy as np
 
 WARM, REPS = 2, 5
-PREFIXES = ("pcr_radius_times", "pcr_fpfh_times", "pcr_iss_times", "pcr_ransac_times", "pcr_compat_times", "pcr_ball_times")
+PREFIXES = ("pcr_radius_times", "pcr_fpfh_times", "pcr_iss_times", "pcr_ransac_times", "pcr_compat_times", "pcr_ball_times",
+            "pcr_direct_times")
 PHASE = re.compile(r"\b([a-z_]+_ms) ([0-9.]+)")
 
 _hip = []
