@@ -14,7 +14,7 @@
 //                          (scan_payload.h)
 //   k_color_reduce         sits where k_symm_reduce sits: behind a full search (pass.hip: pcr_rows_search, ICP's) into a match
 //   k_color_fold           buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold,
-//                          match_pass) with ColorArgs as its SIDE, COLOR_W points per lane in flight.
+//                          match_run) with ColorArgs as its SIDE, COLOR_W points per lane in flight.
 //   k_color_robust         the same pass with each of the two rows weighed by a robust kernel of its own r r
 //                          (RobustSide<ColorArgs>, COLOR_ROBUST_W points per lane in flight), folded by k_color_fold
 //   k_color_residuals      both rows' r r of every scan point in the caller's order (match_residuals)

@@ -8,7 +8,7 @@
 //                     usual "eigenvalues -> (eps, 1, 1)", which depends on the normal only -- or PCR_COV_RAW: cov itself.
 //                     Six floats (xx xy xz yy yz zz) per point, written through pt_orig: the INPUT order of the indexed cloud.
 //   k_gicp_reduce     sits where k_rows sits: behind a full search (pass.hip: pcr_rows_search) into a match buffer of the call.
-//   k_gicp_fold       The pass over a match list of match_pass.h (match_reduce, match_fold, match_pass) with GicpArgs as its
+//   k_gicp_fold       The pass over a match list of match_pass.h (match_reduce, match_fold, match_run) with GicpArgs as its
 //                     SIDE -- the scan side and the sums are DistSide's (gicp_weight.h), shared with vgicp.hip -- GICP_W points
 //                     per lane in flight.  The correspondence is ICP's (xform, the matched PtF, residual_f32<true>), the sums
 //                     are acc_ndt's with M6 from icov_closed_form: nothing is restated here.

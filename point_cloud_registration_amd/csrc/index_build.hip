@@ -1175,7 +1175,7 @@ __global__ void __launch_bounds__(256) k_perm_f64(const double *__restrict__ in,
                                                   const PtD *__restrict__ means, double *out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
-    const size_t i = (size_t)__double_as_longlong(means[j].w);
+    const size_t i = key_index(means[j]);
     for (int k = 0; k < sel.n; ++k) out[(size_t)j * sel.n + k] = in[i * stride + sel.c[k]];
 }
 

@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(256) k_nn_fix(const LinArgs a) {
 
 // The ONE writer of a pose in HBM: T and the copies the kernels read (float64 rotation for the Jacobians, float32 rotation /
 // translation for the point transform).  Batched and single results are bit-identical because every pose goes through here
-// (and through host_pose_k in pass.hip, which rounds alike).
+// (and through host_pose_k of pass_device.h, which rounds alike).
 __device__ __forceinline__ void pose_write(PoseDev *p, const double *T) {
     for (int i = 0; i < 16; ++i) p->T[i] = T[i];
     for (int i = 0; i < 3; ++i) {

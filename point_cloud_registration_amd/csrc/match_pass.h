@@ -1,19 +1,28 @@
-// A pass over a match list, stated once: the three-phase reduce loop, the fold, the host driver of the two launches, the
-// pcr_pass_fn around them and the entry points in front of it.  Behind GICP, VGICP, SymmetricICP and ColoredICP (gicp.hip,
-// vgicp.hip, symm.hip, color.hip).  A unit is a SIDE and a UNIT; it keeps its own __global__ one-liners (k_gicp_* / k_vgicp_* /
-// k_symm_* / k_color_*), its *_W and its twenty-odd lines of extern "C" names, each ONE call of a template here.
+// A pass over a match list, stated once: the three-phase reduce loop, the fold, the ONE place that launches a fold, the host
+// driver around it, the pcr_pass_fn around that and the entry points in front of it.  Behind GICP, VGICP, SymmetricICP and
+// ColoredICP (gicp.hip, vgicp.hip, symm.hip, color.hip) and behind VGICP's direct voxel neighbourhoods (vgicp_direct.hip), whose
+// "match list" is a lookup inside the kernel.  A unit is a SIDE and a UNIT; it keeps its own __global__ one-liners (k_gicp_* /
+// k_vgicp_* / k_symm_* / k_color_* / k_vgicp_direct*), its *_W and its extern "C" names, each ONE call of a template here.
 //
-// A UNIT (GicpUnit, VgicpUnit, SymmUnit, ColorUnit) names what the five entry points of a unit differ in -- and nothing else:
+// A UNIT (GicpUnit, VgicpUnit, SymmUnit, ColorUnit; DirectUnit<NB>, derived from VgicpUnit) names what the entry points of a
+// unit differ in -- and nothing else:
 //   Side                      its SIDE
 //   Params, check(&p, raw...) the checked per-call parameter block, for plain and robust calls alike, and the check that fills
-//                             it from the caller's own parameter (MatchUnit: none; symm.hip: min_cos; color.hip: the two roots)
+//                             it from the caller's own parameter (MatchUnit: none; symm.hip: min_cos; color.hip: the two roots;
+//                             vgicp_direct.hip: neighbors, checked and carried by the instantiation)
 //   kind                      the search: PCR_ICP, or PCR_VPLANE
 //   payloads(t, s)            PCR_ERR_NO_TARGET and its message where target or scan lack what the pass reads
-//   side(t, s, p)             the SIDE of a call, everything but rows
-//   reduce, robust, fold, residuals                 the four __global__ one-liners
+//   no_match(t, s, max_dist, &none)                 MatchUnit: never; vgicp_side.h: a target with no kept voxel
+//   matches(&a, &nn, t, s, kind, T, max_dist, flags, caller_order)
+//                             where the correspondences of a call come from: fills LinArgs and the match buffer, or refuses.
+//                             MatchUnit: the full search of `kind` (pass.hip: pcr_rows_search) -- the four units do not mention
+//                             it; vgicp_direct.hip: the lookup data and the LinArgs of the call, no launch
+//   side(t, s, p)             the SIDE of a call, everything but rows; made behind `matches`
+//   reduce, robust, fold, residuals                 the four __global__ one-liners, launched through launch_side, which a unit
+//                             whose kernels take the parts of its SIDE as separate arguments overloads
 //   keys, adaptive                                  the two of the adaptive pass: a key per scan point, the reduce behind the selection
 //   reduce_range, robust_range, residuals_range, adaptive_range     their roctx range names
-//   no_match(t, s, max_dist, &none)                 MatchUnit: never; vgicp.hip: a target with no kept voxel
+//   times(), print_times(ev, n)                     MatchUnit: no bracket; vgicp_direct.hip: PCR_DIRECT_TIMES and its line
 //
 // A SIDE is a unit's kernel-argument struct (GicpArgs, VgicpArgs, SymmArgs, ColorArgs): its arrays, its parameters, rows -- and
 //   Scan                      what phase A carries per scan point beside index and coordinates
@@ -220,19 +229,38 @@ __device__ __forceinline__ void match_residuals(const LinArgs &a, const SIDE &sd
     }
 }
 
-// reduce + fold + 29 doubles back behind a search into `a`: one stream synchronisation, device blocks from the context's
+// How a kernel of the (LinArgs, SIDE, more...) shape is launched, on blocks of 256.  A unit whose kernels take the parts of its
+// SIDE as separate arguments overloads this for its kernel type (vgicp_direct.hip)
+template <typename SIDE, typename... More>
+static void launch_side(void (*kernel)(const LinArgs, const SIDE, More...), dim3 grid, hipStream_t stream, const LinArgs &a, const SIDE &sd,
+                        More... more) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a, sd, more...);
+}
+
+// The ONE place that launches a fold: `reduce` over sd on nb blocks of 256, then `fold` -- one block -- of sd.rows into sums.
+// ev, where a unit hands one in: a mark before the reduce, one between the two launches, one after the fold
+template <typename KERNEL, typename SIDE>
+static void launch_reduce_fold(pcr_context *ctx, KERNEL reduce, void (*fold)(const double *, int, double *),
+                               const LinArgs &a, const SIDE &sd, int nb, double *sums, StageTimes *ev = nullptr) {
+    if (ev) ev->mark(0, ctx->stream);
+    launch_side(reduce, dim3((unsigned)nb), ctx->stream, a, sd);
+    if (ev) ev->mark(1, ctx->stream);
+    hipLaunchKernelGGL(fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)sd.rows, nb, sums);
+    if (ev) ev->mark(2, ctx->stream);
+}
+
+// reduce + fold + 29 doubles back behind the matches of `a`: one stream synchronisation, device blocks from the context's
 // block cache.  sd comes with everything but rows set.
-template <typename SIDE>
-static pcr_status match_launch(pcr_context *ctx, const char *range_name, void (*reduce)(const LinArgs, const SIDE),
-                               void (*fold)(const double *, int, double *), const LinArgs &a, SIDE sd, int64_t n, double out[29]) {
+template <typename KERNEL, typename SIDE>
+static pcr_status match_launch(pcr_context *ctx, const char *range_name, KERNEL reduce,
+                               void (*fold)(const double *, int, double *), const LinArgs &a, SIDE sd, int64_t n, double out[29], StageTimes *ev) {
     const int nb = choose_blocks(ctx, n);            // n and the device only
     DevBuf<double> rows, sums;
     HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
     sd.rows = rows.p;
     {
         RoctxRange range(range_name);
-        hipLaunchKernelGGL(reduce, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, sd);
-        hipLaunchKernelGGL(fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
+        launch_reduce_fold(ctx, reduce, fold, a, sd, nb, sums.p, ev);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, sums.p, 29 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -241,12 +269,21 @@ static pcr_status match_launch(pcr_context *ctx, const char *range_name, void (*
 }
 
 // ---- the entry points, stated once: a UNIT and the templates over it ------------------------------------------------------
-// What a UNIT leaves unsaid (it derives from this): no parameter of its own between max_dist and the flags, and no target
-// without a match
+// What a UNIT leaves unsaid (it derives from this): no parameter of its own between max_dist and the flags, no target
+// without a match, its correspondences from the full search of its kind, no bracket around its launches
 struct MatchUnit {
     struct Params {};
     static pcr_status check(Params *) { return PCR_OK; }
     static pcr_status no_match(const pcr_target *, const pcr_scan *, double, bool *none) { *none = false; return PCR_OK; }
+    // where the correspondences of a call come from: fills *a (and the match buffer behind a->nn_j), or refuses.  The full
+    // search of `kind` (pass.hip: pcr_rows_search) into a match buffer of the call
+    static pcr_status matches(LinArgs *a, DevBuf<uint32_t> *nn, pcr_target *t, pcr_scan *s, int kind, const double T[16], double max_dist,
+                              unsigned flags, bool caller_order) {
+        return pcr_rows_search(a, nn, t, s, kind, T, max_dist, flags, caller_order);
+    }
+    // events around reduce and fold of a linearize / align pass (launch_reduce_fold), and the line that reports them
+    static bool times() { return false; }
+    static void print_times(StageTimes &, int64_t) {}
 };
 
 // the caller's pcr_robust -> RobustK.  NULL or PCR_ROBUST_NONE: the plain pass (kind 0; the scale is not read)
@@ -260,43 +297,36 @@ static inline pcr_status robust_args(const pcr_robust *rb, RobustK *k) {
     return PCR_OK;
 }
 
-// U's full search (pass.hip: pcr_rows_search) into a match buffer of the call, 29 zeros, and -- for a scan with points --
-// match_launch of `reduce` over sd
-template <typename U, typename SIDE>
-static pcr_status match_pass(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, const char *range_name,
-                             void (*reduce)(const LinArgs, const SIDE), const SIDE &sd, double out[29]) {
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
-    for (int i = 0; i < 29; ++i) out[i] = 0.0;
-    if (s->n == 0) return PCR_OK;
-    return match_launch(t->ctx, range_name, reduce, U::fold, a, sd, s->n, out);
-}
-
-// The pcr_pass_fn of a unit (`kind` is not read: the search is U::kind's).  params: what U::check made of the caller's own
+// The pcr_pass_fn of a unit (`kind` is not read: the matches are U::kind's).  params: what U::check made of the caller's own
 // parameter, and the checked kernel of the call -- PCR_ROBUST_NONE: the plain kernel, the plain bits
 template <typename U>
 struct MatchParams {
     typename U::Params unit;
     RobustK rb;
 };
+// U::matches, 29 zeros, and -- for a scan with points -- the SIDE of the call and match_launch of the call's kernel over it
 template <typename U>
 static pcr_status match_run(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned flags, const void *params, double out[29]) {
     const MatchParams<U> *p = (const MatchParams<U> *)params;
     PCR_TRY(U::payloads(t, s));
     bool none;
     PCR_TRY(U::no_match(t, s, max_dist, &none));
-    if (none) {
-        for (int i = 0; i < 29; ++i) out[i] = 0.0;
-        return PCR_OK;
-    }
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    if (!none) PCR_TRY(U::matches(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
+    for (int i = 0; i < 29; ++i) out[i] = 0.0;
+    if (none || s->n == 0) return PCR_OK;
     const typename U::Side sd = U::side(t, s, p->unit);
-    if (p->rb.kind == PCR_ROBUST_NONE) return match_pass<U>(t, s, T, max_dist, flags, U::reduce_range, U::reduce, sd, out);
-    return match_pass<U>(t, s, T, max_dist, flags, U::robust_range, U::robust, RobustSide<typename U::Side>{sd, p->rb}, out);
+    StageTimes ev;
+    HIP_TRY(ev.init(U::times()));
+    if (p->rb.kind == PCR_ROBUST_NONE) PCR_TRY(match_launch(t->ctx, U::reduce_range, U::reduce, U::fold, a, sd, s->n, out, ev.on ? &ev : nullptr));
+    else PCR_TRY(match_launch(t->ctx, U::robust_range, U::robust, U::fold, a, RobustSide<typename U::Side>{sd, p->rb}, s->n, out, ev.on ? &ev : nullptr));
+    if (ev.on) U::print_times(ev, s->n);
+    return PCR_OK;
 }
 
 // The three entry points of a unit behind its five extern "C" names: rb is NULL from the plain ones, raw is the caller's own
-// parameter of the unit (none, min_cos, lambda_geometric).  The order of refusals, the same for every unit: NULL arguments,
+// parameter of the unit (none, min_cos, lambda_geometric, neighbors).  The order of refusals, the same for every unit: NULL arguments,
 // the unit's parameter, the kernel, (residuals) a scan that knows the caller's order, the payloads, what the search refuses.
 // A refused call writes nothing
 template <typename U, typename... Raw>
@@ -322,44 +352,39 @@ static pcr_status match_align(pcr_target *t, pcr_scan *s, const double T_init[16
     return pcr_align_host_loop(match_run<U>, t, s, U::kind, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
 }
 
-// U's full search, as match_pass, and the residual kernel into Side::M doubles per scan point in the caller's order
-template <typename U>
-static pcr_status match_residuals_run(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, const typename U::Side &sd,
-                                      double *s_out) {
-    const size_t m = U::Side::M;
-    LinArgs a;
-    DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, true));
-    if (s->n == 0) return PCR_OK;
-    pcr_context *ctx = t->ctx;
-    DevBuf<double> d;
-    HIP_TRY(d.alloc(m * (size_t)s->n));
-    {
-        RoctxRange range(U::residuals_range);
-        hipLaunchKernelGGL(U::residuals, dim3((unsigned)choose_blocks(ctx, s->n)), dim3(256), 0, ctx->stream, a, sd, (const uint32_t *)s->order, d.p);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s_out, d.p, m * (size_t)s->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
-}
-
-// +inf for every point of a target without a match, whatever else: the squared residuals of match_residuals_run
+// U::matches, as match_run, and the residual kernel into Side::M doubles per scan point in the caller's order; +inf for every
+// point of a target without a match, whatever else
 template <typename U, typename... Raw>
 static pcr_status match_residuals_entry(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double *s_out, Raw... raw) {
     PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
     typename U::Params p;
     PCR_TRY(U::check(&p, raw...));
     PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
+    pcr_context *ctx = t->ctx;
+    CtxScope scope(ctx);
     PCR_TRY(U::payloads(t, s));
     bool none;
     PCR_TRY(U::no_match(t, s, max_dist, &none));
+    const size_t count = (size_t)U::Side::M * (size_t)s->n;
     if (none) {
-        for (int64_t i = 0; i < U::Side::M * s->n; ++i) s_out[i] = (double)INFINITY;
+        for (size_t i = 0; i < count; ++i) s_out[i] = (double)INFINITY;
         return PCR_OK;
     }
-    return match_residuals_run<U>(t, s, T, max_dist, flags, U::side(t, s, p), s_out);
+    LinArgs a;
+    DevBuf<uint32_t> nn;
+    PCR_TRY(U::matches(&a, &nn, t, s, U::kind, T, max_dist, flags, true));
+    if (s->n == 0) return PCR_OK;
+    const typename U::Side sd = U::side(t, s, p);
+    DevBuf<double> d;
+    HIP_TRY(d.alloc(count));
+    {
+        RoctxRange range(U::residuals_range);
+        launch_side(U::residuals, dim3((unsigned)choose_blocks(ctx, s->n)), ctx->stream, a, sd, (const uint32_t *)s->order, d.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s_out, d.p, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PCR_OK;
 }
 
 
@@ -388,7 +413,7 @@ struct AdaptiveParams {
     mutable double *stats_rows;
 };
 
-// search -> key -> select (-> drop, under PCR_ROBUST_TRIM: the correspondences whose stored key is above tau leave the match
+// matches -> key -> select (-> drop, under PCR_ROBUST_TRIM: the correspondences whose stored key is above tau leave the match
 // list of the call) -> reduce -> fold, and 29 + 5 doubles back: one stream synchronisation.  out[28] is m, the number of keys
 // < +inf, which is what the reduce counts -- but for a trim, where it counts the kept ones: n_le by construction
 template <typename U>
@@ -400,7 +425,7 @@ static pcr_status adaptive_pass(pcr_target *t, pcr_scan *s, const double T[16], 
     if (none) { adaptive_nothing(out, stats); return PCR_OK; }
     LinArgs a;
     DevBuf<uint32_t> nn;
-    PCR_TRY(pcr_rows_search(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
+    PCR_TRY(U::matches(&a, &nn, t, s, U::kind, T, max_dist, flags, false));
     adaptive_nothing(out, stats);
     if (s->n == 0) return PCR_OK;
     pcr_context *ctx = t->ctx;
@@ -424,8 +449,7 @@ static pcr_status adaptive_pass(pcr_target *t, pcr_scan *s, const double T[16], 
         PCR_TRY(pcr_select_launch(ctx, keys.p, s->n, p.ad.quantile, 0, p.ad.kind, p.ad.factor, st.p, sums.p + 32));
         if (p.ad.kind == PCR_ROBUST_TRIM) PCR_TRY(pcr_select_drop_launch(ctx, keys.p, s->n, st.p, nn.p, PCR_NONE));
         ev.mark(2, ctx->stream);
-        hipLaunchKernelGGL(U::adaptive, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, asd);
-        hipLaunchKernelGGL(U::fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
+        launch_reduce_fold(ctx, U::adaptive, U::fold, a, asd, nb, sums.p);
     }
     HIP_TRY(hipGetLastError());
     double h[37];

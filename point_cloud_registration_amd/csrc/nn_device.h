@@ -31,6 +31,8 @@
 
 __device__ __forceinline__ uint32_t pt_orig(const float4 &p) { return __float_as_uint(p.w); }
 __device__ __forceinline__ uint32_t pt_orig(const double4 &p) { return (uint32_t)__double_as_longlong(p.w); }
+// the same word of a centroid record of a voxel target, all 64 bits: the key-order index of the kept voxel
+__device__ __forceinline__ size_t key_index(const double4 &m) { return (size_t)__double_as_longlong(m.w); }
 
 template <typename Real> struct RealTraits;
 template <> struct RealTraits<float> {

@@ -284,14 +284,6 @@ static pcr_status pass_setup(Pass *ps, pcr_target *t, pcr_scan *s, int kind, dou
     return PCR_OK;
 }
 
-// T[16] -> what the kernels read of a pose; rounds exactly as the device-side writer does (kernels.hip: pose_write)
-static void host_pose_k(const double T[16], PoseK *k) {
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) { k->R[3 * i + j] = T[4 * i + j]; k->r32[3 * i + j] = (float)T[4 * i + j]; }
-        k->t32[i] = (float)T[4 * i + 3];
-    }
-}
-
 static void pass_set_host_pose(Pass *ps, const double T[16]) {
     host_pose_k(T, &ps->a.hp);
     memcpy(ps->f.R, ps->a.hp.R, sizeof ps->f.R);

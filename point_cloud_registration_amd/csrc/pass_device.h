@@ -16,6 +16,14 @@ struct PoseK {
     float r32[9], t32[3];
     double R[9];
 };
+// T[16] -> what the kernels read of a pose, for every host-driven pass; rounds exactly as the device-side writer does
+// (kernels.hip: pose_write)
+static inline void host_pose_k(const double T[16], PoseK *k) {
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) { k->R[3 * i + j] = T[4 * i + j]; k->r32[3 * i + j] = (float)T[4 * i + j]; }
+        k->t32[i] = (float)T[4 * i + 3];
+    }
+}
 // the transform half of a pose only (the previous pass' pose)
 struct PoseQ {
     float r32[9], t32[3];

@@ -9,7 +9,7 @@
 //                        INPUT order of the indexed cloud, which for a scan's temporary self-index is its device order.
 //   k_symm_perm<TO_DEV>  caller order <-> device order through pcr_scan::order: ScanPayload<3> (scan_payload.h)
 //   k_symm_reduce        sits where k_gicp_reduce sits: behind a full search (pass.hip: pcr_rows_search, ICP's) into a match
-//   k_symm_fold          buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold, match_pass)
+//   k_symm_fold          buffer of the call.  The pass over a match list of match_pass.h (match_reduce, match_fold, match_run)
 //                        with SymmArgs as its SIDE, SYMM_W points per lane in flight.
 //   k_symm_robust        the same pass with every correspondence weighed by a robust kernel of r r (RobustSide<SymmArgs>,
 //                        SYMM_ROBUST_W points per lane in flight), folded by k_symm_fold

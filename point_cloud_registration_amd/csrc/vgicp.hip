@@ -9,7 +9,7 @@
 //   k_vgicp_cov_out    cell-sorted rows back into key order (the inverse of pcr_permute_rows_f64), for the read-back.
 //   k_vgicp_reduce     sits where k_gicp_reduce sits: behind a full float64 centroid search (pass.hip: pcr_rows_search with
 //   k_vgicp_fold       PCR_VPLANE, which needs the voxel normals only) into a match buffer of the call.  The pass over a match
-//                      list of match_pass.h (match_reduce, match_fold, match_pass) with VgicpArgs as its SIDE -- the scan side
+//                      list of match_pass.h (match_reduce, match_fold, match_run) with VgicpArgs as its SIDE -- the scan side
 //                      and the sums are DistSide's (gicp_weight.h), shared with gicp.hip -- VGICP_W points per lane in flight:
 //                      residual_f64<true> on the gathered centroid, gicp_weight, acc_ndt -- nothing is restated here.
 //   k_vgicp_robust     the same pass with M replaced by w M, w a robust kernel of d^T M d (RobustSide<VgicpArgs>,
@@ -18,9 +18,10 @@
 //   k_vgicp_keys       the adaptive pass (include/pcr.h): a key per scan point in device order (match_residuals<., true>)
 //   k_vgicp_adaptive   k_vgicp_robust's reduce behind the selection over the keys (select.hip), its kernel read from the
 //                      selection's state (AdaptiveSide)
-//   VgicpUnit          what the seven entry points differ in -- the target with no kept voxel among it; the rest of them is
-//                      match_pass.h's (match_run, match_linearize, match_align, match_residuals_entry,
-//                      match_linearize_adaptive, match_align_adaptive)
+//   VgicpUnit          (vgicp_side.h) what the seven entry points differ in -- the target with no kept voxel among it; the
+//                      rest of them is match_pass.h's (match_run, match_linearize, match_align, match_residuals_entry,
+//                      match_linearize_adaptive, match_align_adaptive).  vgicp_direct.hip derives its unit from it and
+//                      folds with k_vgicp_fold
 //
 // Target side: pcr_target::vcov, [n][6] float64 in the cell-sorted order of `means`, produced from key-order rows by
 // pcr_permute_rows_f64 exactly as vicov is.  Centroid and covariance stay two arrays (80 bytes per correspondence in two
@@ -28,8 +29,6 @@
 #include <math.h>
 #include <string.h>
 
-#include "gicp_weight.h"
-#include "match_pass.h"
 #include "vgicp_side.h"
 
 // ---- voxel covariances --------------------------------------------------------------------------------------------------
@@ -43,7 +42,7 @@ __global__ void __launch_bounds__(256) k_vgicp_plane_cov(const double *__restric
 __global__ void __launch_bounds__(256) k_vgicp_cov_out(const double *__restrict__ vcov, int64_t n, const PtD *__restrict__ means, double *out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
-    const size_t i = (size_t)__double_as_longlong(means[j].w);      // key-order index of the voxel at cell-sorted position j
+    const size_t i = key_index(means[j]);            // of the voxel at cell-sorted position j
 #pragma unroll
     for (int k = 0; k < 6; ++k) out[6 * i + k] = vcov[6 * (size_t)j + k];
 }
@@ -139,37 +138,7 @@ __global__ void __launch_bounds__(256) k_vgicp_adaptive(const LinArgs a, const A
     match_reduce<VGICP_ROBUST_W>(a, adaptive_side(va));
 }
 
-// ---- the entry points: a UNIT of match_pass.h -------------------------------------------------------------------------
-// The search is VPlaneICP's, over the centroids; a call has no parameter of the unit's own
-struct VgicpUnit : MatchUnit {
-    typedef VgicpArgs Side;
-    static constexpr int kind = PCR_VPLANE;
-    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
-        if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
-        if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
-        if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-        return PCR_OK;
-    }
-    // no kept voxel: no match (and no voxel 0 for the select of phase B) -- once what the search refuses has been refused here
-    static pcr_status no_match(const pcr_target *t, const pcr_scan *s, double max_dist, bool *none) {
-        *none = t->n == 0;
-        if (!*none) return PCR_OK;
-        PCR_REQUIRE(s->ctx == t->ctx, "scan and target belong to different contexts");
-        PCR_REQUIRE(max_dist > 0, "max_dist must be positive");
-        if (t->ctx->comm != nullptr) { pcr_set_error("VGICP passes are not available on a context with a communicator attached"); return PCR_ERR_UNSUPPORTED; }
-        return PCR_OK;
-    }
-    static Side side(const pcr_target *t, const pcr_scan *s, const Params &) { return {{s->cov}, t->vcov, nullptr}; }
-    static constexpr auto reduce = k_vgicp_reduce;
-    static constexpr auto robust = k_vgicp_robust;
-    static constexpr auto fold = k_vgicp_fold;
-    static constexpr auto residuals = k_vgicp_residuals;
-    static constexpr auto keys = k_vgicp_keys;
-    static constexpr auto adaptive = k_vgicp_adaptive;
-    static constexpr const char *reduce_range = "pcr:vgicp_reduce", *robust_range = "pcr:vgicp_robust", *residuals_range = "pcr:vgicp_residuals",
-                                *adaptive_range = "pcr:vgicp_adaptive";
-};
-
+// ---- the entry points: VgicpUnit (vgicp_side.h), a UNIT of match_pass.h ------------------------------------------------
 extern "C" pcr_status pcr_vgicp_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, unsigned flags, double out[29]) {
     return match_linearize<VgicpUnit>(t, s, T, max_dist, nullptr, flags, out);
 }

@@ -2,7 +2,9 @@
 // kept voxel that CONTAINS its transformed position and with that voxel's neighbours -- 1, 7 or 27 voxels, found by integer
 // lookup in the target's sorted hash keys -- and every voxel found contributes one distribution-to-distribution term, exactly
 // the term a correspondence of vgicp.hip contributes (VgicpArgs, vgicp_side.h; DistSide::each, gicp_weight.h).  No search, no
-// match list.  Built BESIDE the hot path like vgicp.hip: kernels.hip, pass.hip, rows.hip, gicp.hip, seam64.hip do not change.
+// match list -- and a unit of match_pass.h all the same: DirectUnit<NB> is VgicpUnit with the lookup where the search was
+// (MatchUnit::matches), so the refusals, the pose, reduce and fold launches, the read-back, the Gauss-Newton loop and the
+// residual read-back are the scaffold's.  This file holds the lookup, the kernels and what the unit differs in.
 //
 //   k_keys_ascend             st_keys ascend strictly (checked once per target)
 //   k_direct_inverse          key_inv[key-order index] = position in `means` / vcov (the inverse of what means[j].w records), so
@@ -12,9 +14,13 @@
 //   k_vgicp_direct<NB>        the pass, one lane per scan point in device order, grid-stride: transform, ALL lookups (the binary
 //   k_vgicp_direct_robust<NB> searches of a point's rows advance together, a step of every row in flight at a time), the hits
 //                             compacted in offset order into a per-lane list in LDS, then one gather + DistSide::each per hit.
-//                             32 float64 accumulators per lane, block_store_partials, folded by k_vgicp_fold (vgicp.hip): no
-//                             atomics, the grid depends on the scan size and the device only -- two calls return the same bits
+//                             32 float64 accumulators per lane, block_store_partials, folded by k_vgicp_fold (vgicp.hip) from
+//                             the one place that launches a fold (match_pass.h: launch_reduce_fold): no atomics, the grid
+//                             depends on the scan size and the device only -- two calls return the same bits
 //   k_vgicp_direct_residuals<NB>   d^T M d of every (point, offset) in the caller's order, +inf where there is no kept pair
+//   DirectSide<NB, S>         the SIDE of a call on the host: S and the lookup arguments, M = NB residuals per point; the kernels
+//                             take the two as separate arguments (launch_side here)
+//   DirectUnit<NB>            the UNIT; the three extern "C" names dispatch on `neighbors` to an instantiation
 //
 // The lookup.  key(c) = row(cy, cz) + cx with row = ((cz P mod M) + cy) P mod M (voxel_build.hip: k_voxel_keys), so the three
 // x-neighbours of a row are the keys k - 1, k, k + 1 and, the keys being sorted and distinct, sit next to each other behind
@@ -24,11 +30,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "gicp_weight.h"
-#include "match_pass.h"
 #include "vgicp_side.h"
-
-__global__ void k_vgicp_fold(const double *__restrict__ rows, int nb, double *out);      // vgicp.hip
 
 #define DIRECT_P 116101LL
 #define DIRECT_M 10000000000LL
@@ -52,7 +54,7 @@ __global__ void __launch_bounds__(256) k_keys_ascend(const long long *__restrict
 __global__ void __launch_bounds__(256) k_direct_inverse(const PtD *__restrict__ means, int64_t n, uint32_t *inv) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
-    const size_t i = (size_t)__double_as_longlong(means[j].w);
+    const size_t i = key_index(means[j]);
     if (i < (size_t)n) inv[i] = (uint32_t)j;
 }
 
@@ -202,9 +204,26 @@ __global__ void __launch_bounds__(256) k_voxel_lookup(const float *__restrict__ 
 }
 
 // ---- the pass ---------------------------------------------------------------------------------------------------------------
-// the positions in means / vcov of the voxels found, DIRECT_NONE where there is none: every load in flight before the first is used
-template <int NB>
-__device__ __forceinline__ void direct_positions(const DirectArgs &da, const int idx[NB], uint32_t j[NB]) {
+// The SIDE of a direct call on the host: S and the lookup arguments, NB squared residuals per scan point.  The kernels take the
+// two apart, (LinArgs, S, DirectArgs, ...) -- with the lookup arguments inside the SIDE the 27-voxel pass kernel measured 2 %
+// slower (docs/EXPERIMENTS.md) -- and launch_side below hands them over that way
+template <int NB, typename S>
+struct DirectSide : S {
+    static constexpr int M = NB;
+    DirectArgs da;
+};
+
+// What both kernels do with scan point i before they part: its loads, its transformed position and j[o] = the position in
+// means / vcov of the kept voxel at offset o, DIRECT_NONE where there is none (every load of `inv` in flight before the first
+// is used)
+template <int NB, typename SIDE>
+__device__ __forceinline__ void direct_point(const LinArgs &a, const SIDE &sd, const DirectArgs &da, int64_t i, float &x, float &y, float &z, typename SIDE::Scan &sc,
+                                             float &tx, float &ty, float &tz, uint32_t j[NB]) {
+    x = a.sx[i]; y = a.sy[i]; z = a.sz[i];
+    sd.load(i, sc);
+    xform(a.hp, x, y, z, tx, ty, tz);
+    int idx[NB];
+    direct_lookup<NB>(da, tx, ty, tz, idx);
 #pragma unroll
     for (int o = 0; o < NB; ++o) j[o] = da.inv[idx[o] >= 0 ? idx[o] : 0];
 #pragma unroll
@@ -220,15 +239,10 @@ __device__ __forceinline__ void direct_reduce(const LinArgs &a, const SIDE &sd, 
     for (int k = 0; k < 32; ++k) acc[k] = 0.0;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += stride) {
-        const float x = a.sx[i], y = a.sy[i], z = a.sz[i];
+        float x, y, z, tx, ty, tz;
         typename SIDE::Scan sc;
-        sd.load(i, sc);
-        float tx, ty, tz;
-        xform(P, x, y, z, tx, ty, tz);
-        int idx[NB];
-        direct_lookup<NB>(da, tx, ty, tz, idx);
         uint32_t j[NB];
-        direct_positions<NB>(da, idx, j);
+        direct_point<NB>(a, sd, da, i, x, y, z, sc, tx, ty, tz, j);
         int cnt = 0;
 #pragma unroll
         for (int o = 0; o < NB; ++o)
@@ -251,21 +265,16 @@ __global__ void __launch_bounds__(256) k_vgicp_direct_robust(const LinArgs a, co
 }
 
 template <int NB>
-__global__ void __launch_bounds__(256) k_vgicp_direct_residuals(const LinArgs a, const VgicpArgs va, const DirectArgs da,
+__global__ void __launch_bounds__(256) k_vgicp_direct_residuals(const LinArgs a, const VgicpArgs sd, const DirectArgs da,
                                                                 const uint32_t *__restrict__ order, double *__restrict__ out) {
     __shared__ uint32_t slots[NB * 256];         // [o][thread]
     const PoseK &P = a.hp;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += stride) {
-        const float x = a.sx[i], y = a.sy[i], z = a.sz[i];
+        float x, y, z, tx, ty, tz;
         VgicpArgs::Scan sc;
-        va.load(i, sc);
-        float tx, ty, tz;
-        xform(P, x, y, z, tx, ty, tz);
-        int idx[NB];
-        direct_lookup<NB>(da, tx, ty, tz, idx);
         uint32_t j[NB];
-        direct_positions<NB>(da, idx, j);
+        direct_point<NB>(a, sd, da, i, x, y, z, sc, tx, ty, tz, j);
 #pragma unroll
         for (int o = 0; o < NB; ++o) slots[o * 256 + threadIdx.x] = j[o];
         const int64_t dest = order ? (int64_t)order[i] : i;
@@ -275,21 +284,34 @@ __global__ void __launch_bounds__(256) k_vgicp_direct_residuals(const LinArgs a,
             const uint32_t jo = slots[o * 256 + threadIdx.x];
             if (jo != DIRECT_NONE) {
                 VgicpArgs::Match m;
-                va.gather(a, jo, m);
-                va.each(a, P, x, y, z, tx, ty, tz, sc, m, VgicpArgs::Resid(&s, P, x, y, z));
+                sd.gather(a, jo, m);
+                sd.each(a, P, x, y, z, tx, ty, tz, sc, m, VgicpArgs::Resid(&s, P, x, y, z));
             }
             out[NB * dest + o] = s;
         }
     }
 }
 
-// ---- the driver ---------------------------------------------------------------------------------------------------------------
+// The launch adapter: a direct kernel by its host-side SIDE (launch_side of match_pass.h, overloaded on the kernel's shape)
+template <int NB, typename S, typename... More>
+static void launch_side(void (*kernel)(const LinArgs, const S, const DirectArgs, More...), dim3 grid, hipStream_t stream, const LinArgs &a,
+                        const DirectSide<NB, S> &sd, More... more) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a, (const S &)sd, sd.da, more...);
+}
+template <int NB, typename S>
+static void launch_side(void (*kernel)(const LinArgs, const RobustSide<S>, const DirectArgs), dim3 grid, hipStream_t stream, const LinArgs &a,
+                        const RobustSide<DirectSide<NB, S>> &sd) {
+    const RobustSide<S> rsd = {(const S &)sd, sd.rb};
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, a, rsd, sd.da);
+}
+
+// ---- the entry points: a UNIT of match_pass.h, derived from VGICP's ---------------------------------------------------------------
 static pcr_status check_neighbors(int nb) {
     PCR_REQUIRE(nb == 1 || nb == 7 || nb == 27, "neighbors must be 1, 7 or 27");
     return PCR_OK;
 }
 
-// STATEMENT with NB = the checked nb as a constant
+// STATEMENT with NB = nb as a constant (an nb that check_neighbors refuses: any one of them)
 #define DIRECT_WITH_NB(nb, STATEMENT)                                  \
     do {                                                               \
         if ((nb) == 1) { constexpr int NB = 1; STATEMENT; }            \
@@ -297,138 +319,73 @@ static pcr_status check_neighbors(int nb) {
         else { constexpr int NB = 27; STATEMENT; }                     \
     } while (0)
 
-struct DirectParams {
-    int nb;
-    RobustK rb;
-};
-
-// what a direct call refuses behind its own parameters, in the order the nearest-centroid entry points refuse it: the payloads,
-// then what their search refuses
-static pcr_status direct_refuse(const pcr_target *t, const pcr_scan *s, double max_dist) {
-    if (!t->is_voxel) { pcr_set_error("VGICP needs a voxel target"); return PCR_ERR_NO_TARGET; }
-    if (!t->vcov) { pcr_set_error("VGICP target has no covariances (pcr_target_voxels_set_covariances)"); return PCR_ERR_NO_TARGET; }
-    if (!s->cov) { pcr_set_error("VGICP scan has no covariances (pcr_scan_estimate_covariances / _set_covariances)"); return PCR_ERR_NO_TARGET; }
-    PCR_TRY(direct_has_keys(t));
-    PCR_REQUIRE(s->ctx == t->ctx, "scan and target belong to different contexts");
-    PCR_REQUIRE(max_dist > 0, "max_dist must be positive");
-    if (t->ctx->comm != nullptr) { pcr_set_error("VGICP passes are not available on a context with a communicator attached"); return PCR_ERR_UNSUPPORTED; }
-    return PCR_OK;
+// PCR_DIRECT_TIMES=1 (developer, tools/direct_time.py): events around the pass kernel and the fold, their milliseconds on
+// stderr.  Read once per process, whatever the neighbourhoods
+static bool direct_times() {
+    static const bool times = env_flag("PCR_DIRECT_TIMES");
+    return times;
 }
 
-// what the kernels read of a call (LinArgs: the scan, the centroids, the gate, the pose).  The pose is rounded as pass.hip's
-// host_pose_k rounds it for every host-driven pass (R as it is, r32 / t32 = (float) of the entry; that function is local to
-// pass.hip, which this unit leaves alone -- tests/test_gpu_direct.py holds the two together: the pairs of a pass are those of
-// the lookup at the float32 transform).  No flag bit of the caller reaches the kernels: nothing here reads LinArgs::flags, and
-// its upper bits are internal switches of the pass kernels
-static void direct_lin(const pcr_target *t, const pcr_scan *s, const double T[16], double max_dist, LinArgs *a) {
-    memset(a, 0, sizeof *a);
-    a->sx = s->x; a->sy = s->y; a->sz = s->z; a->n = s->n;
-    a->means = t->means;
-    a->md_f = (float)max_dist; a->md_d = max_dist;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) { a->hp.R[3 * i + j] = T[4 * i + j]; a->hp.r32[3 * i + j] = (float)T[4 * i + j]; }
-        a->hp.t32[i] = (float)T[4 * i + 3];
+// VgicpUnit with the lookup in the place of the search: its payloads and the keys; what the search would refuse, refused here
+// for EVERY target; `matches` launches nothing; fold and loop are VGICP's.  (keys / adaptive are not this unit's: there is no
+// adaptive direct pass.)
+template <int NB>
+struct DirectUnit : VgicpUnit {
+    typedef DirectSide<NB, VgicpArgs> Side;
+    static pcr_status check(Params *, int neighbors) { return check_neighbors(neighbors); }
+    static pcr_status payloads(const pcr_target *t, const pcr_scan *s) {
+        PCR_TRY(VgicpUnit::payloads(t, s));
+        return direct_has_keys(t);
     }
-}
-
-// the pcr_pass_fn: one launch and the fold
-static pcr_status direct_run(pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned, const void *params, double out[29]) {
-    const DirectParams *p = (const DirectParams *)params;
-    PCR_TRY(direct_refuse(t, s, max_dist));
-    double o[29];                                    // (a pass refused further down writes nothing)
-    for (int i = 0; i < 29; ++i) o[i] = 0.0;
-    if (t->n > 0 && s->n > 0) {
+    static pcr_status no_match(const pcr_target *t, const pcr_scan *s, double max_dist, bool *none) {
+        PCR_TRY(refuse_as_search(t, s, max_dist));
+        *none = t->n == 0;
+        return PCR_OK;
+    }
+    // What the kernels read of a call (LinArgs: the scan, the centroids, the gate, the pose), behind the lookup data of the
+    // target, which the first call builds -- or refuses -- before the SIDE of the call is made.  An empty scan builds nothing.
+    // No flag bit of the caller reaches the kernels: nothing here reads LinArgs::flags, and its upper bits are internal
+    // switches of the pass kernels
+    static pcr_status matches(LinArgs *a, DevBuf<uint32_t> *, pcr_target *t, pcr_scan *s, int, const double T[16], double max_dist, unsigned, bool) {
+        if (s->n == 0) return PCR_OK;
         pcr_context *ctx = t->ctx;
         HIP_TRY(hipSetDevice(ctx->device));
-        PCR_TRY(pcr_ensure_scratch(ctx, s->n));
+        PCR_TRY(pcr_ensure_scratch(ctx, s->n));          // (fixes ctx->max_blocks: before choose_blocks)
         PCR_TRY(direct_prepare(t));
-        LinArgs a;
-        direct_lin(t, s, T, max_dist, &a);
-        const DirectArgs da = direct_args(t);
-        const int nb = choose_blocks(ctx, s->n);         // n and the device only
-        DevBuf<double> rows, sums;
-        HIP_TRY(rows.alloc(32 * (size_t)nb)); HIP_TRY(sums.alloc(32));
-        const VgicpArgs sd = {{s->cov}, t->vcov, rows.p};
-        const RobustK rb = p->rb;
-        // PCR_DIRECT_TIMES=1 (developer, tools/direct_time.py): events around the pass kernel and the fold, their milliseconds on stderr
-        static const bool times = env_flag("PCR_DIRECT_TIMES");
-        StageTimes ev;
-        HIP_TRY(ev.init(times));
-        {
-            RoctxRange range(rb.kind == PCR_ROBUST_NONE ? "pcr:vgicp_direct" : "pcr:vgicp_direct_robust");
-            const RobustSide<VgicpArgs> rsd = {sd, rb};
-            ev.mark(0, ctx->stream);
-            if (rb.kind == PCR_ROBUST_NONE) DIRECT_WITH_NB(p->nb, hipLaunchKernelGGL(k_vgicp_direct<NB>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, sd, da));
-            else DIRECT_WITH_NB(p->nb, hipLaunchKernelGGL(k_vgicp_direct_robust<NB>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, a, rsd, da));
-            ev.mark(1, ctx->stream);
-            hipLaunchKernelGGL(k_vgicp_fold, dim3(1), dim3(64), 0, ctx->stream, (const double *)rows.p, nb, sums.p);
-            ev.mark(2, ctx->stream);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(o, sums.p, 29 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ev.on) fprintf(stderr, "pcr_direct_times n %lld neighbors %d kernel_ms %.4f fold_ms %.4f\n", (long long)s->n, p->nb, ev.ms(0), ev.ms(1));
+        memset(a, 0, sizeof *a);
+        a->sx = s->x; a->sy = s->y; a->sz = s->z; a->n = s->n;
+        a->means = t->means;
+        a->md_f = (float)max_dist; a->md_d = max_dist;
+        host_pose_k(T, &a->hp);
+        return PCR_OK;
     }
-    for (int i = 0; i < 29; ++i) out[i] = o[i];
-    return PCR_OK;
-}
+    static Side side(const pcr_target *t, const pcr_scan *s, const Params &p) { return {VgicpUnit::side(t, s, p), direct_args(t)}; }
+    static constexpr auto reduce = k_vgicp_direct<NB>;
+    static constexpr auto robust = k_vgicp_direct_robust<NB>;
+    static constexpr auto residuals = k_vgicp_direct_residuals<NB>;
+    static constexpr const char *reduce_range = "pcr:vgicp_direct", *robust_range = "pcr:vgicp_direct_robust",
+                                *residuals_range = "pcr:vgicp_direct_residuals";
+    static bool times() { return direct_times(); }
+    static void print_times(StageTimes &ev, int64_t n) {
+        fprintf(stderr, "pcr_direct_times n %lld neighbors %d kernel_ms %.4f fold_ms %.4f\n", (long long)n, NB, ev.ms(0), ev.ms(1));
+    }
+};
 
 extern "C" pcr_status pcr_vgicp_direct_linearize(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, int neighbors,
                                                  const pcr_robust *rb_or_null, unsigned flags, double out[29]) {
-    PCR_REQUIRE(t && s && T && out, "NULL argument");
-    DirectParams p;
-    PCR_TRY(check_neighbors(neighbors));
-    p.nb = neighbors;
-    PCR_TRY(robust_args(rb_or_null, &p.rb));
-    CtxScope scope(t->ctx);
-    return direct_run(t, s, PCR_VPLANE, T, max_dist, flags, &p, out);
+    DIRECT_WITH_NB(neighbors, return match_linearize<DirectUnit<NB>>(t, s, T, max_dist, rb_or_null, flags, out, neighbors));
 }
 
 extern "C" pcr_status pcr_vgicp_direct_align(pcr_target *t, pcr_scan *s, const double T_init[16], int max_iter, double tol, double max_dist,
                                              int neighbors, const pcr_robust *rb_or_null, unsigned flags, double T_out[16], int *iterations,
                                              double *trace_or_null) {
-    PCR_REQUIRE(t && s && T_init && T_out, "NULL argument");
-    DirectParams p;
-    PCR_TRY(check_neighbors(neighbors));
-    p.nb = neighbors;
-    PCR_TRY(robust_args(rb_or_null, &p.rb));
-    CtxScope scope(t->ctx);
-    return pcr_align_host_loop(direct_run, t, s, PCR_VPLANE, &p, T_init, max_iter, tol, max_dist, flags, T_out, iterations, trace_or_null);
+    DIRECT_WITH_NB(neighbors, return match_align<DirectUnit<NB>>(t, s, T_init, max_iter, tol, max_dist, rb_or_null, flags, T_out, iterations,
+                                                                 trace_or_null, neighbors));
 }
 
 extern "C" pcr_status pcr_vgicp_direct_residuals(pcr_target *t, pcr_scan *s, const double T[16], double max_dist, int neighbors, unsigned flags,
                                                  double *s_out) {
-    (void)flags;                                     // (no flag changes what this call computes)
-    PCR_REQUIRE(t && s && T && (s_out || s->n == 0), "NULL argument");
-    PCR_TRY(check_neighbors(neighbors));
-    PCR_REQUIRE(pcr_scan_knows_order(s), PCR_NEED_ORDER);
-    CtxScope scope(t->ctx);
-    PCR_TRY(direct_refuse(t, s, max_dist));
-    if (s->n == 0) return PCR_OK;
-    const size_t count = (size_t)neighbors * (size_t)s->n;
-    if (t->n == 0) {
-        for (size_t i = 0; i < count; ++i) s_out[i] = (double)INFINITY;
-        return PCR_OK;
-    }
-    pcr_context *ctx = t->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    PCR_TRY(pcr_ensure_scratch(ctx, s->n));
-    PCR_TRY(direct_prepare(t));
-    LinArgs a;
-    direct_lin(t, s, T, max_dist, &a);
-    const DirectArgs da = direct_args(t);
-    const VgicpArgs sd = {{s->cov}, t->vcov, nullptr};
-    DevBuf<double> d;
-    HIP_TRY(d.alloc(count));
-    {
-        RoctxRange range("pcr:vgicp_direct_residuals");
-        const dim3 grid((unsigned)choose_blocks(ctx, s->n));
-        DIRECT_WITH_NB(neighbors, hipLaunchKernelGGL(k_vgicp_direct_residuals<NB>, grid, dim3(256), 0, ctx->stream, a, sd, da, (const uint32_t *)s->order, d.p));
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s_out, d.p, count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PCR_OK;
+    DIRECT_WITH_NB(neighbors, return match_residuals_entry<DirectUnit<NB>>(t, s, T, max_dist, flags, s_out, neighbors));
 }
 
 extern "C" pcr_status pcr_target_voxels_lookup(pcr_target *t, const float *xyz, int64_t m, int neighbors, int64_t *idx) {
